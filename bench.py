@@ -18,7 +18,8 @@ to GPU 0, all timed over exactly --steps steps (strong scaling; rccl_world_size 
 the gathered outputs equal the same batch scored on GPU 0 alone are in rccl_strong).  Every rank
 scoring its own resident 1M pairs with no data movement is reported beside it as weak_value.
 C5 on the whole front end (the PE read set scattered, seeding -> chaining -> extension on every
-rank, records gathered) follows in `c5` when --budget-s and every rank's free HBM allow it.
+rank, records gathered) follows in `c5` with --full, when --budget-s and every rank's free HBM
+allow it.
 
 Reported beside the metric:
   roofline     -- dominant kernel (pc_kernel<160> on C2), integer-VALU bound: algorithmic ops
@@ -26,9 +27,16 @@ Reported beside the metric:
                   launch / HIP-event-timed launch duration, vs the gfx950 packed-int16 VALU
                   peak; traffic = HBM bytes per launch from the rocprofv3 PMC passes of THIS
                   workload (profiles/pmc_latest.json keyed by roofline.pmc_key), else null.
-  cpu_baseline -- oracle/bsw_sse41.c (restated upstream SSE4.1 getScores16 design, "port")
-                  on a bounded sample of the same batch; best of {affinity set, cgroup quota,
-                  16} threads (model, core count and quota recorded), rank 0, N = 1 only.
+  cpu_baseline -- (--full) oracle/bsw_sse41.c (restated upstream SSE4.1 getScores16 design,
+                  "port") on a bounded sample of the same batch; best of {affinity set, cgroup
+                  quota, 16} threads (model, core count and quota recorded), rank 0, N = 1 only.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps,
+writes the last step's outputs when --dump-outputs DIR is given and prints its line (the roofline
+object comes from the timed steps' own launch times: no run of its own).  Every other leg --
+cpu_baseline, the host-buffer rates (abi_inclusive*), the C++ per-call curve, the wide-kernel
+comparison of long reads, the C5 sub-object at N > 1, the CPU legs of the other workloads --
+runs only with --full.
 """
 
 from __future__ import annotations
@@ -201,6 +209,33 @@ def node_extrapolation(rate, threads):
         return None
     return {"value": round(rate / threads * phys, 4), "physical_cores": phys,
             "note": "EXTRAPOLATED, not measured: the measured rate per thread x the node's physical cores (lscpu)"}
+
+
+DUMP_MAX_BYTES = 64_000_000        # --dump-outputs: all files of one run together
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: `arrays` (name -> ndarray; a structured array gives one entry per field,
+    <name>.<field>) as dirname/<name>.npy in float64 (every output here is an integer below 2^53:
+    exact).  Past DUMP_MAX_BYTES in all, every array keeps the same fraction
+    of its rows, drawn once per array by a generator seeded with a constant and kept in order, so
+    two runs with the same arguments write the same rows."""
+    flat = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.names:
+            for f in a.dtype.names:
+                flat[f"{name}.{f}"] = a[f]
+        else:
+            flat[name] = a
+    total = sum(8 * v.size for v in flat.values())
+    keep = min(1.0, DUMP_MAX_BYTES / max(1, total))
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in flat.items():
+        if keep < 1.0 and v.ndim >= 1:
+            rows = np.sort(np.random.default_rng(20240607).choice(len(v), int(len(v) * keep), replace=False))
+            v = v[rows]
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def _timed(fn, reps):
@@ -441,7 +476,21 @@ def main():
                     help="allow more ranks than visible GPUs (ranks share GPUs; rehearsal only)")
     ap.add_argument("--dump", default="", help="strong: rank 0 writes the gathered outputs here (.npy); c4 / "
                                                "c4mem: every rank writes <dump>.rank<r>.npz")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg beside the timed steps: the CPU baselines, the host-buffer "
+                         "(drop-in ABI) rates and the C++ per-call curve, the wide-kernel comparison of long reads, "
+                         "the C5 sub-object at N > 1.  Off by default: a plain run sets up, warms up, times --steps "
+                         "steps and prints its line (--no-cpu / --no-host-path drop single legs of a --full run)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step computed (the arrays its "
+                         "caller receives) as DIR/<name>.npy in float64, at most 64 MB in all (a fixed seeded "
+                         "sample of the rows of a larger output); weak-scaling workloads only")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_host_path = True
+        args.c5_reads = 0
+    if args.dump_outputs and args.scaling == "strong":
+        raise SystemExit("bench.py: --dump-outputs covers the weak-scaling workloads (strong: --dump)")
     c2_default = args.workload == "c2" and args.scaling == "weak"
     if args.steps is None:
         args.steps = 100 if c2_default else 10
@@ -512,6 +561,9 @@ def main():
 
     res = np.empty_like(pairs)
     d_pairs.download(res)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step wrote into the resident SeqPair records (rank 0's batch)
+        dump_outputs(args.dump_outputs, {f: res[f] for f in bsw.OUT_FIELDS})
     # N > 1: the HEADLINE is the RCCL batch scatter (BASELINE configs[4]): one batch resident on
     # GPU 0, scattered over the ranks by RCCL, scored, outputs gathered back -- timed over exactly
     # --steps steps after --warmup; the weak rate above (every rank its own resident 1M pairs, no
@@ -588,7 +640,7 @@ def main():
         "roofline": roof,
         "kernel_only_value": round(args.pairs * world / (kms_mean * 1e-3) / 1e6, 3),
     }
-    if wave and world == 1:
+    if wave and world == 1 and args.full:
         # the same resident batch on the int32 wide kernel (BSW_OPT_LONG 0): what long queries
         # ran on before the wave kernel
         e0 = bsw.Engine(device=local, long=0)
@@ -1270,6 +1322,8 @@ def main_c4(args, rank, local, world):
     d_out.download(out)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out": out})
     st = bsw.ext_last_stats(eng)
     value = n_ext_all / dt_max / 1e6
     # PCIe-inclusive (reads + seeds up, regions down; resident reference) and host-built rates
@@ -1377,6 +1431,8 @@ def main_c4pe(args, rank, local, world):
     ext = d_ext.download(ext_buf)
     if args.dump:                                    # every rank: its shard's regions (tests)
         np.savez(f"{args.dump}.rank{rank}.npz", out=out, ext=ext)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": out, "ext": ext})
     # the host-array form (bsw_chain2aln_device: seeds up, regions down inside the call)
     t = time.perf_counter()
     for _ in range(2):
@@ -1635,6 +1691,8 @@ def main_mem(args, rank, local, world, c1: bool):
         sr[so:so + nk] += a
     if args.dump:                                    # every rank: its shard's seeds and regions (tests)
         np.savez(f"{args.dump}.rank{rank}.npz", seeds=seeds, sr=sr, sc=sc, out=out, ext=ext)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"seeds": seeds, "sr": sr, "sc": sc, "out": out, "ext": ext})
     if rank != 0:
         return
     st = sts[-1]
@@ -1793,6 +1851,8 @@ def main_mate(args, rank, local, world):
     d_aln.download(aln)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"aln": aln})
     st = sts[-1]
     fwd_ms = float(np.mean([x.fwd_ms for x in sts]))
     rev_ms = float(np.mean([x.rev_ms for x in sts]))
@@ -1874,6 +1934,10 @@ def main_global(args, rank, local, world):
     d_nc.download(nc)
     if rank != 0:
         return
+    if args.dump_outputs:
+        # the CIGAR words past a job's n_cigar are not written by the call: zeroed here
+        dump_outputs(args.dump_outputs, {"score": res["score"], "n_cigar": nc,
+                                         "cigar": np.where(np.arange(stride)[None, :] < nc[:, None], cig, 0)})
     st = sts[-1]
     kms = float(np.mean([x.kernel_ms for x in sts]))
     value = args.jobs * world * args.steps / dt_max / 1e6
@@ -2022,6 +2086,8 @@ def main_smem(args, rank, local, world):
     if rank != 0:
         return
     cnt = d_cnt.download(np.zeros(args.reads, dtype=np.int32))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"n_mems": cnt})     # (the interval rows: compared by the oracle check below)
     kernel_ms = float(np.median(kms))
     value = args.reads * world * args.steps / dt_max / 1e6
     sys.path.insert(0, os.path.join(ROOT, "oracle"))

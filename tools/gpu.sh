@@ -9,7 +9,8 @@
 #   testsall        the whole -m gpu suite without -x (every failure listed; a GPU fault still ends it)
 #   smoke           __graft_entry__.smoke()
 #   bench           the default bench line (driver form: python bench.py)
-#   bench:<args>    bench.py with extra arguments (commas for spaces: bench:--workload,c1)
+#   bench:<args>    bench.py with extra arguments (commas for spaces: bench:--workload,c1;
+#                   bench:--full adds the CPU baseline, host-path and per-call legs to the line)
 #   torchrun:<N>:<args>  bench.py --gpus N under torchrun (N ranks; --rehearse shares the box's GPU)
 #   prof            rocprofv3 kernel trace + PMC passes of a short C2 bench (tools/profile.sh)
 #   prof:<args>     the same over bench.py <args> (commas for spaces)
