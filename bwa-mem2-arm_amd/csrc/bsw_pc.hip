@@ -45,7 +45,7 @@ constexpr int kPcChunkDw = 17;           // dwords per lane per 64-row target ch
 #define BSW_PC_EXP_HALFHEAD 0
 #endif
 #ifdef BSW_PC_STATS
-__device__ unsigned long long g_pc_stats[8];
+__device__ unsigned long long g_pc_stats[11];
 // per-wave schedule record (tools/pc_times.py): start / end (s_memrealtime, 100 MHz), XCC id and
 // HW_ID (CU / SIMD / SE), rows run -- the launch's occupancy over time, ramp-up and tail
 constexpr int kPcTimesMax = 1 << 16;
@@ -582,6 +582,74 @@ __device__ __forceinline__ int pc_lastpos(std::integer_sequence<int, G...>, cons
     return (int)max(lp & 0xffffu, lp >> 16);
 }
 
+// Early stop: a lane whose band has reached the query's end (end == qlen) and
+// left column 0 (beg > 0) retires once no cell of any later row can reach gscore (hence best):
+// every later value is a path from one of this row's slots whose only gains are diagonal steps,
+// at most 1 each (the pk_ok contract: match 1, the same fact the A.5 gate of PC_PH1 rests on) and
+// at most qlen - 1 - j of them from column j.
+//   BSW_PC_EARLY_STOP 0 : off (the literal loop; make ab AB_FLAGS=-DBSW_PC_EARLY_STOP=0)
+//   scalar bound        : UB = m + min(qlen - 1 - beg, tlen - 1 - i), selects at the row end
+//   per-cell bound      : UB = max over slots s in (beg, end] of H(i, s-1) + (qlen - s), a packed
+//                         scan (BSW_PC_EARLY_SCAN 0: scalar bound only) behind one ballot
+#ifndef BSW_PC_EARLY_STOP
+#define BSW_PC_EARLY_STOP 1
+#endif
+#ifndef BSW_PC_EARLY_SCAN
+#define BSW_PC_EARLY_SCAN 1
+#endif
+// rows on which a lane may ask for the scan: (i & BSW_PC_SCAN_PHASE) == BSW_PC_SCAN_PHASE, a
+// wave-uniform test (3: every fourth row; 0, 1, 7 and 15 measured in DESIGN.md §4.5)
+#ifndef BSW_PC_SCAN_PHASE
+#define BSW_PC_SCAN_PHASE 3
+#endif
+
+// one plane register of the per-cell bound (slots 2K, 2K+1) of a lane with end == qlen:
+// c = H + (qlen - s), cleared where s > qlen (= end: the gain's sign) or s <= beg, ub = max(ub, c).
+// H <= 255 and 0 <= qlen - s < QMAX on the kept slots: the unsigned max is exact.
+template <int K>
+__device__ __forceinline__ void pc_ub_reg(uint32_t hv, uint32_t qw, uint32_t begw, uint32_t &ub)
+{
+    constexpr uint32_t SC = (uint32_t)(2 * K) | ((uint32_t)(2 * K + 1) << 16);
+    uint32_t c, m;
+    asm volatile(
+        "v_pk_sub_i16 %[c], %[qw], %[sc]\n\t"               // qlen - s
+        "v_pk_ashrrev_i16 %[m], 15, %[c] op_sel_hi:[0,1]\n\t"  // s > qlen
+        "v_pk_add_u16 %[c], %[c], %[h]\n\t"
+        "v_bfi_b32 %[c], %[m], 0, %[c]\n\t"
+        "v_pk_sub_i16 %[m], %[bg], %[sc]\n\t"               // beg - s < 0  <=>  s > beg
+        "v_pk_ashrrev_i16 %[m], 15, %[m] op_sel_hi:[0,1]\n\t"
+        "v_and_b32_e32 %[c], %[c], %[m]\n\t"
+        "v_pk_max_u16 %[ub], %[ub], %[c]\n\t"
+        : [ub] "+v"(ub), [c] "=&v"(c), [m] "=&v"(m)
+        : [h] "v"(hv), [qw] "v"(qw), [sc] "s"(SC), [bg] "v"(begw));
+}
+
+template <int QMAX, bool BY, int GG>
+__device__ __forceinline__ void pc_ub_group(const uint32_t (&hh)[(BY ? QMAX / 4 : QMAX / 2)], uint32_t qw,
+                                            uint32_t begw, uint32_t &ub, uint64_t enter)
+{
+    if (!((enter >> GG) & 1)) return;                     // uniform: outside [min beg, max end]
+    if constexpr (BY) {
+        pc_ub_reg<2 * GG + 1>(__builtin_amdgcn_perm(hh[GG], hh[GG], kSelHi), qw, begw, ub);
+        pc_ub_reg<2 * GG>(__builtin_amdgcn_perm(hh[GG], hh[GG], kSelLo), qw, begw, ub);
+    } else {
+        pc_ub_reg<2 * GG + 1>(hh[2 * GG + 1], qw, begw, ub);
+        pc_ub_reg<2 * GG>(hh[2 * GG], qw, begw, ub);
+    }
+}
+
+// the per-cell bound of every lane with end == qlen over its slots (beg, end], registers from the
+// one holding slot max(end) down to the one holding min beg (the row's entered set)
+template <int QMAX, bool BY, int... G>
+__device__ __forceinline__ int pc_ubscan(std::integer_sequence<int, G...>, const uint32_t (&hh)[(BY ? QMAX / 4 : QMAX / 2)],
+                                         int qlen, int beg, uint64_t enter)
+{
+    uint32_t ub = 0;
+    const uint32_t qw = pack2(qlen), begw = pack2(beg);
+    (pc_ub_group<QMAX, BY, QMAX / 4 - 1 - G>(hh, qw, begw, ub, enter), ...);
+    return (int)max(ub & 0xffffu, ub >> 16);
+}
+
 // WPB waves per workgroup: with 1, a wave's slot (and its LDS) is reused as soon as that wave
 // ends, instead of when the slowest of its block's waves ends.
 template <int QMAX, int WPB, bool BY>
@@ -678,6 +746,10 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
     }
     int best = h0, best_i = -1, best_j = -1, max_ie = -1, gsc = -1, moff = 0, endc = qlen;
     bool alive = valid && tlen > 0;
+    // an invalid lane stores nothing: kept as a null pair pointer, not as a lane mask that would
+    // hold an SGPR pair across the row loop (the loop has none to spare: it was spilled to a VGPR)
+    if (!valid) sp = nullptr;
+    asm volatile("" : "+v"(sp));          // made here: the select is not sunk below the loop with its mask
     // target bases HBM -> LDS by LDS-DMA, 64-row chunks double-buffered (as the lane kernel)
     const uint8_t *tp = ref + idr;
     const int tsh = (int)((uintptr_t)tp & 3);
@@ -705,6 +777,8 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
     if constexpr (BY || (BSW_PC_JKEY && QMAX >= 128)) asm volatile("" : "+v"(bs.ka), "+v"(bs.kb));
 #ifdef BSW_PC_STATS
     uint32_t nrows = 0, nlast = 0, nue = 0;
+    uint32_t nscan = 0, nstop_s = 0, nstop_c = 0;   // early stop: scan rows; this lane retired by bound
+    (void)nscan; (void)nstop_s; (void)nstop_c;
 #endif
 
 #if BSW_PC_EXP_HALFHEAD
@@ -814,6 +888,47 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
                 best_j = better ? mj : best_j;
                 best = better ? m : best;
             }
+#if BSW_PC_EARLY_STOP
+            {   // early stop, after this row's best / gscore updates.  gsc <= best
+                // always (gsc is an H value of some row, best >= every row's maximum), so UB < gsc
+                // covers UB <= best; both are written as the rule states them.  Selects only.
+                // (the three differences by inline asm: written in C++, the loop-invariant parts
+                // qlen - 1, tlen - 1 and the scan's packed qlen are hoisted into registers that
+                // live across the groups, which costs the 96 and 64 classes a wave per SIMD)
+                int gq, gt, gm;                    // qlen - beg, tlen - i, qlen - mj
+                asm volatile("v_sub_u32_e32 %0, %3, %4\n\t"
+                             "v_subrev_u32_e32 %1, %5, %6\n\t"
+                             "v_sub_u32_e32 %2, %3, %7"
+                             : "=&v"(gq), "=&v"(gt), "=&v"(gm)
+                             : "v"(qlen), "v"(beg), "s"(i), "v"(tlen), "v"(mj));
+                const bool edge = end == qlen && gq < qlen;    // beg > 0, from the opaque difference: a
+                                                               // test of beg is made at the row head and
+                                                               // its mask kept across the groups
+                const int ubs = m - 1 + min(gq, gt);
+                const bool stop = edge && ubs <= best && ubs < gsc;
+#ifdef BSW_PC_STATS
+                nstop_s += alive && stop;
+#endif
+                alive = alive && !stop;
+#if BSW_PC_EARLY_SCAN
+                // the per-cell bound, on rows of one phase (wave-uniform: every fourth) and only for lanes
+                // whose arg-max cell already passes it (a necessary condition: false all along the
+                // diagonal phase, true right after it).  Not for QMAX <= 64: there the scan's
+                // registers cost the int16 form its fourth wave per SIMD (127 -> 137 VGPRs)
+                const int ubm = m - 1 + gm;
+                const bool want = QMAX > 64 && alive && edge && ubm <= best && ubm < gsc;
+                if (QMAX > 64 && (i & BSW_PC_SCAN_PHASE) == BSW_PC_SCAN_PHASE && __ballot(want)) {
+                    const int ubc = pc_ubscan<QMAX, BY>(std::make_integer_sequence<int, NG>{}, hh, gq + beg, beg, r.enter);
+                    const bool stopc = want && ubc <= best && ubc < gsc;
+#ifdef BSW_PC_STATS
+                    nscan += 1;
+                    nstop_c += stopc;
+#endif
+                    alive = alive && !stopc;
+                }
+#endif
+            }
+#endif
 #ifdef BSW_PC_STATS
             nrows += act;
             nue += act && (emax == emin);  // every live lane has the same band end
@@ -838,6 +953,9 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
         const unsigned rows = (unsigned)wave_max((int)nrows);
         const unsigned nl = (unsigned)wave_max((int)nlast);
         const unsigned nu = (unsigned)wave_max((int)nue);
+        const unsigned ns = (unsigned)wave_max((int)nscan);               // uniform: rows the scan ran on
+        const unsigned rs = (unsigned)__popcll(__ballot(nstop_s != 0));   // lanes retired by the scalar bound
+        const unsigned rc = (unsigned)__popcll(__ballot(nstop_c != 0));   // ... by the per-cell bound
         unsigned cmax[4];
         for (int k = 0; k < 4; ++k) cmax[k] = (unsigned)wave_max((int)ctr[k]);   // the longest lane
         if ((threadIdx.x & 63) == 0) {
@@ -846,6 +964,9 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
             atomicAdd(&g_pc_stats[5], (unsigned long long)nl);
             atomicAdd(&g_pc_stats[6], 1ull);
             atomicAdd(&g_pc_stats[7], (unsigned long long)nu);
+            atomicAdd(&g_pc_stats[8], (unsigned long long)ns);
+            atomicAdd(&g_pc_stats[9], (unsigned long long)rs);
+            atomicAdd(&g_pc_stats[10], (unsigned long long)rc);
         }
         const unsigned wid = blockIdx.x * WPB + (threadIdx.x >> 6);
         if ((threadIdx.x & 63) == 0 && wid < (unsigned)kPcTimesMax) {
@@ -859,7 +980,7 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
         }
     }
 #endif
-    if (valid) {
+    if (sp) {
         sp->score = best;
         sp->tle = best_i + 1;
         sp->gtle = max_ie + 1;
@@ -870,12 +991,13 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
 }
 
 #ifdef BSW_PC_STATS
-// [rows, groups entered, fast, masked-R, masked-L, lastpos scans, waves, uniform-end rows] summed over waves
+// [rows, groups entered, fast, masked-R, masked-L, lastpos scans, waves, uniform-end rows, early-stop scan
+// rows, lanes retired by the scalar bound, lanes retired by the per-cell bound] summed over waves
 extern "C" int bsw_pc_stats(unsigned long long *out, int reset)
 {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pc_stats), 8 * sizeof(unsigned long long)) != hipSuccess) return -5;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pc_stats), 11 * sizeof(unsigned long long)) != hipSuccess) return -5;
     if (reset) {
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        unsigned long long z[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_pc_stats), z, sizeof(z)) != hipSuccess) return -5;
     }
     return 0;
