@@ -16,8 +16,13 @@ SYNTH    := $(LIBDIR)/libbsw_synth.so
 SHIMTEST := $(LIBDIR)/bsw_shim_example
 ORACLE   := oracle/liboracle.so
 
-HIP_SRCS := $(CSRC)/bsw_kernels.hip $(CSRC)/bsw_pc.hip $(CSRC)/bsw_wv.hip $(CSRC)/bsw_gq.hip $(CSRC)/bsw_mate.hip $(CSRC)/bsw_global.hip $(CSRC)/bsw_ext_dev.hip $(CSRC)/bsw_fmi.hip $(CSRC)/bsw_fmi_build.hip $(CSRC)/bsw_memchain.hip $(CSRC)/bsw_chain.hip $(CSRC)/bsw_host.cpp $(CSRC)/bsw_ext.cpp $(CSRC)/bsw_pack.cpp $(CSRC)/bsw_devcache.cpp
-HIP_HDRS := $(CSRC)/bsw_devcache.h $(CSRC)/bsw_pool.h $(CSRC)/bsw_kernels.h $(CSRC)/bsw_mate_k.h include/bsw_mate.h $(CSRC)/bsw_global_k.h include/bsw_global.h $(CSRC)/bsw_ext_k.h $(CSRC)/bsw_wave.h $(CSRC)/bsw_internal.h $(CSRC)/bsw_fmi_internal.h include/bsw.h include/bsw_seqpair.h include/bsw_ext.h include/bsw_batch.h include/bsw_fmi.h
+HIP_HDRS := $(CSRC)/bsw_devcache.h $(CSRC)/bsw_pool.h $(CSRC)/bsw_kernels.h $(CSRC)/bsw_mate_k.h include/bsw_mate.h $(CSRC)/bsw_global_k.h include/bsw_global.h $(CSRC)/bsw_ext_k.h $(CSRC)/bsw_wave.h $(CSRC)/bsw_internal.h $(CSRC)/bsw_engine.h $(CSRC)/bsw_fmi_internal.h include/bsw.h include/bsw_seqpair.h include/bsw_ext.h include/bsw_batch.h include/bsw_fmi.h
+
+# the product's objects; the experiment libraries below are this list with one object swapped
+OBJS := $(addprefix $(LIBDIR)/,bsw_kernels.o bsw_pc.o bsw_wv.o bsw_gq.o bsw_mate.o bsw_global.o bsw_ext_dev.o \
+          bsw_fmi.o bsw_fmi_build.o bsw_memchain.o bsw_chain.o bsw_dispatch.o bsw_pipeline.o bsw_host.o bsw_ext.o \
+          bsw_pack.o bsw_devcache.o bsw_batch.o)
+LINK  = $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(1) -lpthread
 
 all: product synth oracle percall
 
@@ -33,41 +38,13 @@ oracle: $(ORACLE)
 $(LIBDIR):
 	mkdir -p $(LIBDIR)
 
-$(LIBDIR)/bsw_kernels.o: $(CSRC)/bsw_kernels.hip $(HIP_HDRS) | $(LIBDIR)
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(HIP_HDRS) | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBDIR)/bsw_pc.o: $(CSRC)/bsw_pc.hip $(HIP_HDRS) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/bsw_wv.o: $(CSRC)/bsw_wv.hip $(HIP_HDRS) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/bsw_gq.o: $(CSRC)/bsw_gq.hip $(HIP_HDRS) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/bsw_mate.o: $(CSRC)/bsw_mate.hip $(HIP_HDRS) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/bsw_global.o: $(CSRC)/bsw_global.hip $(HIP_HDRS) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/bsw_ext_dev.o: $(CSRC)/bsw_ext_dev.hip $(HIP_HDRS) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/bsw_fmi.o: $(CSRC)/bsw_fmi.hip $(HIP_HDRS) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/bsw_chain.o: $(CSRC)/bsw_chain.hip $(HIP_HDRS) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/bsw_memchain.o: $(CSRC)/bsw_memchain.hip $(HIP_HDRS) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/bsw_fmi_build.o: $(CSRC)/bsw_fmi_build.hip $(HIP_HDRS) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/bsw_host.o: $(CSRC)/bsw_host.cpp $(HIP_HDRS) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
+# hipcc-compiled .cpp (bsw_host.cpp as HIP; bsw_ext.cpp and bsw_pack.cpp have g++ rules of their own below)
+$(LIBDIR)/%.o: $(CSRC)/%.cpp $(HIP_HDRS) | $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) $(XHIP) -c $< -o $@
+$(LIBDIR)/bsw_host.o: XHIP := -x hip
 
 $(LIBDIR)/bsw_ext.o: $(CSRC)/bsw_ext.cpp $(HIP_HDRS) | $(LIBDIR)
 	g++ -O3 -std=c++17 -fPIC -Wall -Iinclude -c $< -o $@
@@ -75,14 +52,11 @@ $(LIBDIR)/bsw_ext.o: $(CSRC)/bsw_ext.cpp $(HIP_HDRS) | $(LIBDIR)
 $(LIBDIR)/bsw_pack.o: $(CSRC)/bsw_pack.cpp $(CSRC)/bsw_internal.h | $(LIBDIR)
 	g++ -O3 -std=c++17 -fPIC -Wall -Iinclude -c $< -o $@
 
-$(LIBDIR)/bsw_devcache.o: $(CSRC)/bsw_devcache.cpp $(CSRC)/bsw_devcache.h | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
 $(LIBDIR)/bsw_batch.o: $(CSRC)/bsw_batch.c include/bsw_batch.h include/bsw.h | $(LIBDIR)
 	gcc $(CFLAGS) -std=c11 -c $< -o $@
 
-$(PRODUCT): $(LIBDIR)/bsw_kernels.o $(LIBDIR)/bsw_pc.o $(LIBDIR)/bsw_wv.o $(LIBDIR)/bsw_gq.o $(LIBDIR)/bsw_mate.o $(LIBDIR)/bsw_global.o $(LIBDIR)/bsw_ext_dev.o $(LIBDIR)/bsw_fmi.o $(LIBDIR)/bsw_fmi_build.o $(LIBDIR)/bsw_memchain.o $(LIBDIR)/bsw_chain.o $(LIBDIR)/bsw_host.o $(LIBDIR)/bsw_ext.o $(LIBDIR)/bsw_pack.o $(LIBDIR)/bsw_devcache.o $(LIBDIR)/bsw_batch.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
+$(PRODUCT): $(OBJS)
+	$(call LINK,$^)
 
 $(SYNTH): $(CSRC)/bsw_synth.c include/bsw_seqpair.h | $(LIBDIR)
 	gcc $(CFLAGS) -shared -o $@ $<
@@ -99,27 +73,19 @@ STATSLIB := $(LIBDIR)/libbsw_hip_stats.so
 stats: $(STATSLIB)
 $(LIBDIR)/bsw_pc_stats.o: $(CSRC)/bsw_pc.hip $(HIP_HDRS) | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -DBSW_PC_STATS -c $< -o $@
-$(STATSLIB): $(LIBDIR)/bsw_kernels.o $(LIBDIR)/bsw_pc_stats.o $(LIBDIR)/bsw_wv.o $(LIBDIR)/bsw_gq.o $(LIBDIR)/bsw_mate.o $(LIBDIR)/bsw_global.o $(LIBDIR)/bsw_ext_dev.o $(LIBDIR)/bsw_fmi.o $(LIBDIR)/bsw_fmi_build.o $(LIBDIR)/bsw_memchain.o $(LIBDIR)/bsw_chain.o $(LIBDIR)/bsw_host.o $(LIBDIR)/bsw_ext.o $(LIBDIR)/bsw_pack.o $(LIBDIR)/bsw_devcache.o $(LIBDIR)/bsw_batch.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
+$(STATSLIB): $(subst bsw_pc.o,bsw_pc_stats.o,$(OBJS))
+	$(call LINK,$^)
 
-# experiment build: the product with bsw_pc.hip compiled under AB_FLAGS (same-box A/B runs: tools/ab_lib.sh)
-ABLIB := $(LIBDIR)/libbsw_hip_ab.so
+# experiment builds: the product with one file compiled under AB_FLAGS (same-box A/B runs:
+# tools/ab_lib.sh) -- ab: bsw_pc.hip -> libbsw_hip_ab.so; abhost: bsw_pipeline.hip (host pipeline,
+# host_shard) -> libbsw_hip_abhost.so; abfmi: bsw_fmi.hip (SMEM walk) -> libbsw_hip_abfmi.so
 AB_FLAGS ?=
-ab:
-	$(HIPCC) $(HIPFLAGS) $(AB_FLAGS) -c $(CSRC)/bsw_pc.hip -o $(LIBDIR)/bsw_pc_ab.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(ABLIB) $(LIBDIR)/bsw_kernels.o $(LIBDIR)/bsw_pc_ab.o $(LIBDIR)/bsw_wv.o $(LIBDIR)/bsw_gq.o $(LIBDIR)/bsw_mate.o $(LIBDIR)/bsw_global.o $(LIBDIR)/bsw_ext_dev.o $(LIBDIR)/bsw_fmi.o $(LIBDIR)/bsw_fmi_build.o $(LIBDIR)/bsw_memchain.o $(LIBDIR)/bsw_chain.o $(LIBDIR)/bsw_host.o $(LIBDIR)/bsw_ext.o $(LIBDIR)/bsw_pack.o $(LIBDIR)/bsw_devcache.o $(LIBDIR)/bsw_batch.o -lpthread
-
-# the same for bsw_host.cpp (host pipeline experiments): libbsw_hip_abhost.so
-ABHOSTLIB := $(LIBDIR)/libbsw_hip_abhost.so
-abhost:
-	$(HIPCC) $(HIPFLAGS) $(AB_FLAGS) -x hip -c $(CSRC)/bsw_host.cpp -o $(LIBDIR)/bsw_host_ab.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(ABHOSTLIB) $(LIBDIR)/bsw_kernels.o $(LIBDIR)/bsw_pc.o $(LIBDIR)/bsw_wv.o $(LIBDIR)/bsw_gq.o $(LIBDIR)/bsw_mate.o $(LIBDIR)/bsw_global.o $(LIBDIR)/bsw_ext_dev.o $(LIBDIR)/bsw_fmi.o $(LIBDIR)/bsw_fmi_build.o $(LIBDIR)/bsw_memchain.o $(LIBDIR)/bsw_chain.o $(LIBDIR)/bsw_host_ab.o $(LIBDIR)/bsw_ext.o $(LIBDIR)/bsw_pack.o $(LIBDIR)/bsw_devcache.o $(LIBDIR)/bsw_batch.o -lpthread
-
-# the same for bsw_fmi.hip (SMEM walk experiments): libbsw_hip_abfmi.so
-ABFMILIB := $(LIBDIR)/libbsw_hip_abfmi.so
-abfmi:
-	$(HIPCC) $(HIPFLAGS) $(AB_FLAGS) -c $(CSRC)/bsw_fmi.hip -o $(LIBDIR)/bsw_fmi_ab.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(ABFMILIB) $(LIBDIR)/bsw_kernels.o $(LIBDIR)/bsw_pc.o $(LIBDIR)/bsw_wv.o $(LIBDIR)/bsw_gq.o $(LIBDIR)/bsw_mate.o $(LIBDIR)/bsw_global.o $(LIBDIR)/bsw_ext_dev.o $(LIBDIR)/bsw_fmi_ab.o $(LIBDIR)/bsw_fmi_build.o $(LIBDIR)/bsw_memchain.o $(LIBDIR)/bsw_chain.o $(LIBDIR)/bsw_host.o $(LIBDIR)/bsw_ext.o $(LIBDIR)/bsw_pack.o $(LIBDIR)/bsw_devcache.o $(LIBDIR)/bsw_batch.o -lpthread
+AB_SRC_ab := bsw_pc
+AB_SRC_abhost := bsw_pipeline
+AB_SRC_abfmi := bsw_fmi
+ab abhost abfmi:
+	$(HIPCC) $(HIPFLAGS) $(AB_FLAGS) -c $(CSRC)/$(AB_SRC_$@).hip -o $(LIBDIR)/$(AB_SRC_$@)_ab.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/libbsw_hip_$@.so $(subst $(AB_SRC_$@).o,$(AB_SRC_$@)_ab.o,$(OBJS)) -lpthread
 
 .PHONY: all product synth oracle percall clean stats ab abfmi abhost
 

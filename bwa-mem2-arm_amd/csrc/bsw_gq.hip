@@ -151,7 +151,7 @@ __device__ __forceinline__ int gq_init_h(int j, int h0, int qlen, int oe_ins, in
 // pair for 16-lane groups (4 per wave), 512 B for quads (16 per wave: 8 KB of LDS per wave).
 __host__ __device__ constexpr int gq_tmax(int gs) { return gs >= 16 ? 1024 : 512; }
 
-// Same int16 bounds as the wave kernel (bsw_host.cpp wv_class); the whole query is resident,
+// Same int16 bounds as the wave kernel (bsw_dispatch.hip wv_class); the whole query is resident,
 // so the band cap only limits [beg, end).
 __host__ __device__ __forceinline__ bool gq_eligible(const KParams &kp, int qlen, int tlen, int h0, int qmax,
                                                      int tmax)

@@ -38,11 +38,12 @@ int chain_rounds_device(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint8_t 
                         const int32_t *d_sr, const int32_t *d_sc, int32_t ns, bsw_alnreg_t *d_out, int32_t *d_ext,
                         bsw_chain_stats_t *cs);
 // staging packers (bsw_pack.cpp): nibbles (dst[k] = src[2k] & 15 | (src[2k+1] & 15) << 4) and
-// 2-bit codes + exception words (pos0 + k) << 4 | (src[k] & 15) for bytes outside 0..3
+// 2-bit codes (src[k] & 3) + one exception word (pos0 + k) << 2 | (src[k] >> 2 & 3) per byte
+// outside 0..3, ascending (the staging kernels patch code bits 2-3 from them, bsw_pipeline.hip)
 void pack_nibbles(uint8_t *dst, const uint8_t *src, size_t nbytes);
 void pack_2bit(uint8_t *dst, const uint8_t *src, size_t nbytes, uint32_t pos0, std::vector<uint32_t> &exc);
-// host pipeline fast path (bsw_host.cpp host_shard_fast): plan_kernel's schedule key of the
-// packed-column class for pairs [0, n) -- (255 - qlen) << 20 | (1 - related) << 19 |
+// plan_kernel's schedule key (bsw_dispatch.hip) of the packed-column class computed on the host
+// for pairs [0, n) -- (255 - qlen) << 20 | (1 - related) << 19 |
 // (63 - tlen / 32) << 13 | (31 - seed identities) << 8 | (255 - h0), identities as the device's
 // seed_matches (best of 13 shifts of query[10, 40) against target[4 + s, 34 + s))
 void fast_keys(const SeqPair *pairs, int32_t n, const uint8_t *ref, const uint8_t *qer, uint32_t *keys);

@@ -1,4 +1,4 @@
-// bsw_pack.cpp -- host-side code packing of the bsw_get_scores staging pipeline (bsw_host.cpp):
+// bsw_pack.cpp -- host-side code packing of the bsw_get_scores staging pipeline (bsw_pipeline.hip):
 // nibbles and 2-bit codes + exception words, written into the pinned staging buffer with
 // streaming stores.  Plain C++ (g++), so the AVX2 form can be selected at run time without the
 // HIP device pass seeing x86 target attributes.
@@ -145,7 +145,7 @@ void pack_2bit(uint8_t *dst, const uint8_t *src, size_t nbytes, uint32_t pos0, s
     else pack_2bit_sse2(dst, src, nbytes, pos0, exc);
 }
 
-// seed identities (plan_kernel's seed_matches, bsw_host.cpp): best over shifts s = 0..12 of the
+// seed identities (plan_kernel's seed_matches, bsw_dispatch.hip): best over shifts s = 0..12 of the
 // matches of query[10, 40) with target[4 + s, 34 + s); 31 when the pair is too short to test
 static int seed_matches_scalar(const uint8_t *q, int qlen, const uint8_t *r, int tlen)
 {

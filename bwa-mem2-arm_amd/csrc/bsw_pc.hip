@@ -19,7 +19,7 @@
 // = 34 VALU per 4 cells, against 47 for the lane kernel's fast group.  ~200 VGPRs at
 // QMAX = 160: two waves per SIMD (the occupancy the packed two-pairs-per-lane kernel lacks).
 //
-// Eligibility (planner, bsw_host.cpp): pk_ok scoring, h0 + min(qlen, tlen) <= 255 (H <= 255:
+// Eligibility (planner, bsw_dispatch.hip): pk_ok scoring, h0 + min(qlen, tlen) <= 255 (H <= 255:
 // the 8-bit key H << 8 | j and the 16-bit lanes), qlen < QMAX (slot qlen inside a group).
 //
 // Band edges (per lane [beg, end)): a group is FAST when every live lane has all
