@@ -20,6 +20,7 @@
 #include "../../include/bsw.h"
 #include "../../include/bsw_mate.h"
 #include "../../include/bsw_global.h"
+#include "../../include/bsw_aln.h"
 #include "bsw_kernels.h"
 #include "bsw_internal.h"
 
@@ -129,6 +130,7 @@ struct PlanCall {
 };
 
 struct ExtState;
+struct AlnState;
 // Everything one call needs on one device.  Members are destroyed in reverse order: buffers, then
 // events, then streams.
 struct BSW_HIDDEN Slot {
@@ -180,6 +182,13 @@ struct BSW_HIDDEN Slot {
     DevBuf<uint8_t> d_xq, d_xt;
     DevBuf<ExtState> d_xst;
     DevBuf<int64_t> d_xwin;             // per-read target windows (ext_scan)
+    // final alignments (bsw_aln.h)
+    DevBuf<AlnState> d_ast;             // per-region band-loop state
+    DevBuf<int32_t> d_alist;            // compact DP job lists of two passes (ping-pong), n_regs each
+    DevBuf<int32_t> d_acnt;             // their job counts
+    DevBuf<SeqPair> d_apairs;
+    DevBuf<uint8_t> d_aq, d_at;         // per-job query / reference codes
+    DevBuf<uint8_t> d_aio;              // host form: the staged inputs and outputs
     bool timed = false;
     hipStream_t run_stream = nullptr;   // stream of the last run_device (finish_stats waits on it)
     bsw_stats_t stats{};
@@ -344,6 +353,7 @@ struct bsw_ctx {
     bsw_chain_stats_t chain_last{};
     bsw_mate_stats_t mate_last{};
     bsw_global_stats_t glob_last{};
+    bsw_aln_stats_t aln_last{};
     struct Pinned { std::mutex mu; bsw::PinnedBuf<uint8_t> b; } pin[2];
     int glob_band = 0;                  // BSW_OPT_GLOB_BAND
     int64_t ext_chunk = 0;              // BSW_OPT_EXT_CHUNK (0: the int32-offset bound)

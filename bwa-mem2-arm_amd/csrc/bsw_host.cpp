@@ -27,6 +27,7 @@
 #include "bsw_mate_k.h"
 #include "bsw_global_k.h"
 #include "bsw_ext_k.h"
+#include "bsw_aln_k.h"
 
 namespace bsw {
 
@@ -1044,5 +1045,207 @@ const char *bsw_strerror(int code)
 }
 
 int bsw_abi_version(void) { return BSW_ABI_VERSION; }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- final alignments (bsw_aln.h)
+namespace bsw {
+
+static_assert(kAlnMetaSpread * 16 <= kMetaMaxq && kMetaMaxq + kAlnCntWords <= kMetaWords, "aln meta fits d_meta");
+
+// plan + gap-free -> per pass: build -> ksw_global2 (glob_device) -> finish.  Everything on `st`;
+// the host waits once for the plan's counts and once per pass for the next pass's job count.
+static int reg2aln_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st, const bsw_ext_opt_t &opt,
+                          const uint8_t *d_reads, const int64_t *d_read_off, const int32_t *d_read_len,
+                          int32_t n_reads, const bsw_alnreg_t *d_regs, const int32_t *d_reg_read, int32_t n,
+                          bsw_aln_t *d_aln, uint32_t *d_cigar, int32_t cigar_stride, uint8_t *d_md,
+                          int32_t md_stride, bsw_aln_stats_t &as)
+{
+    const bsw_params_t &pr = ctx->params;
+    AlnParams p{};
+    p.W = opt.w; p.a = pr.mat[0];
+    p.o_del = pr.o_del; p.e_del = pr.e_del; p.o_ins = pr.o_ins; p.e_ins = pr.e_ins;
+    p.n_reads = n_reads;
+    p.cigar_stride = cigar_stride; p.md_stride = md_stride;
+    p.ref_len = dc.refres_len; p.l_pac = opt.l_pac;
+    memcpy(p.mat, pr.mat, 25);
+    GlobParams gp;
+    make_glob_params(pr, ctx->glob_band, gp);
+    BSW_TRY(s.d_ast.grow((size_t)n));
+    BSW_TRY(s.d_alist.grow(2 * (size_t)n));
+    BSW_TRY(s.d_acnt.grow(kAlnCntWords));
+    if (!s.ev2) BSW_TRY(hipEventCreate(&s.ev2.p));
+    if (!s.ev3) BSW_TRY(hipEventCreate(&s.ev3.p));
+    int32_t *h_cnt = s.h_meta + kMetaMaxq;
+    float ms = 0.f;
+    BSW_TRY(hipEventRecord(s.ev2, st));
+    BSW_TRY(launch_aln_plan(p, d_read_len, d_regs, d_reg_read, n, s.d_ast, s.d_alist, s.d_acnt, s.d_meta, d_aln, st));
+    BSW_TRY(hipMemcpyAsync(s.h_meta, s.d_meta, kAlnMetaSpread * 16 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_cnt, s.d_acnt, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    // (regions the plan found in error are marked rejected: the gap-free kernel skips them)
+    BSW_TRY(launch_aln_gapfree(p, d_reads, d_read_off, d_read_len, d_regs, d_reg_read, n, s.d_ast, dc.d_refres, d_aln,
+                               d_cigar, d_md, st));
+    BSW_TRY(hipEventRecord(s.ev3, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(hipEventElapsedTime(&ms, s.ev2, s.ev3));
+    as.helper_ms += ms;
+    int32_t m[5] = {0, 0, 0, 0, 0};
+    for (int sl = 0; sl < kAlnMetaSpread; ++sl) {
+        const int32_t *v = s.h_meta + sl * 16;
+        m[0] |= v[0]; m[1] += v[1]; m[2] += v[2]; m[3] = std::max(m[3], v[3]); m[4] = std::max(m[4], v[4]);
+    }
+    if (m[0]) return BSW_E_RANGE;
+    as.n_rejected = m[1];
+    as.n_gapfree = m[2];
+    p.qstride = std::max(m[3], 1);                      // longest DP query / reference span
+    p.tstride = std::max(m[4], 1);
+    int32_t nj = h_cnt[0];
+    for (int pass = 0; pass < 3 && nj > 0; ++pass) {
+        as.n_dp[pass] = nj;
+        const int32_t *list = s.d_alist + (size_t)(pass & 1) * n;
+        int32_t *next = s.d_alist + (size_t)((pass + 1) & 1) * n;
+        // SeqPair idr / idq are int32: chunk so j * stride stays below 2^31
+        const int32_t chunk = (int32_t)std::min<int64_t>(nj, (int64_t)INT32_MAX / std::max(p.tstride, p.qstride) - 1);
+        BSW_TRY(s.d_apairs.grow((size_t)chunk));
+        BSW_TRY(s.d_aq.grow((size_t)chunk * p.qstride));
+        BSW_TRY(s.d_at.grow((size_t)chunk * p.tstride));
+        BSW_TRY(s.d_gcig.grow((size_t)chunk * (size_t)cigar_stride));
+        BSW_TRY(s.d_gncig.grow((size_t)chunk));
+        for (int32_t a = 0; a < nj; a += chunk) {
+            const int32_t b = std::min(nj, a + chunk);
+            BSW_TRY(hipEventRecord(s.ev2, st));
+            BSW_TRY(launch_aln_build(p, d_reads, d_read_off, d_regs, d_reg_read, s.d_ast, list + a, b - a, dc.d_refres,
+                                     s.d_apairs, s.d_aq, s.d_at, st));
+            BSW_TRY(hipEventRecord(s.ev3, st));
+            bsw_global_stats_t gs;
+            if (int r = glob_device(gp, s, s.d_apairs, s.d_at, s.d_aq, b - a, s.d_gcig, cigar_stride, s.d_gncig, st, &gs))
+                return r;
+            as.dp_ms += gs.kernel_ms;
+            {
+                std::lock_guard<std::mutex> g(ctx->stats_mu);   // (bsw_global_last_stats: the last DP batch)
+                ctx->glob_last = gs;
+            }
+            BSW_TRY(hipEventElapsedTime(&ms, s.ev2, s.ev3));
+            as.helper_ms += ms;
+            BSW_TRY(hipEventRecord(s.ev2, st));
+            BSW_TRY(launch_aln_finish(p, d_read_len, d_regs, d_reg_read, s.d_ast, list + a, b - a, s.d_apairs, s.d_aq,
+                                      s.d_at, s.d_gcig, s.d_gncig, next, s.d_acnt + pass + 1, d_aln, d_cigar, d_md, st));
+            BSW_TRY(hipEventRecord(s.ev3, st));
+            BSW_TRY(hipMemcpyAsync(h_cnt, s.d_acnt + pass + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            BSW_TRY(hipStreamSynchronize(st));
+            BSW_TRY(hipEventElapsedTime(&ms, s.ev2, s.ev3));
+            as.helper_ms += ms;
+        }
+        nj = pass < 2 ? h_cnt[0] : 0;
+    }
+    return BSW_OK;
+}
+
+// argument checks shared by both forms; the caller holds dc.refmu shared
+static int reg2aln_check(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, DeviceCtx &dc, int32_t n_reads, int32_t n_regs,
+                         int32_t cigar_stride, const void *md, int32_t md_stride)
+{
+    if (n_reads < 0 || n_regs < 0 || cigar_stride < 1 || md_stride < 0 || (md == nullptr) != (md_stride == 0))
+        return BSW_E_INVAL;
+    if (!dc.d_refres) return BSW_E_INVAL;
+    if (opt->w < 0 || opt->w > (1 << 28) || opt->l_pac < 0 || (opt->l_pac > 0 && dc.refres_len != 2 * opt->l_pac))
+        return BSW_E_INVAL;
+    return BSW_OK;
+}
+
+static void set_aln_stats(bsw_ctx_t *ctx, const bsw_aln_stats_t &as)
+{
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    ctx->aln_last = as;
+}
+
+}  // namespace bsw
+
+extern "C" {
+
+int bsw_reg2aln_resident(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint8_t *d_reads,
+                         const int64_t *d_read_off, const int32_t *d_read_len, int32_t n_reads,
+                         const bsw_alnreg_t *d_regs, const int32_t *d_reg_read, int32_t n_regs,
+                         bsw_aln_t *d_aln, uint32_t *d_cigar, int32_t cigar_stride, uint8_t *d_md,
+                         int32_t md_stride, void *stream)
+{
+    if (!ctx || !opt) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the resident reference stays put
+    if (const int rc = bsw::reg2aln_check(ctx, opt, dc, n_reads, n_regs, cigar_stride, d_md, md_stride)) return rc;
+    if (n_regs > 0 && (!d_reads || !d_read_off || !d_read_len || !d_regs || !d_reg_read || !d_aln || !d_cigar))
+        return BSW_E_INVAL;
+    bsw_aln_stats_t as{};
+    as.n_regs = n_regs;
+    if (n_regs > 0) {
+        const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+            hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+            return bsw::reg2aln_device(ctx, dc, s, st, *opt, d_reads, d_read_off, d_read_len, n_reads, d_regs,
+                                       d_reg_read, n_regs, d_aln, d_cigar, cigar_stride, d_md, md_stride, as);
+        });
+        if (rc) return rc;
+    }
+    bsw::set_aln_stats(ctx, as);
+    return BSW_OK;
+}
+
+int bsw_reg2aln(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint8_t *reads, const int64_t *read_off,
+                const int32_t *read_len, int32_t n_reads, const bsw_alnreg_t *regs, const int32_t *reg_read,
+                int32_t n_regs, bsw_aln_t *aln, uint32_t *cigar, int32_t cigar_stride, uint8_t *md,
+                int32_t md_stride)
+{
+    if (!ctx || !opt) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::reg2aln_check(ctx, opt, dc, n_reads, n_regs, cigar_stride, md, md_stride)) return rc;
+    if (n_regs > 0 && (!reads || !read_off || !read_len || !regs || !reg_read || !aln || !cigar)) return BSW_E_INVAL;
+    bsw_aln_stats_t as{};
+    as.n_regs = n_regs;
+    if (n_regs > 0) {
+        int64_t rbytes = 0;
+        for (int32_t i = 0; i < n_reads; ++i) {
+            if (read_off[i] < 0 || read_len[i] < 0) return BSW_E_RANGE;
+            rbytes = std::max<int64_t>(rbytes, read_off[i] + read_len[i]);
+        }
+        // one staged blob: inputs, then outputs, each part 16-B aligned
+        const size_t n = (size_t)n_regs, nr = (size_t)n_reads;
+        const size_t part[8] = {(size_t)rbytes, nr * sizeof(int64_t), nr * sizeof(int32_t), n * sizeof(bsw_alnreg_t),
+                                n * sizeof(int32_t), n * sizeof(bsw_aln_t), n * (size_t)cigar_stride * sizeof(uint32_t),
+                                n * (size_t)md_stride};
+        size_t off[9] = {0};
+        for (int k = 0; k < 8; ++k) off[k + 1] = off[k] + ((part[k] + 15) & ~(size_t)15);
+        const void *src[5] = {reads, read_off, read_len, regs, reg_read};
+        void *dst[3] = {aln, cigar, md};
+        const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+            BSW_TRY(s.d_aio.grow(off[8] + 16));
+            uint8_t *b = s.d_aio;
+            // (rows the kernels leave unwritten -- rejected regions, overflows -- read back as zeros)
+            BSW_TRY(hipMemsetAsync(b + off[6], 0, off[8] - off[6], s.stream));
+            for (int k = 0; k < 5; ++k)
+                if (part[k]) BSW_TRY(hipMemcpyAsync(b + off[k], src[k], part[k], hipMemcpyHostToDevice, s.stream));
+            if (int r = bsw::reg2aln_device(ctx, dc, s, s.stream, *opt, b + off[0], (const int64_t *)(b + off[1]),
+                                            (const int32_t *)(b + off[2]), n_reads, (const bsw_alnreg_t *)(b + off[3]),
+                                            (const int32_t *)(b + off[4]), n_regs, (bsw_aln_t *)(b + off[5]),
+                                            (uint32_t *)(b + off[6]), cigar_stride, md ? b + off[7] : nullptr,
+                                            md_stride, as))
+                return r;
+            for (int k = 0; k < 3; ++k)
+                if (part[5 + k]) BSW_TRY(hipMemcpyAsync(dst[k], b + off[5 + k], part[5 + k], hipMemcpyDeviceToHost, s.stream));
+            BSW_TRY(hipStreamSynchronize(s.stream));
+            return BSW_OK;
+        });
+        if (rc) return rc;
+    }
+    bsw::set_aln_stats(ctx, as);
+    return BSW_OK;
+}
+
+int bsw_aln_last_stats(bsw_ctx_t *ctx, bsw_aln_stats_t *out)
+{
+    if (!ctx || !out) return BSW_E_INVAL;
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    *out = ctx->aln_last;
+    return BSW_OK;
+}
 
 }  // extern "C"

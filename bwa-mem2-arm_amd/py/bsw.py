@@ -39,6 +39,9 @@ ABI_SYMBOLS = ("bsw_params_default", "bsw_create", "bsw_create_on", "bsw_destroy
                "bsw_fmi_copy_bwt", "bsw_mem_collect_intv", "bsw_mem_collect_intv_device", "bsw_fmi_sa_device",
                "bsw_fmi_last_kernel_ms", "bsw_chain_opt_default", "bsw_mem_chain_device", "bsw_fmi_build2", "bsw_fmi_check")
 
+# include/bsw_aln.h (additive to ABI version 8: its functions are listed here, not in ABI_SYMBOLS)
+ALN_SYMBOLS = ("bsw_reg2aln", "bsw_reg2aln_resident", "bsw_aln_last_stats")
+
 # include/bsw.h engine options (bsw_set_option)
 OPT_KERNEL8, OPT_FORK, OPT_SORTKEY, OPT_GLOB_BAND, OPT_EXT_CHUNK, OPT_HOST_CHUNK, OPT_LONG, OPT_HOST_PACK = 1, 2, 3, 4, 5, 6, 7, 8
 OPT_SMALL_BATCH = 9
@@ -58,6 +61,13 @@ ALNREG_DTYPE = np.dtype([("rb", np.int64), ("re", np.int64), ("qb", np.int32), (
                          ("score", np.int32), ("truesc", np.int32), ("w", np.int32),
                          ("seedlen0", np.int32)])
 assert SEED_DTYPE.itemsize == 16 and ALNREG_DTYPE.itemsize == 40
+
+# include/bsw_aln.h
+ALN_DTYPE = np.dtype([("pos", np.int64), ("is_rev", np.int32), ("n_cigar", np.int32), ("NM", np.int32),
+                      ("score", np.int32), ("w", np.int32), ("n_pass", np.int32), ("md_len", np.int32),
+                      ("flags", np.int32)])
+assert ALN_DTYPE.itemsize == 40
+ALN_REJECTED, ALN_NODP, ALN_OVERFLOW = 1, 2, 4
 
 # include/bsw_mate.h
 KSW_XBYTE, KSW_XSTOP, KSW_XSUBO, KSW_XSTART = 0x10000, 0x20000, 0x40000, 0x80000
@@ -164,6 +174,13 @@ def hip_lib():
                                            P, P]
         L.bsw_mem_chain_device.restype = ctypes.c_int
         L.bsw_pack_batch.argtypes = [P, P, P, ctypes.c_int32, P, ctypes.c_int64, P]
+        L.bsw_reg2aln.argtypes = [P, P, P, P, P, ctypes.c_int32, P, P, ctypes.c_int32, P, P, ctypes.c_int32, P,
+                                  ctypes.c_int32]
+        L.bsw_reg2aln_resident.argtypes = [P, P, P, P, P, ctypes.c_int32, P, P, ctypes.c_int32, P, P, ctypes.c_int32,
+                                           P, ctypes.c_int32, P]
+        L.bsw_aln_last_stats.argtypes = [P, P]
+        for f in ALN_SYMBOLS:
+            getattr(L, f).restype = ctypes.c_int
         L.bsw_get_scores_packed_device.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int, P, P]
         for f in ("bsw_create", "bsw_create_on", "bsw_get_scores", "bsw_get_scores_device", "bsw_last_stats",
                   "bsw_pack_batch", "bsw_get_scores_packed_device",
@@ -636,6 +653,51 @@ def chain2aln_resident(engine, d_reads: int, d_off: int, d_len: int, n_reads: in
 def chain_last_stats(engine) -> ChainStats:
     st = ChainStats()
     _check(hip_lib().bsw_chain_last_stats(engine._ctx, ctypes.byref(st)))
+    return st
+
+
+# ---------------------------------------------------------------- final alignments (bsw_aln.h)
+class AlnStats(ctypes.Structure):
+    _fields_ = [("n_regs", ctypes.c_int32), ("n_rejected", ctypes.c_int32), ("n_gapfree", ctypes.c_int32),
+                ("n_dp", ctypes.c_int32 * 3), ("dp_ms", ctypes.c_float), ("helper_ms", ctypes.c_float)]
+
+
+def reg2aln(engine, reads, read_off, read_len, regs, reg_read, opt: ExtOpt | None = None, cigar_stride: int = 16,
+            md_stride: int = 64):
+    """bsw_reg2aln (host arrays, resident reference required): regions (ALNREG_DTYPE) of reads
+    reg_read[k] -> (aln ALN_DTYPE, cigar [n, cigar_stride] uint32, md [n, md_stride] uint8 or None
+    when md_stride == 0)."""
+    opt = opt if opt is not None else ext_opt()
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+    read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+    regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
+    reg_read = np.ascontiguousarray(reg_read, dtype=np.int32)
+    n = len(regs)
+    aln = np.zeros(n, dtype=ALN_DTYPE)
+    cig = np.zeros((n, cigar_stride), dtype=np.uint32)
+    md = np.zeros((n, md_stride), dtype=np.uint8) if md_stride > 0 else None
+    _check(hip_lib().bsw_reg2aln(engine._ctx, ctypes.byref(opt), _ptr(reads), _ptr(read_off), _ptr(read_len),
+                                 len(read_len), _ptr(regs), _ptr(reg_read), n, _ptr(aln), _ptr(cig), cigar_stride,
+                                 _ptr(md) if md is not None else None, md_stride))
+    return aln, cig, md
+
+
+def reg2aln_resident(engine, d_reads: int, d_off: int, d_len: int, n_reads: int, d_regs: int, d_reg_read: int,
+                     n_regs: int, d_aln: int, d_cigar: int, cigar_stride: int, d_md: int, md_stride: int,
+                     opt: ExtOpt | None = None, stream: int = 0):
+    """bsw_reg2aln_resident: every array a device pointer (d_regs / d_reg_read as
+    bsw_chain2aln_resident leaves them in d_out / d_seed_read)."""
+    opt = opt if opt is not None else ext_opt()
+    V = ctypes.c_void_p
+    _check(hip_lib().bsw_reg2aln_resident(engine._ctx, ctypes.byref(opt), V(d_reads), V(d_off), V(d_len), n_reads,
+                                          V(d_regs), V(d_reg_read), n_regs, V(d_aln), V(d_cigar), cigar_stride,
+                                          V(d_md or None), md_stride, V(stream or None)))
+
+
+def aln_last_stats(engine) -> AlnStats:
+    st = AlnStats()
+    _check(hip_lib().bsw_aln_last_stats(engine._ctx, ctypes.byref(st)))
     return st
 
 
