@@ -21,6 +21,7 @@
 #include "../../include/bsw_mate.h"
 #include "../../include/bsw_global.h"
 #include "../../include/bsw_aln.h"
+#include "../../include/bsw_sel.h"
 #include "bsw_kernels.h"
 #include "bsw_internal.h"
 
@@ -131,6 +132,8 @@ struct PlanCall {
 
 struct ExtState;
 struct AlnState;
+struct SelW;
+struct SelRd;
 // Everything one call needs on one device.  Members are destroyed in reverse order: buffers, then
 // events, then streams.
 struct BSW_HIDDEN Slot {
@@ -189,6 +192,14 @@ struct BSW_HIDDEN Slot {
     DevBuf<SeqPair> d_apairs;
     DevBuf<uint8_t> d_aq, d_at;         // per-job query / reference codes
     DevBuf<uint8_t> d_aio;              // host form: the staged inputs and outputs
+    // region selection (bsw_sel.h); its DP jobs use d_apairs / d_aq / d_at, its host form d_aio
+    DevBuf<SelW> d_swork;               // per-read work lists, flat: a read's list at its first seed slot
+    DevBuf<SelRd> d_sst;                // per-read list length and suspended loop
+    DevBuf<int32_t> d_sz;               // primary marking's z lists (flat, as d_swork)
+    DevBuf<int32_t> d_srun;             // sbeg[n_reads], send[n_reads]
+    DevBuf<int32_t> d_skept;            // kept counts, n_reads + 1
+    DevBuf<int32_t> d_slist;            // suspended reads of two rounds (ping-pong), n_reads each
+    DevBuf<int32_t> d_smeta;            // kSelMetaWords
     bool timed = false;
     hipStream_t run_stream = nullptr;   // stream of the last run_device (finish_stats waits on it)
     bsw_stats_t stats{};
@@ -354,6 +365,7 @@ struct bsw_ctx {
     bsw_mate_stats_t mate_last{};
     bsw_global_stats_t glob_last{};
     bsw_aln_stats_t aln_last{};
+    bsw_sel_stats_t sel_last{};
     struct Pinned { std::mutex mu; bsw::PinnedBuf<uint8_t> b; } pin[2];
     int glob_band = 0;                  // BSW_OPT_GLOB_BAND
     int64_t ext_chunk = 0;              // BSW_OPT_EXT_CHUNK (0: the int32-offset bound)

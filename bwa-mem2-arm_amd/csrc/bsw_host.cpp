@@ -28,6 +28,7 @@
 #include "bsw_global_k.h"
 #include "bsw_ext_k.h"
 #include "bsw_aln_k.h"
+#include "bsw_sel_k.h"
 
 namespace bsw {
 
@@ -1245,6 +1246,274 @@ int bsw_aln_last_stats(bsw_ctx_t *ctx, bsw_aln_stats_t *out)
     if (!ctx || !out) return BSW_E_INVAL;
     std::lock_guard<std::mutex> g(ctx->stats_mu);
     *out = ctx->aln_last;
+    return BSW_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- region selection (bsw_sel.h)
+namespace bsw {
+
+struct SelIo {                          // device pointers of one call, either form
+    const uint8_t *reads;
+    const int64_t *read_off;
+    const int32_t *read_len;
+    const bsw_seed_t *seeds;
+    const int32_t *seed_read, *seed_chain;
+    const bsw_alnreg_t *regs;
+    const int32_t *extended, *csub;
+    const float *frac_rep;
+    bsw_alnreg_t *sel_regs;
+    int32_t *sel_read;
+    bsw_selinfo_t *sel_info;
+    int32_t *read_first;
+};
+
+// runs -> gather -> step; per patch round: build -> score-only ksw_global2 (glob_device) -> step
+// over the suspended reads; then scan of the kept counts -> emit.  Everything on `st`; the host
+// waits once per round for the next round's job count and once for the total.
+static int regs_select_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st, const bsw_sel_opt_t &opt,
+                              const SelIo &io, int32_t n_reads, int32_t n_seeds, int32_t sel_cap, int32_t *n_sel,
+                              bsw_sel_stats_t &ss)
+{
+    const bsw_params_t &pr = ctx->params;
+    SelParams p{};
+    p.W = opt.w; p.a = pr.mat[0]; p.b = opt.b;
+    p.o_del = pr.o_del; p.e_del = pr.e_del; p.o_ins = pr.o_ins; p.e_ins = pr.e_ins;
+    p.n_reads = n_reads; p.n_seeds = n_seeds;
+    p.max_chain_gap = opt.max_chain_gap; p.min_seed_len = opt.min_seed_len;
+    p.mapQ_coef_len = opt.mapQ_coef_len; p.mapQ_coef_fac = opt.mapQ_coef_fac; p.patch = opt.patch;
+    p.mask_level_redun = opt.mask_level_redun; p.mask_level = opt.mask_level;
+    p.ref_len = dc.refres_len; p.l_pac = opt.l_pac; p.id0 = opt.id0;
+    memcpy(p.mat, pr.mat, 25);
+    GlobParams gp;
+    make_glob_params(pr, ctx->glob_band, gp);
+    const size_t nr = (size_t)n_reads, ns = (size_t)n_seeds;
+    size_t scan_bytes = 0;
+    BSW_TRY(launch_sel_scan(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
+    BSW_TRY(s.d_swork.grow(std::max<size_t>(ns, 1)));
+    BSW_TRY(s.d_sz.grow(std::max<size_t>(ns, 1)));
+    BSW_TRY(s.d_sst.grow(std::max<size_t>(nr, 1)));
+    BSW_TRY(s.d_srun.grow(2 * nr + 1));
+    BSW_TRY(s.d_skept.grow(nr + 1));
+    BSW_TRY(s.d_slist.grow(2 * nr + 1));
+    BSW_TRY(s.d_smeta.grow(kSelMetaWords));
+    BSW_TRY(s.d_tmp.grow(std::max<size_t>(scan_bytes, 16)));
+    if (!s.ev2) BSW_TRY(hipEventCreate(&s.ev2.p));
+    if (!s.ev3) BSW_TRY(hipEventCreate(&s.ev3.p));
+    int32_t *sbeg = s.d_srun, *send = s.d_srun + nr;
+    int32_t *h_meta = s.h_meta;
+    float ms = 0.f;
+    BSW_TRY(hipEventRecord(s.ev2, st));
+    BSW_TRY(hipMemsetAsync(s.d_srun, 0, (2 * nr + 1) * sizeof(int32_t), st));
+    BSW_TRY(hipMemsetAsync(s.d_skept, 0, (nr + 1) * sizeof(int32_t), st));
+    BSW_TRY(hipMemsetAsync(s.d_smeta, 0, kSelMetaWords * sizeof(int32_t), st));
+    BSW_TRY(launch_sel_runs(io.seed_read, n_seeds, n_reads, sbeg, send, s.d_smeta, st));
+    BSW_TRY(launch_sel_gather(p, sbeg, send, io.read_len, io.seeds, io.seed_chain, io.regs, io.extended, io.csub,
+                              s.d_swork, s.d_sst, s.d_smeta, st));
+    BSW_TRY(launch_sel_step(p, nullptr, n_reads, nullptr, sbeg, io.reads, io.read_off, io.frac_rep, dc.d_refres,
+                            s.d_swork, s.d_sst, s.d_sz, s.d_slist, s.d_smeta + kSelCnt, s.d_skept, s.d_smeta, st));
+    BSW_TRY(hipEventRecord(s.ev3, st));
+    BSW_TRY(hipMemcpyAsync(h_meta, s.d_smeta, kSelMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(hipEventElapsedTime(&ms, s.ev2, s.ev3));
+    ss.helper_ms += ms;
+    if (h_meta[kSelErr]) return BSW_E_RANGE;
+    int32_t nj = h_meta[kSelCnt];
+    for (int round = 0; nj > 0; ++round) {
+        ss.rounds++;
+        ss.n_dp += nj;
+        const int cur = round & 1, nxt = cur ^ 1;
+        const int32_t *list = s.d_slist + (size_t)cur * nr;
+        int32_t *next = s.d_slist + (size_t)nxt * nr;
+        p.qstride = std::max(h_meta[kSelMaxQ], 1);          // longest patch query / reference span so far
+        p.tstride = std::max(h_meta[kSelMaxT], 1);
+        // SeqPair idr / idq are int32: chunk so j * stride stays below 2^31
+        const int32_t chunk = (int32_t)std::min<int64_t>(nj, (int64_t)INT32_MAX / std::max(p.tstride, p.qstride) - 1);
+        BSW_TRY(s.d_apairs.grow((size_t)chunk));
+        BSW_TRY(s.d_aq.grow((size_t)chunk * p.qstride));
+        BSW_TRY(s.d_at.grow((size_t)chunk * p.tstride));
+        BSW_TRY(hipMemsetAsync(s.d_smeta + kSelCnt + nxt, 0, sizeof(int32_t), st));
+        for (int32_t a = 0; a < nj; a += chunk) {
+            const int32_t b = std::min(nj, a + chunk);
+            BSW_TRY(hipEventRecord(s.ev2, st));
+            BSW_TRY(launch_sel_build(p, list + a, b - a, sbeg, io.reads, io.read_off, s.d_swork, s.d_sst, dc.d_refres,
+                                     s.d_apairs, s.d_aq, s.d_at, st));
+            BSW_TRY(hipEventRecord(s.ev3, st));
+            bsw_global_stats_t gs;
+            if (int r = glob_device(gp, s, s.d_apairs, s.d_at, s.d_aq, b - a, nullptr, 0, nullptr, st, &gs)) return r;
+            ss.dp_ms += gs.kernel_ms;
+            {
+                std::lock_guard<std::mutex> g(ctx->stats_mu);   // (bsw_global_last_stats: the last DP batch)
+                ctx->glob_last = gs;
+            }
+            BSW_TRY(hipEventElapsedTime(&ms, s.ev2, s.ev3));
+            ss.helper_ms += ms;
+            BSW_TRY(hipEventRecord(s.ev2, st));
+            BSW_TRY(launch_sel_step(p, list + a, b - a, s.d_apairs, sbeg, io.reads, io.read_off, io.frac_rep,
+                                    dc.d_refres, s.d_swork, s.d_sst, s.d_sz, next, s.d_smeta + kSelCnt + nxt, s.d_skept,
+                                    s.d_smeta, st));
+            BSW_TRY(hipEventRecord(s.ev3, st));
+            BSW_TRY(hipMemcpyAsync(h_meta, s.d_smeta, kSelMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            BSW_TRY(hipStreamSynchronize(st));
+            BSW_TRY(hipEventElapsedTime(&ms, s.ev2, s.ev3));
+            ss.helper_ms += ms;
+            if (h_meta[kSelErr]) return BSW_E_RANGE;
+        }
+        nj = h_meta[kSelCnt + nxt];
+    }
+    ss.n_regs_in = h_meta[kSelRegsIn];
+    ss.n_redundant = h_meta[kSelRedundant];
+    ss.n_identical = h_meta[kSelIdentical];
+    ss.n_patch_tried = h_meta[kSelTried];
+    ss.n_patch_ok = h_meta[kSelOk];
+    ss.n_patch_ratio = h_meta[kSelRatio];
+    BSW_TRY(hipEventRecord(s.ev2, st));
+    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, s.d_skept, io.read_first, n_reads, st));
+    BSW_TRY(hipMemcpyAsync(h_meta, io.read_first + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    *n_sel = ss.n_sel = h_meta[0];
+    if (h_meta[0] > sel_cap) return BSW_E_RANGE;
+    BSW_TRY(launch_sel_emit(p, io.seed_read, sbeg, s.d_skept, io.read_first, s.d_swork, io.frac_rep, io.sel_regs,
+                            io.sel_read, io.sel_info, st));
+    BSW_TRY(hipEventRecord(s.ev3, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(hipEventElapsedTime(&ms, s.ev2, s.ev3));
+    ss.helper_ms += ms;
+    return BSW_OK;
+}
+
+// argument checks shared by both forms; the caller holds dc.refmu shared
+static int regs_select_check(const bsw_sel_opt_t *opt, DeviceCtx &dc, int32_t n_reads, int32_t n_seeds,
+                             int32_t sel_cap)
+{
+    if (n_reads < 0 || n_seeds < 0 || sel_cap < 0) return BSW_E_INVAL;
+    if (!dc.d_refres) return BSW_E_INVAL;
+    if (opt->w < 0 || opt->w > (1 << 28) || opt->l_pac < 0 || (opt->l_pac > 0 && dc.refres_len != 2 * opt->l_pac))
+        return BSW_E_INVAL;
+    if (opt->max_chain_gap < 0 || opt->mapQ_coef_len < 0 || opt->b < 0 || opt->min_seed_len < 0) return BSW_E_INVAL;
+    return BSW_OK;
+}
+
+static void set_sel_stats(bsw_ctx_t *ctx, const bsw_sel_stats_t &ss)
+{
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    ctx->sel_last = ss;
+}
+
+}  // namespace bsw
+
+extern "C" {
+
+void bsw_sel_opt_default(bsw_sel_opt_t *opt)
+{
+    if (!opt) return;
+    memset(opt, 0, sizeof(*opt));
+    opt->w = 100;
+    opt->max_chain_gap = 10000;
+    opt->l_pac = 0;
+    opt->mask_level_redun = 0.95f;
+    opt->mask_level = 0.5f;
+    opt->min_seed_len = 19;
+    opt->b = 4;
+    opt->mapQ_coef_len = 50;
+    opt->mapQ_coef_fac = 3;
+    opt->patch = 1;
+    opt->id0 = 0;
+}
+
+int bsw_regs_select_resident(bsw_ctx_t *ctx, const bsw_sel_opt_t *opt, const uint8_t *d_reads,
+                             const int64_t *d_read_off, const int32_t *d_read_len, int32_t n_reads,
+                             const bsw_seed_t *d_seeds, const int32_t *d_seed_read, const int32_t *d_seed_chain,
+                             const bsw_alnreg_t *d_regs, const int32_t *d_extended, int32_t n_seeds,
+                             const int32_t *d_csub, const float *d_frac_rep, bsw_alnreg_t *d_sel_regs,
+                             int32_t *d_sel_read, bsw_selinfo_t *d_sel_info, int32_t *d_read_first,
+                             int32_t sel_cap, int32_t *n_sel, void *stream)
+{
+    if (!ctx || !opt || !n_sel) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the resident reference stays put
+    if (const int rc = bsw::regs_select_check(opt, dc, n_reads, n_seeds, sel_cap)) return rc;
+    if (!d_read_first || (n_reads > 0 && (!d_read_off || !d_read_len)) ||
+        (n_seeds > 0 && (!d_reads || !d_seeds || !d_seed_read || !d_seed_chain || !d_regs || !d_extended)) ||
+        (sel_cap > 0 && (!d_sel_regs || !d_sel_read || !d_sel_info)))
+        return BSW_E_INVAL;
+    bsw_sel_stats_t ss{};
+    ss.n_reads = n_reads;
+    const bsw::SelIo io = {d_reads, d_read_off, d_read_len, d_seeds, d_seed_read, d_seed_chain, d_regs, d_extended,
+                           d_csub, d_frac_rep, d_sel_regs, d_sel_read, d_sel_info, d_read_first};
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::regs_select_device(ctx, dc, s, st, *opt, io, n_reads, n_seeds, sel_cap, n_sel, ss);
+    });
+    if (rc) return rc;
+    bsw::set_sel_stats(ctx, ss);
+    return BSW_OK;
+}
+
+int bsw_regs_select(bsw_ctx_t *ctx, const bsw_sel_opt_t *opt, const uint8_t *reads, const int64_t *read_off,
+                    const int32_t *read_len, int32_t n_reads, const bsw_seed_t *seeds, const int32_t *seed_read,
+                    const int32_t *seed_chain, const bsw_alnreg_t *regs, const int32_t *extended, int32_t n_seeds,
+                    const int32_t *csub, const float *frac_rep, bsw_alnreg_t *sel_regs, int32_t *sel_read,
+                    bsw_selinfo_t *sel_info, int32_t *read_first, int32_t sel_cap, int32_t *n_sel)
+{
+    if (!ctx || !opt || !n_sel) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::regs_select_check(opt, dc, n_reads, n_seeds, sel_cap)) return rc;
+    if (!read_first || (n_reads > 0 && (!read_off || !read_len)) ||
+        (n_seeds > 0 && (!reads || !seeds || !seed_read || !seed_chain || !regs || !extended)) ||
+        (sel_cap > 0 && (!sel_regs || !sel_read || !sel_info)))
+        return BSW_E_INVAL;
+    int64_t rbytes = 0;
+    for (int32_t i = 0; i < n_reads; ++i) {
+        if (read_off[i] < 0 || read_len[i] < 0) return BSW_E_RANGE;
+        rbytes = std::max<int64_t>(rbytes, read_off[i] + read_len[i]);
+    }
+    bsw_sel_stats_t ss{};
+    ss.n_reads = n_reads;
+    // one staged blob: inputs, then outputs, each part 16-B aligned
+    const size_t ns = (size_t)n_seeds, nr = (size_t)n_reads, nc = (size_t)sel_cap;
+    constexpr int kIn = 10, kAll = 14;
+    const size_t part[kAll] = {(size_t)rbytes, nr * sizeof(int64_t), nr * sizeof(int32_t), ns * sizeof(bsw_seed_t),
+                               ns * sizeof(int32_t), ns * sizeof(int32_t), ns * sizeof(bsw_alnreg_t),
+                               ns * sizeof(int32_t), csub ? ns * sizeof(int32_t) : 0, frac_rep ? nr * sizeof(float) : 0,
+                               nc * sizeof(bsw_alnreg_t), nc * sizeof(int32_t), nc * sizeof(bsw_selinfo_t),
+                               (nr + 1) * sizeof(int32_t)};
+    size_t off[kAll + 1] = {0};
+    for (int k = 0; k < kAll; ++k) off[k + 1] = off[k] + ((part[k] + 15) & ~(size_t)15);
+    const void *src[kIn] = {reads, read_off, read_len, seeds, seed_read, seed_chain, regs, extended, csub, frac_rep};
+    void *dst[4] = {sel_regs, sel_read, sel_info, read_first};
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(s.d_aio.grow(off[kAll] + 16));
+        uint8_t *b = s.d_aio;
+        for (int k = 0; k < kIn; ++k)
+            if (part[k]) BSW_TRY(hipMemcpyAsync(b + off[k], src[k], part[k], hipMemcpyHostToDevice, s.stream));
+        const bsw::SelIo io = {b + off[0], (const int64_t *)(b + off[1]), (const int32_t *)(b + off[2]),
+                               (const bsw_seed_t *)(b + off[3]), (const int32_t *)(b + off[4]),
+                               (const int32_t *)(b + off[5]), (const bsw_alnreg_t *)(b + off[6]),
+                               (const int32_t *)(b + off[7]), csub ? (const int32_t *)(b + off[8]) : nullptr,
+                               frac_rep ? (const float *)(b + off[9]) : nullptr, (bsw_alnreg_t *)(b + off[10]),
+                               (int32_t *)(b + off[11]), (bsw_selinfo_t *)(b + off[12]), (int32_t *)(b + off[13])};
+        if (int r = bsw::regs_select_device(ctx, dc, s, s.stream, *opt, io, n_reads, n_seeds, sel_cap, n_sel, ss))
+            return r;
+        const size_t k = (size_t)*n_sel;
+        const size_t got[4] = {k * sizeof(bsw_alnreg_t), k * sizeof(int32_t), k * sizeof(bsw_selinfo_t), part[13]};
+        for (int o = 0; o < 4; ++o)
+            if (got[o]) BSW_TRY(hipMemcpyAsync(dst[o], b + off[10 + o], got[o], hipMemcpyDeviceToHost, s.stream));
+        BSW_TRY(hipStreamSynchronize(s.stream));
+        return BSW_OK;
+    });
+    if (rc) return rc;
+    bsw::set_sel_stats(ctx, ss);
+    return BSW_OK;
+}
+
+int bsw_sel_last_stats(bsw_ctx_t *ctx, bsw_sel_stats_t *out)
+{
+    if (!ctx || !out) return BSW_E_INVAL;
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    *out = ctx->sel_last;
     return BSW_OK;
 }
 

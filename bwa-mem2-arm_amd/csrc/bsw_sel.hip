@@ -1,0 +1,601 @@
+// bsw_sel.hip -- region selection (include/bsw_sel.h: mem_sort_dedup_patch, mem_mark_primary_se,
+// mem_approx_mapq_se) between bsw_chain2aln_resident and bsw_reg2aln_resident, every per-read
+// step on the GPU:
+//   sel_runs_kernel   : each read's run of seed slots; a read's work list lives in the flat
+//                       work[] at its run's first slot (a read has at most one region per slot)
+//   sel_gather_kernel : av in upstream's order (chains in order, each by len * a and index
+//                       descending), seedcov, csub, validation
+//   sel_step_kernel   : one work item per read -- the re sort, the i / j loop of the dedup; a
+//                       patch_reg that passes its cheap tests SUSPENDS the read (one DP job,
+//                       compacted by a ballot and one atomic per wave) and the next launch resumes
+//                       it with the job's score; a read whose loop ends goes on through the drops,
+//                       the score sort, the identical-hit rule, the hash sort, primary marking and
+//                       MAPQ (double precision).  Reads with at most one region skip all of it.
+//   sel_build_kernel  : 16 lanes per job, SeqPair + query slice / reference span as aln_build_kernel
+//   sel_emit_kernel   : after the scan of the kept counts, the compact output
+// The sorts are klib's ks_introsort (w_introsort of bsw_memchain.hip with a comparator), their
+// explicit stack in LDS.  Plain C++ with vector stores only; no private arrays.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include <stdint.h>
+#include "bsw_sel_k.h"
+#include "bsw_wave.h"
+
+namespace bsw {
+
+constexpr int kSelStack = 20;           // introsort frames: a push halves the range, n <= 2^20
+
+// A region moves as five 16-byte words held in registers (a struct assignment between two
+// possibly equal addresses was lowered through a stack temporary).
+struct SelRaw { uint4 a, b, c, d, e; };
+static_assert(sizeof(SelW) == 80 && alignof(SelW) == 16, "SelW moves as 5 x uint4");
+__device__ __forceinline__ SelRaw sel_ld(const SelW *p)
+{
+    const uint4 *q = reinterpret_cast<const uint4 *>(p);
+    return SelRaw{q[0], q[1], q[2], q[3], q[4]};
+}
+__device__ __forceinline__ void sel_st(SelW *p, const SelRaw &v)
+{
+    uint4 *q = reinterpret_cast<uint4 *>(p);
+    q[0] = v.a; q[1] = v.b; q[2] = v.c; q[3] = v.d; q[4] = v.e;
+}
+__device__ __forceinline__ void sel_copy(SelW *dst, const SelW *src) { sel_st(dst, sel_ld(src)); }
+__device__ __forceinline__ void sel_swap(SelW *x, SelW *y)
+{
+    const SelRaw a = sel_ld(x), b = sel_ld(y);
+    sel_st(x, b);
+    sel_st(y, a);
+}
+
+// comparators over small keys (a pivot kept as a whole SelW went to scratch)
+struct LtRe {
+    typedef int64_t K;
+    static __device__ __forceinline__ K key(const SelW &x) { return x.r.re; }
+    static __device__ __forceinline__ bool lt(const K &x, const K &y) { return x < y; }
+};
+struct LtScorePos {                     // alnreg_slt2 + rb + qb
+    struct K { int32_t score, qb; int64_t rb; };
+    static __device__ __forceinline__ K key(const SelW &x) { return K{x.r.score, x.r.qb, x.r.rb}; }
+    static __device__ __forceinline__ bool lt(const K &x, const K &y)
+    {
+        return x.score > y.score || (x.score == y.score && (x.rb < y.rb || (x.rb == y.rb && x.qb < y.qb)));
+    }
+};
+struct LtScoreHash {                    // alnreg_hlt
+    struct K { int32_t score; uint64_t hash; };
+    static __device__ __forceinline__ K key(const SelW &x) { return K{x.r.score, x.hash}; }
+    static __device__ __forceinline__ bool lt(const K &x, const K &y)
+    {
+        return x.score > y.score || (x.score == y.score && x.hash < y.hash);
+    }
+};
+#define SEL_LT(x, y) LT::lt(LT::key(x), LT::key(y))
+
+template <class LT>
+__device__ __forceinline__ void sel_insertsort(SelW *s, SelW *t, LT)
+{
+    for (SelW *i = s + 1; i < t; ++i)
+        for (SelW *j = i; j > s && SEL_LT(*j, *(j - 1)); --j) sel_swap(j, j - 1);
+}
+
+template <class LT>
+__device__ __forceinline__ void sel_combsort(int n, SelW *a, LT)
+{
+    const double shrink_factor = 1.2473309501039786540366528676643;
+    int do_swap, gap = n;
+    do {
+        if (gap > 2) {
+            gap = (int)(gap / shrink_factor);
+            if (gap == 9 || gap == 10) gap = 11;
+        }
+        do_swap = 0;
+        for (SelW *i = a; i < a + n - gap; ++i) {
+            SelW *j = i + gap;
+            if (SEL_LT(*j, *i)) {
+                sel_swap(i, j);
+                do_swap = 1;
+            }
+        }
+    } while (do_swap || gap > 2);
+    if (gap != 1) sel_insertsort(a, a + n, LT());
+}
+
+// klib ks_introsort; stk = this thread's column of the LDS stack (frame f at stk[(3 f + k) * 64])
+template <class LT>
+__device__ __forceinline__ void sel_introsort(int n, SelW *a, int *stk, LT)
+{
+    if (n < 2) return;
+    if (n == 2) {
+        if (SEL_LT(a[1], a[0])) sel_swap(a, a + 1);
+        return;
+    }
+    int d, top = 0;
+    for (d = 2; (1 << d) < n; ++d) ;
+    int s = 0, t = n - 1, i, j, k;
+    d <<= 1;
+    while (true) {
+        if (s < t) {
+            if (--d == 0) {
+                sel_combsort(t - s + 1, a + s, LT());
+                t = s;
+                continue;
+            }
+            i = s; j = t; k = i + ((j - i) >> 1) + 1;
+            if (SEL_LT(a[k], a[i])) {
+                if (SEL_LT(a[k], a[j])) k = j;
+            } else {
+                k = SEL_LT(a[j], a[i]) ? i : j;
+            }
+            const typename LT::K rp = LT::key(a[k]);
+            if (k != t) sel_swap(a + k, a + t);
+            for (;;) {
+                do ++i; while (LT::lt(LT::key(a[i]), rp));
+                do --j; while (i <= j && LT::lt(rp, LT::key(a[j])));
+                if (j <= i) break;
+                sel_swap(a + i, a + j);
+            }
+            sel_swap(a + i, a + t);
+            int pl = -1, pr = -1;
+            if (i - s > t - i) {
+                if (i - s > 16) { pl = s; pr = i - 1; }
+                s = t - i > 16 ? i + 1 : t;
+            } else {
+                if (t - i > 16) { pl = i + 1; pr = t; }
+                t = i - s > 16 ? i - 1 : s;
+            }
+            if (pl >= 0 && top < kSelStack) {       // (a frame left out is sorted by the last insertion sort)
+                stk[(3 * top) * 64] = pl; stk[(3 * top + 1) * 64] = pr; stk[(3 * top + 2) * 64] = d;
+                ++top;
+            }
+        } else {
+            if (top == 0) {
+                sel_insertsort(a, a + n, LT());
+                return;
+            }
+            --top;
+            s = stk[(3 * top) * 64]; t = stk[(3 * top + 1) * 64]; d = stk[(3 * top + 2) * 64];
+        }
+    }
+}
+
+__device__ __forceinline__ uint64_t hash_64(uint64_t key)
+{
+    key += ~(key << 32);
+    key ^= (key >> 22);
+    key += ~(key << 13);
+    key ^= (key >> 8);
+    key += (key << 3);
+    key ^= (key >> 15);
+    key += ~(key << 27);
+    key ^= (key >> 31);
+    return key;
+}
+
+// bsw_gen_cigar_band (include/bsw_global.h), device form
+__device__ __forceinline__ int sel_cigar_band(const SelParams &p, int lq, int rlen, int w_)
+{
+    const int max_ins = (int)((double)(((lq + 1) >> 1) * p.a - p.o_ins) / p.e_ins + 1.);
+    const int max_del = (int)((double)(((lq + 1) >> 1) * p.a - p.o_del) / p.e_del + 1.);
+    const int max_gap = max(max(max_ins, max_del), 1);
+    const int d = abs(rlen - lq);
+    const int w = min((max_gap + d + 1) >> 1, w_);
+    return max(w, d + 3);
+}
+
+__device__ __forceinline__ int sel_mapq(const SelParams &p, const SelW &x, float frac_rep)
+{
+    if (x.secondary >= 0) return 0;
+    const int score = x.r.score;
+    int sub = x.sub ? x.sub : p.min_seed_len * p.a;
+    sub = max(sub, x.csub);
+    if (sub >= score) return 0;
+    const int l = max(x.r.qe - x.r.qb, (int)(x.r.re - x.r.rb));
+    const double identity = 1. - (double)(l * p.a - score) / (p.a + p.b) / l;
+    int mapq;
+    if (score == 0) {
+        mapq = 0;
+    } else if (p.mapQ_coef_len > 0) {
+        double tmp = l < p.mapQ_coef_len ? 1. : p.mapQ_coef_fac / log((double)l);
+        tmp *= identity * identity;
+        mapq = (int)(6.02 * (score - sub) / p.a * tmp * tmp + .499);
+    } else {
+        mapq = (int)(30.0 * (1. - (double)sub / score) * log((double)x.seedcov) + .499);
+        if (identity < 0.95) mapq = (int)(mapq * identity * identity + .499);
+    }
+    if (x.sub_n > 0) mapq -= (int)(4.343 * log((double)(x.sub_n + 1)) + .499);
+    mapq = min(mapq, 60);
+    mapq = max(mapq, 0);
+    return (int)(mapq * (1. - frac_rep) + .499);
+}
+
+// A read whose dedup loop has ended (dedup: it ran, n > 1 at its start): steps 4..7, primary
+// marking and MAPQ; returns the number kept.
+__device__ __forceinline__ int sel_finish(const SelParams &p, int r, SelW *W, int n, bool dedup, int *stk, int32_t *Z, float frac_rep,
+                          int32_t *meta)
+{
+    if (dedup) {
+        int m = 0;
+        for (int k = 0; k < n; ++k)
+            if (W[k].r.qe > W[k].r.qb) {
+                if (m != k) sel_copy(W + m, W + k);
+                ++m;
+            }
+        n = m;
+        sel_introsort(n, W, stk, LtScorePos());
+        int ident = 0;
+        for (int k = 1; k < n; ++k)
+            if (W[k].r.score == W[k - 1].r.score && W[k].r.rb == W[k - 1].r.rb && W[k].r.qb == W[k - 1].r.qb) {
+                W[k].r.qe = W[k].r.qb;
+                ++ident;
+            }
+        if (ident) {
+            atomicAdd(&meta[kSelIdentical], ident);
+            m = 1;
+            for (int k = 1; k < n; ++k)
+                if (W[k].r.qe > W[k].r.qb) {
+                    if (m != k) sel_copy(W + m, W + k);
+                    ++m;
+                }
+            n = m;
+        }
+    }
+    if (n == 0) return 0;
+    for (int k = 0; k < n; ++k) {
+        W[k].sub = 0;
+        W[k].secondary = -1;
+        W[k].hash = hash_64((uint64_t)p.id0 + (uint64_t)(int64_t)r + (uint64_t)k);
+    }
+    sel_introsort(n, W, stk, LtScoreHash());
+    if (n > 1) {
+        const int tmp = max(max(p.a + p.b, p.o_del + p.e_del), p.o_ins + p.e_ins);
+        int nz = 1;
+        Z[0] = 0;
+        for (int i = 1; i < n; ++i) {
+            const int iqb = W[i].r.qb, iqe = W[i].r.qe, isc = W[i].r.score;
+            int k = 0;
+            for (; k < nz; ++k) {
+                const int j = Z[k];
+                const int jqb = W[j].r.qb, jqe = W[j].r.qe;
+                const int b_max = max(jqb, iqb), e_min = min(jqe, iqe);
+                if (e_min > b_max) {
+                    const int min_l = min(iqe - iqb, jqe - jqb);
+                    if ((float)(e_min - b_max) >= (float)min_l * p.mask_level) {
+                        if (W[j].sub == 0) W[j].sub = isc;
+                        if (W[j].r.score - isc <= tmp) ++W[j].sub_n;
+                        break;
+                    }
+                }
+            }
+            if (k < nz) W[i].secondary = Z[k];
+            else Z[nz++] = i;
+        }
+    }
+    for (int k = 0; k < n; ++k) W[k].mapq = sel_mapq(p, W[k], frac_rep);
+    return n;
+}
+
+__global__ void sel_runs_kernel(const int32_t *__restrict__ sr, int32_t ns, int32_t n_reads,
+                                int32_t *__restrict__ sbeg, int32_t *__restrict__ send, int32_t *__restrict__ meta)
+{
+    const int32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= ns) return;
+    const int32_t r = sr[k];
+    if (r < 0 || r >= n_reads || (k > 0 && sr[k - 1] > r)) {
+        atomicOr(&meta[kSelErr], 1);
+        return;
+    }
+    if (k == 0 || sr[k - 1] != r) sbeg[r] = k;
+    if (k == ns - 1 || sr[k + 1] != r) send[r] = k + 1;
+}
+
+__global__ __launch_bounds__(64) void sel_gather_kernel(
+    const SelParams p, const int32_t *__restrict__ sbeg, const int32_t *__restrict__ send,
+    const int32_t *__restrict__ read_len, const bsw_seed_t *__restrict__ seeds, const int32_t *__restrict__ sc,
+    const bsw_alnreg_t *__restrict__ regs, const int32_t *__restrict__ ext, const int32_t *__restrict__ csub,
+    SelW *__restrict__ work, SelRd *__restrict__ st, int32_t *__restrict__ meta)
+{
+    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    int n = 0, err = 0;
+    if (r < p.n_reads && meta[kSelErr] == 0) {              // (bad read ids: the runs are not to be trusted)
+        const int32_t b = sbeg[r], e = send[r];
+        const int l_query = read_len[r];
+        SelW *W = work + b;
+        for (int32_t c0 = b; c0 < e;) {
+            int32_t c1 = c0;
+            const int32_t cid = sc[c0];
+            while (c1 < e && sc[c1] == cid) ++c1;
+            const int n0 = n;
+            for (int32_t i = c0; i < c1; ++i) {
+                if (ext[i] == 0) continue;
+                SelW x;
+                x.r = regs[i];
+                if (x.r.qe == x.r.qb) continue;
+                if (x.r.qb < 0 || x.r.qe > l_query || x.r.qe < x.r.qb || x.r.rb < 0 || x.r.rb > x.r.re ||
+                    x.r.re > p.ref_len) {
+                    err = 1;
+                    continue;
+                }
+                int cov = 0;
+                for (int32_t k = c0; k < c1; ++k) {
+                    const bsw_seed_t t = seeds[k];
+                    if (t.qbeg >= x.r.qb && t.qbeg + t.len <= x.r.qe && t.rbeg >= x.r.rb && t.rbeg + t.len <= x.r.re)
+                        cov += t.len;
+                }
+                x.seedcov = cov; x.sub = 0; x.csub = csub ? csub[i] : 0; x.sub_n = 0; x.n_comp = 1;
+                x.secondary = -1; x.src = i; x.mapq = 0; x.hash = 0;
+                // insert into W[n0 .. n): (len * a, slot) descending
+                const int64_t ki = (int64_t)seeds[i].len * p.a;
+                int j = n;
+                while (j > n0) {
+                    const int32_t s = W[j - 1].src;
+                    const int64_t kx = (int64_t)seeds[s].len * p.a;
+                    if (kx > ki || (kx == ki && s > i)) break;
+                    sel_copy(W + j, W + j - 1);
+                    --j;
+                }
+                W[j] = x;
+                ++n;
+            }
+            c0 = c1;
+        }
+        if (n > BSW_SEL_MAX_PER_READ) err = 1;
+        SelRd s;
+        s.n = n; s.i = 0; s.j = 0; s.w = 0;
+        st[r] = s;
+    }
+    int tot = n;
+    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+    const unsigned long long be = __ballot(err);
+    if ((threadIdx.x & 63) == 0) {
+        if (tot) atomicAdd(&meta[kSelRegsIn], tot);
+        if (be) atomicOr(&meta[kSelErr], 1);
+    }
+}
+
+// The i / j loop of read r from (i, j); have: score answers the patch_reg it was suspended at (a
+// global score may be negative, so the score itself cannot say so).  Returns true when it
+// suspends again (st[r] holds where; lq / rl its job's spans).
+__device__ __forceinline__ bool sel_dedup(const SelParams &p, int r, SelW *W, int n, int i, int j, int w, bool have,
+                                          int score,
+                          const uint8_t *__restrict__ q_codes, const uint8_t *__restrict__ ref, const int8_t *s_mat,
+                          SelRd *st, int32_t *meta, int &lq_out, int &rl_out)
+{
+    for (; i < n; ++i, j = -2) {
+        if (j == -2) {
+            if (W[i].r.rb >= W[i - 1].r.re + p.max_chain_gap) continue;
+            j = i - 1;
+        }
+        for (; j >= 0 && W[i].r.rb < W[j].r.re + p.max_chain_gap; --j) {
+            const bsw_alnreg_t P = W[i].r, Q = W[j].r;
+            if (!have) {
+                if (Q.qe == Q.qb) continue;
+                const int64_t orr = Q.re - P.rb;
+                const int oq = Q.qb < P.qb ? Q.qe - P.qb : P.qe - Q.qb;
+                const int64_t mr = min(Q.re - Q.rb, P.re - P.rb);
+                const int mq = min(Q.qe - Q.qb, P.qe - P.qb);
+                if ((float)orr > p.mask_level_redun * (float)mr && (float)oq > p.mask_level_redun * (float)mq) {
+                    atomicAdd(&meta[kSelRedundant], 1);
+                    if (P.score < Q.score) {
+                        W[i].r.qe = P.qb;
+                        break;
+                    }
+                    W[j].r.qe = Q.qb;
+                    continue;
+                }
+                if (!(Q.rb < P.rb)) continue;
+                // patch_reg(a = Q, b = P)
+                if (p.patch == 0) continue;
+                if (Q.rb < p.l_pac && P.rb >= p.l_pac) continue;
+                if (Q.qb >= P.qb || Q.qe >= P.qe || Q.re >= P.re) continue;
+                int64_t w64 = (Q.re - P.rb) - (int64_t)(Q.qe - P.qb);
+                w64 = w64 > 0 ? w64 : -w64;
+                const double rr = fabs((double)(Q.re - P.rb) / (double)(P.re - Q.rb) -
+                                       (double)(Q.qe - P.qb) / (double)(P.qe - Q.qb));
+                if (Q.re < P.rb || Q.qe < P.qb) {
+                    if (w64 > (int64_t)(p.W << 1) || rr >= 0.05) continue;
+                } else {
+                    if (w64 > (int64_t)(p.W << 2) || rr >= 0.10) continue;
+                }
+                w = (int)min(w64 + Q.w + P.w, (int64_t)(p.W << 2));
+                atomicAdd(&meta[kSelTried], 1);
+                const int64_t lq = (int64_t)P.qe - Q.qb, rl = P.re - Q.rb;
+                if (lq > BSW_MAX_LEN || rl > BSW_MAX_LEN) {
+                    atomicOr(&meta[kSelErr], 1);
+                    continue;
+                }
+                if (lq <= 0 || rl <= 0 || (p.l_pac > 0 && Q.rb < p.l_pac && P.re > p.l_pac)) {
+                    score = 0;                              // gen_cigar2 rejects the span
+                } else if (lq == rl && w == 0) {
+                    score = 0;                              // gen_cigar2's gap-free shortcut
+                    for (int c = 0; c < (int)lq; ++c)
+                        score += s_mat[min((int)ref[Q.rb + c], 4) * 5 + min((int)q_codes[Q.qb + c], 4)];
+                } else {
+                    SelRd s;
+                    s.n = n; s.i = i; s.j = j; s.w = w;
+                    st[r] = s;
+                    lq_out = (int)lq; rl_out = (int)rl;
+                    return true;
+                }
+            }
+            // the rest of patch_reg, then its caller
+            const int sum = P.score + Q.score;
+            const int q_s = (int)((double)(P.qe - Q.qb) / ((P.qe - P.qb) + (Q.qe - Q.qb)) * sum + .499);
+            const int r_s = (int)((double)(P.re - Q.rb) / (double)((P.re - P.rb) + (Q.re - Q.rb)) * sum + .499);
+            const int sc = score;
+            have = false;
+            if ((double)sc / max(q_s, r_s) < 0.90) {
+                atomicAdd(&meta[kSelRatio], 1);
+                continue;
+            }
+            if (sc <= 0) continue;
+            atomicAdd(&meta[kSelOk], 1);
+            const int ync = W[j].n_comp, ycov = W[j].seedcov, ysub = W[j].sub, ycsub = W[j].csub;
+            W[i].n_comp += ync + 1;
+            W[i].seedcov = max(W[i].seedcov, ycov);
+            W[i].sub = max(W[i].sub, ysub);
+            W[i].csub = max(W[i].csub, ycsub);
+            W[i].r.qb = Q.qb; W[i].r.rb = Q.rb;
+            W[i].r.truesc = W[i].r.score = sc;
+            W[i].r.w = w;
+            W[j].r.qb = Q.qe;
+        }
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(64) void sel_step_kernel(
+    const SelParams p, const int32_t *__restrict__ list, int32_t n_items, const SeqPair *__restrict__ pairs,
+    const int32_t *__restrict__ sbeg, const uint8_t *__restrict__ reads, const int64_t *__restrict__ read_off,
+    const float *__restrict__ frac_rep, const uint8_t *__restrict__ ref, SelW *__restrict__ work,
+    SelRd *__restrict__ st, int32_t *__restrict__ zbuf, int32_t *__restrict__ next, int32_t *__restrict__ next_cnt,
+    int32_t *__restrict__ kept, int32_t *__restrict__ meta)
+{
+    __shared__ int s_stk[kSelStack * 3 * 64];
+    __shared__ int8_t s_mat[32];
+#pragma unroll
+    for (int k = 0; k < 25; ++k)
+        if (threadIdx.x == k) s_mat[k] = p.mat[k];
+    __syncthreads();
+    const int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    bool susp = false;
+    int r = 0, lq = 0, rl = 0;
+    if (t < n_items && meta[kSelErr] == 0) {
+        r = list ? list[t] : t;
+        const SelRd s = st[r];
+        SelW *W = work + sbeg[r];
+        int *stk = s_stk + threadIdx.x;
+        const bool dedup = s.n > 1;
+        if (dedup) {
+            if (!list) sel_introsort(s.n, W, stk, LtRe());
+            susp = sel_dedup(p, r, W, s.n, list ? s.i : 1, list ? s.j : -2, s.w, list != nullptr, list ? pairs[t].score : 0,
+                             reads + read_off[r], ref, s_mat, st, meta, lq, rl);
+        }
+        if (!susp)
+            kept[r] = sel_finish(p, r, W, s.n, dedup, stk, zbuf + sbeg[r], frac_rep ? frac_rep[r] : 0.f, meta);
+    }
+    const unsigned long long b = __ballot(susp);
+    const int lane = threadIdx.x & 63;
+    const int mq = wave_max(lq), mt = wave_max(rl);
+    int base = 0;
+    if (lane == 0 && b) {
+        base = atomicAdd(next_cnt, __popcll(b));
+        atomicMax(&meta[kSelMaxQ], mq);
+        atomicMax(&meta[kSelMaxT], mt);
+    }
+    base = __shfl(base, 0);
+    if (susp) next[base + __popcll(b & ((1ull << lane) - 1))] = r;
+}
+
+__global__ void sel_build_kernel(const SelParams p, const int32_t *__restrict__ list, int32_t nj,
+                                 const int32_t *__restrict__ sbeg, const uint8_t *__restrict__ reads,
+                                 const int64_t *__restrict__ read_off, const SelW *__restrict__ work,
+                                 const SelRd *__restrict__ st, const uint8_t *__restrict__ ref,
+                                 SeqPair *__restrict__ pairs, uint8_t *__restrict__ qbuf, uint8_t *__restrict__ tbuf)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = (int)(t >> 4), sub = (int)(t & 15);
+    if (j >= nj) return;
+    const int rd = list[j];
+    const SelRd s = st[rd];
+    const SelW *W = work + sbeg[rd];
+    const int qb = W[s.j].r.qb, qe = W[s.i].r.qe;
+    const int64_t rb = W[s.j].r.rb, re = W[s.i].r.re;
+    const int lq = qe - qb, rl = (int)(re - rb);
+    const uint8_t *q = reads + read_off[rd];
+    uint8_t *qd = qbuf + (int64_t)j * p.qstride, *td = tbuf + (int64_t)j * p.tstride;
+    if (sub == 0) {
+        SeqPair sp{};
+        sp.idr = j * p.tstride; sp.idq = j * p.qstride; sp.id = j;
+        sp.len1 = rl; sp.len2 = lq;
+        sp.h0 = sel_cigar_band(p, lq, rl, s.w);
+        pairs[j] = sp;
+    }
+    if (p.l_pac > 0 && rb >= p.l_pac) {
+        for (int k = sub; k < lq; k += 16) qd[k] = q[qe - 1 - k];
+        for (int k = sub; k < rl; k += 16) td[k] = ref[re - 1 - k];
+    } else {
+        for (int k = sub; k < lq; k += 16) qd[k] = q[qb + k];
+        for (int k = sub; k < rl; k += 16) td[k] = ref[rb + k];
+    }
+}
+
+__global__ void sel_emit_kernel(const SelParams p, const int32_t *__restrict__ sr, const int32_t *__restrict__ sbeg,
+                                const int32_t *__restrict__ kept, const int32_t *__restrict__ first,
+                                const SelW *__restrict__ work, const float *__restrict__ frac_rep,
+                                bsw_alnreg_t *__restrict__ sel_regs, int32_t *__restrict__ sel_read,
+                                bsw_selinfo_t *__restrict__ sel_info)
+{
+    const int32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= p.n_seeds) return;
+    const int32_t r = sr[k], idx = k - sbeg[r];
+    if (idx >= kept[r]) return;
+    const SelW x = work[k];
+    const int32_t o = first[r] + idx;
+    sel_regs[o] = x.r;
+    sel_read[o] = r;
+    bsw_selinfo_t f;
+    f.seedcov = x.seedcov; f.sub = x.sub; f.csub = x.csub; f.sub_n = x.sub_n; f.n_comp = x.n_comp;
+    f.secondary = x.secondary; f.mapq = x.mapq; f.src = x.src; f.frac_rep = frac_rep ? frac_rep[r] : 0.f;
+    sel_info[o] = f;
+}
+
+static inline dim3 grid_of(int64_t n, int b) { return dim3((unsigned)((n + b - 1) / b)); }
+
+hipError_t launch_sel_runs(const int32_t *seed_read, int32_t n_seeds, int32_t n_reads, int32_t *sbeg, int32_t *send,
+                           int32_t *meta, hipStream_t s)
+{
+    if (n_seeds <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sel_runs_kernel, grid_of(n_seeds, 256), dim3(256), 0, s, seed_read, n_seeds, n_reads, sbeg, send,
+                       meta);
+    return hipGetLastError();
+}
+
+hipError_t launch_sel_gather(const SelParams &p, const int32_t *sbeg, const int32_t *send, const int32_t *read_len,
+                             const bsw_seed_t *seeds, const int32_t *seed_chain, const bsw_alnreg_t *regs,
+                             const int32_t *extended, const int32_t *csub, SelW *work, SelRd *st, int32_t *meta,
+                             hipStream_t s)
+{
+    if (p.n_reads <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sel_gather_kernel, grid_of(p.n_reads, 64), dim3(64), 0, s, p, sbeg, send, read_len, seeds,
+                       seed_chain, regs, extended, csub, work, st, meta);
+    return hipGetLastError();
+}
+
+hipError_t launch_sel_step(const SelParams &p, const int32_t *list, int32_t n, const SeqPair *pairs,
+                           const int32_t *sbeg, const uint8_t *reads, const int64_t *read_off, const float *frac_rep,
+                           const uint8_t *ref, SelW *work, SelRd *st, int32_t *zbuf, int32_t *next,
+                           int32_t *next_cnt, int32_t *kept, int32_t *meta, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sel_step_kernel, grid_of(n, 64), dim3(64), 0, s, p, list, n, pairs, sbeg, reads, read_off,
+                       frac_rep, ref, work, st, zbuf, next, next_cnt, kept, meta);
+    return hipGetLastError();
+}
+
+hipError_t launch_sel_build(const SelParams &p, const int32_t *list, int32_t nj, const int32_t *sbeg,
+                            const uint8_t *reads, const int64_t *read_off, const SelW *work, const SelRd *st,
+                            const uint8_t *ref, SeqPair *pairs, uint8_t *qbuf, uint8_t *tbuf, hipStream_t s)
+{
+    if (nj <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sel_build_kernel, grid_of((int64_t)nj * 16, 256), dim3(256), 0, s, p, list, nj, sbeg, reads,
+                       read_off, work, st, ref, pairs, qbuf, tbuf);
+    return hipGetLastError();
+}
+
+hipError_t launch_sel_scan(void *tmp, size_t *tmp_bytes, const int32_t *kept, int32_t *first, int32_t n_reads,
+                           hipStream_t s)
+{
+    return hipcub::DeviceScan::ExclusiveSum(tmp, *tmp_bytes, kept, first, n_reads + 1, s);
+}
+
+hipError_t launch_sel_emit(const SelParams &p, const int32_t *seed_read, const int32_t *sbeg, const int32_t *kept,
+                           const int32_t *first, const SelW *work, const float *frac_rep, bsw_alnreg_t *sel_regs,
+                           int32_t *sel_read, bsw_selinfo_t *sel_info, hipStream_t s)
+{
+    if (p.n_seeds <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sel_emit_kernel, grid_of(p.n_seeds, 256), dim3(256), 0, s, p, seed_read, sbeg, kept, first, work,
+                       frac_rep, sel_regs, sel_read, sel_info);
+    return hipGetLastError();
+}
+
+}  // namespace bsw

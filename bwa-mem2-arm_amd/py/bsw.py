@@ -41,6 +41,8 @@ ABI_SYMBOLS = ("bsw_params_default", "bsw_create", "bsw_create_on", "bsw_destroy
 
 # include/bsw_aln.h (additive to ABI version 8: its functions are listed here, not in ABI_SYMBOLS)
 ALN_SYMBOLS = ("bsw_reg2aln", "bsw_reg2aln_resident", "bsw_aln_last_stats")
+# include/bsw_sel.h (additive in the same way)
+SEL_SYMBOLS = ("bsw_sel_opt_default", "bsw_regs_select", "bsw_regs_select_resident", "bsw_sel_last_stats")
 
 # include/bsw.h engine options (bsw_set_option)
 OPT_KERNEL8, OPT_FORK, OPT_SORTKEY, OPT_GLOB_BAND, OPT_EXT_CHUNK, OPT_HOST_CHUNK, OPT_LONG, OPT_HOST_PACK = 1, 2, 3, 4, 5, 6, 7, 8
@@ -68,6 +70,11 @@ ALN_DTYPE = np.dtype([("pos", np.int64), ("is_rev", np.int32), ("n_cigar", np.in
                       ("flags", np.int32)])
 assert ALN_DTYPE.itemsize == 40
 ALN_REJECTED, ALN_NODP, ALN_OVERFLOW = 1, 2, 4
+# include/bsw_sel.h
+SELINFO_DTYPE = np.dtype([("seedcov", np.int32), ("sub", np.int32), ("csub", np.int32), ("sub_n", np.int32),
+                          ("n_comp", np.int32), ("secondary", np.int32), ("mapq", np.int32), ("src", np.int32),
+                          ("frac_rep", np.float32)])
+assert SELINFO_DTYPE.itemsize == 36
 
 # include/bsw_mate.h
 KSW_XBYTE, KSW_XSTOP, KSW_XSUBO, KSW_XSTART = 0x10000, 0x20000, 0x40000, 0x80000
@@ -180,6 +187,14 @@ def hip_lib():
                                            P, ctypes.c_int32, P]
         L.bsw_aln_last_stats.argtypes = [P, P]
         for f in ALN_SYMBOLS:
+            getattr(L, f).restype = ctypes.c_int
+        L.bsw_sel_opt_default.argtypes = [P]
+        L.bsw_sel_opt_default.restype = None
+        L.bsw_regs_select.argtypes = [P, P, P, P, P, ctypes.c_int32, P, P, P, P, P, ctypes.c_int32, P, P, P, P, P, P,
+                                      ctypes.c_int32, P]
+        L.bsw_regs_select_resident.argtypes = L.bsw_regs_select.argtypes + [P]
+        L.bsw_sel_last_stats.argtypes = [P, P]
+        for f in SEL_SYMBOLS[1:]:
             getattr(L, f).restype = ctypes.c_int
         L.bsw_get_scores_packed_device.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int, P, P]
         for f in ("bsw_create", "bsw_create_on", "bsw_get_scores", "bsw_get_scores_device", "bsw_last_stats",
@@ -698,6 +713,100 @@ def reg2aln_resident(engine, d_reads: int, d_off: int, d_len: int, n_reads: int,
 def aln_last_stats(engine) -> AlnStats:
     st = AlnStats()
     _check(hip_lib().bsw_aln_last_stats(engine._ctx, ctypes.byref(st)))
+    return st
+
+
+# ---------------------------------------------------------------- region selection (bsw_sel.h)
+class SelOpt(ctypes.Structure):
+    """Mirror of bsw_sel_opt_t (include/bsw_sel.h)."""
+    _fields_ = [("w", ctypes.c_int32), ("max_chain_gap", ctypes.c_int32), ("l_pac", ctypes.c_int64),
+                ("mask_level_redun", ctypes.c_float), ("mask_level", ctypes.c_float),
+                ("min_seed_len", ctypes.c_int32), ("b", ctypes.c_int32), ("mapQ_coef_len", ctypes.c_int32),
+                ("mapQ_coef_fac", ctypes.c_int32), ("patch", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("id0", ctypes.c_int64)]
+
+
+class SelStats(ctypes.Structure):
+    _fields_ = [("n_reads", ctypes.c_int32), ("n_regs_in", ctypes.c_int32), ("n_redundant", ctypes.c_int32),
+                ("n_identical", ctypes.c_int32), ("n_patch_tried", ctypes.c_int32), ("n_patch_ok", ctypes.c_int32),
+                ("n_patch_ratio", ctypes.c_int32), ("n_dp", ctypes.c_int32), ("rounds", ctypes.c_int32),
+                ("n_sel", ctypes.c_int32), ("dp_ms", ctypes.c_float), ("helper_ms", ctypes.c_float)]
+
+
+def sel_opt(**kw) -> SelOpt:
+    o = SelOpt()
+    hip_lib().bsw_sel_opt_default(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def regs_select(engine, reads, read_off, read_len, seeds, seed_read, seed_chain, regs, extended,
+                opt: SelOpt | None = None, csub=None, frac_rep=None, sel_cap: int | None = None):
+    """bsw_regs_select (host arrays, resident reference required): the regions bsw_chain2aln* left
+    -> (sel_regs ALNREG_DTYPE, sel_read int32, sel_info SELINFO_DTYPE, read_first int32 [n_reads + 1]).
+    A sel_cap below the number kept raises BswError with .needed set."""
+    opt = opt if opt is not None else sel_opt()
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+    read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+    seeds = np.ascontiguousarray(seeds, dtype=SEED_DTYPE)
+    seed_read = np.ascontiguousarray(seed_read, dtype=np.int32)
+    seed_chain = np.ascontiguousarray(seed_chain, dtype=np.int32)
+    regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
+    extended = np.ascontiguousarray(extended, dtype=np.int32)
+    csub = None if csub is None else np.ascontiguousarray(csub, dtype=np.int32)
+    frac_rep = None if frac_rep is None else np.ascontiguousarray(frac_rep, dtype=np.float32)
+    n = len(seeds)
+    assert len(seed_read) == len(seed_chain) == len(regs) == len(extended) == n
+    assert (csub is None or len(csub) == n) and (frac_rep is None or len(frac_rep) == len(read_len))
+    cap = n if sel_cap is None else sel_cap
+    sel_regs = np.zeros(max(cap, 1), dtype=ALNREG_DTYPE)
+    sel_read = np.zeros(max(cap, 1), dtype=np.int32)
+    sel_info = np.zeros(max(cap, 1), dtype=SELINFO_DTYPE)
+    first = np.zeros(len(read_len) + 1, dtype=np.int32)
+    n_sel = ctypes.c_int32(-1)
+    rc = hip_lib().bsw_regs_select(engine._ctx, ctypes.byref(opt), _ptr(reads), _ptr(read_off), _ptr(read_len),
+                                   len(read_len), _ptr(seeds), _ptr(seed_read), _ptr(seed_chain), _ptr(regs),
+                                   _ptr(extended), n, _ptr(csub) if csub is not None else None,
+                                   _ptr(frac_rep) if frac_rep is not None else None, _ptr(sel_regs), _ptr(sel_read),
+                                   _ptr(sel_info), _ptr(first), cap, ctypes.byref(n_sel))
+    if rc != 0:
+        try:
+            _check(rc)
+        except BswError as e:
+            e.needed = n_sel.value
+            raise
+    k = n_sel.value
+    return sel_regs[:k], sel_read[:k], sel_info[:k], first
+
+
+def regs_select_resident(engine, d_reads: int, d_off: int, d_len: int, n_reads: int, d_seeds: int, d_sr: int,
+                         d_sc: int, d_regs: int, d_ext: int, n_seeds: int, d_sel_regs: int, d_sel_read: int,
+                         d_sel_info: int, d_read_first: int, sel_cap: int, opt: SelOpt | None = None,
+                         d_csub: int = 0, d_frac_rep: int = 0, stream: int = 0) -> int:
+    """bsw_regs_select_resident: every array a device pointer (the inputs as bsw_chain2aln_resident
+    takes and leaves them; d_sel_regs / d_sel_read feed bsw_reg2aln_resident).  Returns n_sel."""
+    opt = opt if opt is not None else sel_opt()
+    V = ctypes.c_void_p
+    n_sel = ctypes.c_int32(-1)
+    rc = hip_lib().bsw_regs_select_resident(engine._ctx, ctypes.byref(opt), V(d_reads), V(d_off), V(d_len), n_reads,
+                                            V(d_seeds), V(d_sr), V(d_sc), V(d_regs), V(d_ext), n_seeds,
+                                            V(d_csub or None), V(d_frac_rep or None), V(d_sel_regs), V(d_sel_read),
+                                            V(d_sel_info), V(d_read_first), sel_cap, ctypes.byref(n_sel),
+                                            V(stream or None))
+    if rc != 0:
+        try:
+            _check(rc)
+        except BswError as e:
+            e.needed = n_sel.value
+            raise
+    return n_sel.value
+
+
+def sel_last_stats(engine) -> SelStats:
+    st = SelStats()
+    _check(hip_lib().bsw_sel_last_stats(engine._ctx, ctypes.byref(st)))
     return st
 
 
