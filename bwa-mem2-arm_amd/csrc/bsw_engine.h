@@ -22,6 +22,7 @@
 #include "../../include/bsw_global.h"
 #include "../../include/bsw_aln.h"
 #include "../../include/bsw_sel.h"
+#include "../../include/bsw_pe.h"
 #include "bsw_kernels.h"
 #include "bsw_internal.h"
 
@@ -134,6 +135,7 @@ struct ExtState;
 struct AlnState;
 struct SelW;
 struct SelRd;
+struct PeV;
 // Everything one call needs on one device.  Members are destroyed in reverse order: buffers, then
 // events, then streams.
 struct BSW_HIDDEN Slot {
@@ -200,6 +202,11 @@ struct BSW_HIDDEN Slot {
     DevBuf<int32_t> d_skept;            // kept counts, n_reads + 1
     DevBuf<int32_t> d_slist;            // suspended reads of two rounds (ping-pong), n_reads each
     DevBuf<int32_t> d_smeta;            // kSelMetaWords
+    // paired-end stage (bsw_pe.h); its general path marks in d_swork / d_sz, its host forms stage in d_aio
+    DevBuf<int32_t> d_phist;            // insert-size counts, 4 x (max_ins + 1)
+    DevBuf<int32_t> d_pmeta;            // kPeMetaWords
+    DevBuf<int32_t> d_plist;            // pairs of the general path, n_pairs
+    DevBuf<PeV> d_pv;                   // mem_pair's v (flat, a pair's at its first region)
     bool timed = false;
     hipStream_t run_stream = nullptr;   // stream of the last run_device (finish_stats waits on it)
     bsw_stats_t stats{};
@@ -366,6 +373,7 @@ struct bsw_ctx {
     bsw_global_stats_t glob_last{};
     bsw_aln_stats_t aln_last{};
     bsw_sel_stats_t sel_last{};
+    bsw_pe_stats_t pe_last{};
     struct Pinned { std::mutex mu; bsw::PinnedBuf<uint8_t> b; } pin[2];
     int glob_band = 0;                  // BSW_OPT_GLOB_BAND
     int64_t ext_chunk = 0;              // BSW_OPT_EXT_CHUNK (0: the int32-offset bound)

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -29,6 +30,7 @@
 #include "bsw_ext_k.h"
 #include "bsw_aln_k.h"
 #include "bsw_sel_k.h"
+#include "bsw_pe_k.h"
 
 namespace bsw {
 
@@ -1514,6 +1516,331 @@ int bsw_sel_last_stats(bsw_ctx_t *ctx, bsw_sel_stats_t *out)
     if (!ctx || !out) return BSW_E_INVAL;
     std::lock_guard<std::mutex> g(ctx->stats_mu);
     *out = ctx->sel_last;
+    return BSW_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- paired-end stage (bsw_pe.h)
+namespace bsw {
+
+// argument checks of both calls and both forms, before anything touches a device
+static int pe_check_args(const bsw_pe_opt_t *opt, int32_t n_reads, int32_t n_regs)
+{
+    if (!opt || n_reads < 0 || (n_reads & 1) || n_regs < 0) return BSW_E_INVAL;
+    if (opt->l_pac <= 0 || (opt->id0 & 1) || opt->max_ins < 1 || opt->max_ins > BSW_PE_MAX_INS) return BSW_E_INVAL;
+    if (opt->min_seed_len < 0 || opt->b < 0 || opt->mapQ_coef_len < 0) return BSW_E_INVAL;
+    return BSW_OK;
+}
+
+static int pe_check_pes(const bsw_pestat_t *pes)
+{
+    if (!pes) return BSW_E_INVAL;
+    for (int d = 0; d < 4; ++d)
+        if (!pes[d].failed && !(std::isfinite(pes[d].std) && pes[d].std > 0 && std::isfinite(pes[d].avg)))
+            return BSW_E_INVAL;
+    return BSW_OK;
+}
+
+// the caller holds dc.refmu shared
+static int pe_check_ref(const bsw_pe_opt_t &opt, DeviceCtx &dc)
+{
+    return dc.d_refres && dc.refres_len != 2 * opt.l_pac ? BSW_E_INVAL : BSW_OK;
+}
+
+static void make_pe_params(const bsw_ctx_t *ctx, const bsw_pe_opt_t &opt, int32_t n_reads, int32_t n_regs, PeParams &p)
+{
+    const bsw_params_t &pr = ctx->params;
+    memset(&p, 0, sizeof(p));
+    p.s.a = pr.mat[0]; p.s.b = opt.b;
+    p.s.o_del = pr.o_del; p.s.e_del = pr.e_del; p.s.o_ins = pr.o_ins; p.s.e_ins = pr.e_ins;
+    p.s.n_reads = n_reads;
+    p.s.min_seed_len = opt.min_seed_len; p.s.mapQ_coef_len = opt.mapQ_coef_len; p.s.mapQ_coef_fac = opt.mapQ_coef_fac;
+    p.s.mask_level = opt.mask_level;
+    p.s.l_pac = opt.l_pac; p.s.id0 = opt.id0;
+    p.n_pairs = n_reads / 2; p.n_regs = n_regs;
+    p.max_ins = opt.max_ins; p.T = opt.T; p.pen_unpaired = opt.pen_unpaired;
+}
+
+// mem_pestat's per-direction arithmetic over the counts c[v] of insert size v (bsw_pe.h)
+static void pestat_of_counts(const int32_t *hist, int bins, bsw_pestat_t *pes)
+{
+    int64_t nmax = 0;
+    for (int d = 0; d < 4; ++d) {
+        const int32_t *c = hist + (size_t)d * bins;
+        int64_t n = 0;
+        for (int v = 0; v < bins; ++v) n += c[v];
+        bsw_pestat_t r{};
+        r.n = (int32_t)n;
+        nmax = std::max(nmax, n);
+        if (n < 10) {
+            r.failed = 1;
+            pes[d] = r;
+            continue;
+        }
+        auto at = [&](int k) {                      // the k-th smallest value
+            int64_t acc = 0;
+            for (int v = 0; v < bins; ++v) {
+                acc += c[v];
+                if (acc > k) return v;
+            }
+            return bins - 1;
+        };
+        const int p25 = at((int)(.25 * n + .499)), p75 = at((int)(.75 * n + .499));
+        r.low = (int)(p25 - 2.0 * (p75 - p25) + .499);
+        if (r.low < 1) r.low = 1;
+        r.high = (int)(p75 + 2.0 * (p75 - p25) + .499);
+        int64_t x = 0;
+        const int v0 = std::max(r.low, 0), v1 = std::min(r.high, bins - 1);
+        for (int v = v0; v <= v1; ++v) {
+            r.avg += (double)c[v] * v;              // (sums of integers: exact in any order)
+            x += c[v];
+        }
+        r.avg /= x;
+        for (int v = v0; v <= v1; ++v) r.std += (double)c[v] * ((v - r.avg) * (v - r.avg));
+        r.std = sqrt(r.std / x);
+        r.low = (int)(p25 - 3.0 * (p75 - p25) + .499);
+        r.high = (int)(p75 + 3.0 * (p75 - p25) + .499);
+        if (r.low > r.avg - 4.0 * r.std) r.low = (int)(r.avg - 4.0 * r.std + .499);
+        if (r.high < r.avg + 4.0 * r.std) r.high = (int)(r.avg + 4.0 * r.std + .499);
+        if (r.low < 1) r.low = 1;
+        pes[d] = r;
+    }
+    for (int d = 0; d < 4; ++d)
+        if (pes[d].failed == 0 && pes[d].n < nmax * 0.05) pes[d].failed = 1;
+}
+
+static int pe_events(Slot &s)
+{
+    if (!s.ev2) BSW_TRY(hipEventCreate(&s.ev2.p));
+    if (!s.ev3) BSW_TRY(hipEventCreate(&s.ev3.p));
+    return BSW_OK;
+}
+
+// count kernel -> the four count arrays and the error word back -> the statistics on the host
+static int pe_stat_device(bsw_ctx_t *ctx, Slot &s, hipStream_t st, const bsw_pe_opt_t &opt, const bsw_alnreg_t *regs,
+                          const int32_t *first, int32_t n_reads, int32_t n_regs, bsw_pestat_t *pes, bsw_pe_stats_t &ps)
+{
+    PeParams p;
+    make_pe_params(ctx, opt, n_reads, n_regs, p);
+    const int bins = opt.max_ins + 1;
+    BSW_TRY(s.d_phist.grow((size_t)4 * bins));
+    BSW_TRY(s.d_pmeta.grow(kPeSlots * kPeMetaWords));
+    if (int r = pe_events(s)) return r;
+    std::vector<int32_t> h((size_t)4 * bins);
+    int32_t *h_meta = s.h_meta;
+    BSW_TRY(hipMemsetAsync(s.d_phist, 0, h.size() * sizeof(int32_t), st));
+    BSW_TRY(hipMemsetAsync(s.d_pmeta, 0, kPeSlots * kPeMetaWords * sizeof(int32_t), st));
+    BSW_TRY(hipEventRecord(s.ev2, st));
+    BSW_TRY(launch_pe_stat(p, regs, first, s.d_phist, s.d_pmeta, st));
+    BSW_TRY(hipEventRecord(s.ev3, st));
+    BSW_TRY(hipMemcpyAsync(h_meta, s.d_pmeta, kPeSlots * kPeMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h.data(), s.d_phist, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(hipEventElapsedTime(&ps.kernel_ms, s.ev2, s.ev3));
+    if (h_meta[kPeErr]) return BSW_E_RANGE;
+    pestat_of_counts(h.data(), bins, pes);
+    for (int d = 0; d < 4; ++d) ps.n_cand[d] = pes[d].n;
+    return BSW_OK;
+}
+
+// fast kernel over every pair -> general kernel over the pairs it listed (their count stays on
+// the device) -> the counters back
+static int pe_pair_device(bsw_ctx_t *ctx, Slot &s, hipStream_t st, const bsw_pe_opt_t &opt, const bsw_pestat_t *pes,
+                          bsw_alnreg_t *regs, bsw_selinfo_t *info, const int32_t *first, int32_t n_reads,
+                          int32_t n_regs, bsw_pair_t *pairs, bsw_pe_stats_t &ps)
+{
+    PeParams p;
+    make_pe_params(ctx, opt, n_reads, n_regs, p);
+    for (int d = 0; d < 4; ++d) {
+        p.pes[d].avg = pes[d].avg; p.pes[d].std = pes[d].std;
+        p.pes[d].low = pes[d].low; p.pes[d].high = pes[d].high; p.pes[d].failed = pes[d].failed != 0;
+    }
+    const size_t ng = std::max<size_t>((size_t)n_regs, 1);
+    BSW_TRY(s.d_swork.grow(ng));
+    BSW_TRY(s.d_sz.grow(ng));
+    BSW_TRY(s.d_pv.grow(ng));
+    BSW_TRY(s.d_plist.grow(std::max<size_t>((size_t)p.n_pairs, 1)));
+    BSW_TRY(s.d_pmeta.grow(kPeSlots * kPeMetaWords));
+    if (int r = pe_events(s)) return r;
+    int32_t *h_meta = s.h_meta;
+    BSW_TRY(hipMemsetAsync(s.d_pmeta, 0, kPeSlots * kPeMetaWords * sizeof(int32_t), st));
+    BSW_TRY(hipEventRecord(s.ev2, st));
+    BSW_TRY(launch_pe_pair_fast(p, regs, info, first, pairs, s.d_plist, s.d_pmeta, st));
+    BSW_TRY(launch_pe_pair_general(p, regs, info, first, pairs, s.d_plist, s.d_swork, s.d_sz, s.d_pv, s.d_pmeta, st));
+    BSW_TRY(hipEventRecord(s.ev3, st));
+    BSW_TRY(hipMemcpyAsync(h_meta, s.d_pmeta, kPeSlots * kPeMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(hipEventElapsedTime(&ps.kernel_ms, s.ev2, s.ev3));
+    if (h_meta[kPeErr]) return BSW_E_RANGE;
+    static_assert(kPeSlots * kPeMetaWords <= kMetaWords, "the slot's pinned mirror holds the pair counters");
+    for (int k = 0; k < kPeSlots; ++k) {
+        const int32_t *m = h_meta + k * kPeMetaWords;
+        int64_t nu;
+        memcpy(&nu, m + kPeNu, sizeof(nu));
+        ps.n_pairing_tried += m[kPeTried];
+        ps.n_paired += m[kPePaired];
+        ps.n_multi += m[kPeMulti];
+        ps.n_unpaired_preferred += m[kPeUnpaired];
+        ps.n_proper += m[kPeProper];
+        ps.n_u += nu;
+    }
+    return BSW_OK;
+}
+
+static void set_pe_stats(bsw_ctx_t *ctx, const bsw_pe_stats_t &ps)
+{
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    ctx->pe_last = ps;
+}
+
+// host forms: read_first as the device will check it, so the staged sizes can be trusted
+static int pe_host_first(const int32_t *read_first, int32_t n_reads, int32_t &n_regs)
+{
+    if (!read_first) return BSW_E_INVAL;
+    if (read_first[0] < 0) return BSW_E_RANGE;
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (read_first[r + 1] < read_first[r]) return BSW_E_RANGE;
+    n_regs = read_first[n_reads];
+    return BSW_OK;
+}
+
+}  // namespace bsw
+
+extern "C" {
+
+void bsw_pe_opt_default(bsw_pe_opt_t *opt)
+{
+    if (!opt) return;
+    memset(opt, 0, sizeof(*opt));
+    opt->max_ins = 10000;
+    opt->min_seed_len = 19;
+    opt->b = 4;
+    opt->T = 30;
+    opt->pen_unpaired = 17;
+    opt->mapQ_coef_len = 50;
+    opt->mapQ_coef_fac = 3;
+    opt->mask_level = 0.5f;
+}
+
+int bsw_pe_stat_resident(bsw_ctx_t *ctx, const bsw_pe_opt_t *opt, const bsw_alnreg_t *d_sel_regs,
+                         const bsw_selinfo_t *d_sel_info, const int32_t *d_read_first, int32_t n_reads,
+                         int32_t n_regs, bsw_pestat_t *pes, void *stream)
+{
+    (void)d_sel_info;                   // (the statistics read the regions alone)
+    if (const int rc = bsw::pe_check_args(opt, n_reads, n_regs)) return rc;
+    if (!ctx || !pes || !d_read_first || (n_regs > 0 && !d_sel_regs)) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::pe_check_ref(*opt, dc)) return rc;
+    bsw_pe_stats_t ps{};
+    ps.n_pairs = n_reads / 2;
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::pe_stat_device(ctx, s, st, *opt, d_sel_regs, d_read_first, n_reads, n_regs, pes, ps);
+    });
+    if (rc) return rc;
+    bsw::set_pe_stats(ctx, ps);
+    return BSW_OK;
+}
+
+int bsw_pe_stat(bsw_ctx_t *ctx, const bsw_pe_opt_t *opt, const bsw_alnreg_t *sel_regs, const bsw_selinfo_t *sel_info,
+                const int32_t *read_first, int32_t n_reads, bsw_pestat_t *pes)
+{
+    (void)sel_info;
+    if (const int rc = bsw::pe_check_args(opt, n_reads, 0)) return rc;
+    if (!ctx || !pes) return BSW_E_INVAL;
+    int32_t n_regs = 0;
+    if (const int rc = bsw::pe_host_first(read_first, n_reads, n_regs)) return rc;
+    if (n_regs > 0 && !sel_regs) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::pe_check_ref(*opt, dc)) return rc;
+    bsw_pe_stats_t ps{};
+    ps.n_pairs = n_reads / 2;
+    const size_t part[2] = {(size_t)n_regs * sizeof(bsw_alnreg_t), ((size_t)n_reads + 1) * sizeof(int32_t)};
+    const size_t off1 = (part[0] + 15) & ~(size_t)15;
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(s.d_aio.grow(off1 + part[1] + 16));
+        uint8_t *b = s.d_aio;
+        if (part[0]) BSW_TRY(hipMemcpyAsync(b, sel_regs, part[0], hipMemcpyHostToDevice, s.stream));
+        BSW_TRY(hipMemcpyAsync(b + off1, read_first, part[1], hipMemcpyHostToDevice, s.stream));
+        return bsw::pe_stat_device(ctx, s, s.stream, *opt, (const bsw_alnreg_t *)b, (const int32_t *)(b + off1), n_reads,
+                                   n_regs, pes, ps);
+    });
+    if (rc) return rc;
+    bsw::set_pe_stats(ctx, ps);
+    return BSW_OK;
+}
+
+int bsw_pe_pair_resident(bsw_ctx_t *ctx, const bsw_pe_opt_t *opt, const bsw_pestat_t *pes, bsw_alnreg_t *d_sel_regs,
+                         bsw_selinfo_t *d_sel_info, const int32_t *d_read_first, int32_t n_reads, int32_t n_regs,
+                         bsw_pair_t *d_pairs, void *stream)
+{
+    if (const int rc = bsw::pe_check_args(opt, n_reads, n_regs)) return rc;
+    if (const int rc = bsw::pe_check_pes(pes)) return rc;
+    if (!ctx || !d_read_first || (n_regs > 0 && (!d_sel_regs || !d_sel_info)) || (n_reads > 0 && !d_pairs))
+        return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::pe_check_ref(*opt, dc)) return rc;
+    bsw_pe_stats_t ps{};
+    ps.n_pairs = n_reads / 2;
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::pe_pair_device(ctx, s, st, *opt, pes, d_sel_regs, d_sel_info, d_read_first, n_reads, n_regs, d_pairs,
+                                   ps);
+    });
+    if (rc) return rc;
+    bsw::set_pe_stats(ctx, ps);
+    return BSW_OK;
+}
+
+int bsw_pe_pair(bsw_ctx_t *ctx, const bsw_pe_opt_t *opt, const bsw_pestat_t *pes, bsw_alnreg_t *sel_regs,
+                bsw_selinfo_t *sel_info, const int32_t *read_first, int32_t n_reads, bsw_pair_t *pairs)
+{
+    if (const int rc = bsw::pe_check_args(opt, n_reads, 0)) return rc;
+    if (const int rc = bsw::pe_check_pes(pes)) return rc;
+    if (!ctx || (n_reads > 0 && !pairs)) return BSW_E_INVAL;
+    int32_t n_regs = 0;
+    if (const int rc = bsw::pe_host_first(read_first, n_reads, n_regs)) return rc;
+    if (n_regs > 0 && (!sel_regs || !sel_info)) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::pe_check_ref(*opt, dc)) return rc;
+    bsw_pe_stats_t ps{};
+    ps.n_pairs = n_reads / 2;
+    // one staged blob: regions, info, offsets, pairs, each part 16-B aligned
+    const size_t part[4] = {(size_t)n_regs * sizeof(bsw_alnreg_t), (size_t)n_regs * sizeof(bsw_selinfo_t),
+                            ((size_t)n_reads + 1) * sizeof(int32_t), (size_t)(n_reads / 2) * sizeof(bsw_pair_t)};
+    size_t off[5] = {0};
+    for (int k = 0; k < 4; ++k) off[k + 1] = off[k] + ((part[k] + 15) & ~(size_t)15);
+    const void *src[3] = {sel_regs, sel_info, read_first};
+    void *dst[4] = {sel_regs, sel_info, nullptr, pairs};
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(s.d_aio.grow(off[4] + 16));
+        uint8_t *b = s.d_aio;
+        for (int k = 0; k < 3; ++k)
+            if (part[k]) BSW_TRY(hipMemcpyAsync(b + off[k], src[k], part[k], hipMemcpyHostToDevice, s.stream));
+        if (int r = bsw::pe_pair_device(ctx, s, s.stream, *opt, pes, (bsw_alnreg_t *)(b + off[0]),
+                                        (bsw_selinfo_t *)(b + off[1]), (const int32_t *)(b + off[2]), n_reads, n_regs,
+                                        (bsw_pair_t *)(b + off[3]), ps))
+            return r;
+        for (int k = 0; k < 4; ++k)
+            if (dst[k] && part[k]) BSW_TRY(hipMemcpyAsync(dst[k], b + off[k], part[k], hipMemcpyDeviceToHost, s.stream));
+        BSW_TRY(hipStreamSynchronize(s.stream));
+        return BSW_OK;
+    });
+    if (rc) return rc;
+    bsw::set_pe_stats(ctx, ps);
+    return BSW_OK;
+}
+
+int bsw_pe_last_stats(bsw_ctx_t *ctx, bsw_pe_stats_t *out)
+{
+    if (!ctx || !out) return BSW_E_INVAL;
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    *out = ctx->pe_last;
     return BSW_OK;
 }
 

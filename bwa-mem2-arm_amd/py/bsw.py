@@ -43,6 +43,9 @@ ABI_SYMBOLS = ("bsw_params_default", "bsw_create", "bsw_create_on", "bsw_destroy
 ALN_SYMBOLS = ("bsw_reg2aln", "bsw_reg2aln_resident", "bsw_aln_last_stats")
 # include/bsw_sel.h (additive in the same way)
 SEL_SYMBOLS = ("bsw_sel_opt_default", "bsw_regs_select", "bsw_regs_select_resident", "bsw_sel_last_stats")
+# include/bsw_pe.h (additive in the same way)
+PE_SYMBOLS = ("bsw_pe_opt_default", "bsw_pe_stat", "bsw_pe_stat_resident", "bsw_pe_pair", "bsw_pe_pair_resident",
+              "bsw_pe_last_stats")
 
 # include/bsw.h engine options (bsw_set_option)
 OPT_KERNEL8, OPT_FORK, OPT_SORTKEY, OPT_GLOB_BAND, OPT_EXT_CHUNK, OPT_HOST_CHUNK, OPT_LONG, OPT_HOST_PACK = 1, 2, 3, 4, 5, 6, 7, 8
@@ -75,6 +78,13 @@ SELINFO_DTYPE = np.dtype([("seedcov", np.int32), ("sub", np.int32), ("csub", np.
                           ("n_comp", np.int32), ("secondary", np.int32), ("mapq", np.int32), ("src", np.int32),
                           ("frac_rep", np.float32)])
 assert SELINFO_DTYPE.itemsize == 36
+# include/bsw_pe.h
+PESTAT_DTYPE = np.dtype([("low", np.int32), ("high", np.int32), ("failed", np.int32), ("n", np.int32),
+                         ("avg", np.float64), ("std", np.float64)])
+PAIR_DTYPE = np.dtype([("paired", np.int32), ("z", np.int32, (2,)), ("mapq", np.int32, (2,)), ("proper", np.int32),
+                       ("score", np.int32), ("sub", np.int32), ("n_sub", np.int32), ("q_pe", np.int32)])
+assert PESTAT_DTYPE.itemsize == 32 and PAIR_DTYPE.itemsize == 40
+PE_MAX_INS = 1 << 16
 
 # include/bsw_mate.h
 KSW_XBYTE, KSW_XSTOP, KSW_XSUBO, KSW_XSTART = 0x10000, 0x20000, 0x40000, 0x80000
@@ -195,6 +205,15 @@ def hip_lib():
         L.bsw_regs_select_resident.argtypes = L.bsw_regs_select.argtypes + [P]
         L.bsw_sel_last_stats.argtypes = [P, P]
         for f in SEL_SYMBOLS[1:]:
+            getattr(L, f).restype = ctypes.c_int
+        L.bsw_pe_opt_default.argtypes = [P]
+        L.bsw_pe_opt_default.restype = None
+        L.bsw_pe_stat.argtypes = [P, P, P, P, P, ctypes.c_int32, P]
+        L.bsw_pe_stat_resident.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int32, P, P]
+        L.bsw_pe_pair.argtypes = [P, P, P, P, P, P, ctypes.c_int32, P]
+        L.bsw_pe_pair_resident.argtypes = [P, P, P, P, P, P, ctypes.c_int32, ctypes.c_int32, P, P]
+        L.bsw_pe_last_stats.argtypes = [P, P]
+        for f in PE_SYMBOLS[1:]:
             getattr(L, f).restype = ctypes.c_int
         L.bsw_get_scores_packed_device.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int, P, P]
         for f in ("bsw_create", "bsw_create_on", "bsw_get_scores", "bsw_get_scores_device", "bsw_last_stats",
@@ -807,6 +826,87 @@ def regs_select_resident(engine, d_reads: int, d_off: int, d_len: int, n_reads: 
 def sel_last_stats(engine) -> SelStats:
     st = SelStats()
     _check(hip_lib().bsw_sel_last_stats(engine._ctx, ctypes.byref(st)))
+    return st
+
+
+# ---------------------------------------------------------------- paired-end stage (bsw_pe.h)
+class PeOpt(ctypes.Structure):
+    """Mirror of bsw_pe_opt_t (include/bsw_pe.h)."""
+    _fields_ = [("l_pac", ctypes.c_int64), ("id0", ctypes.c_int64), ("max_ins", ctypes.c_int32),
+                ("min_seed_len", ctypes.c_int32), ("b", ctypes.c_int32), ("T", ctypes.c_int32),
+                ("pen_unpaired", ctypes.c_int32), ("mapQ_coef_len", ctypes.c_int32), ("mapQ_coef_fac", ctypes.c_int32),
+                ("mask_level", ctypes.c_float)]
+
+
+class PeStats(ctypes.Structure):
+    _fields_ = [("n_pairs", ctypes.c_int32), ("n_cand", ctypes.c_int32 * 4), ("n_pairing_tried", ctypes.c_int32),
+                ("n_paired", ctypes.c_int32), ("n_multi", ctypes.c_int32), ("n_unpaired_preferred", ctypes.c_int32),
+                ("n_proper", ctypes.c_int32), ("n_u", ctypes.c_int64), ("kernel_ms", ctypes.c_float),
+                ("reserved", ctypes.c_int32)]
+
+
+def pe_opt(**kw) -> PeOpt:
+    o = PeOpt()
+    hip_lib().bsw_pe_opt_default(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def _pe_host(sel_regs, sel_info, read_first):
+    sel_regs = np.ascontiguousarray(sel_regs, dtype=ALNREG_DTYPE)
+    sel_info = np.ascontiguousarray(sel_info, dtype=SELINFO_DTYPE)
+    read_first = np.ascontiguousarray(read_first, dtype=np.int32)
+    assert len(read_first) >= 1 and len(sel_regs) == len(sel_info)
+    return sel_regs, sel_info, read_first
+
+
+def pe_stat(engine, sel_regs, sel_info, read_first, opt: PeOpt) -> np.ndarray:
+    """bsw_pe_stat (host arrays as bsw_regs_select returns them) -> pes PESTAT_DTYPE [4]."""
+    sel_regs, sel_info, read_first = _pe_host(sel_regs, sel_info, read_first)
+    pes = np.zeros(4, dtype=PESTAT_DTYPE)
+    _check(hip_lib().bsw_pe_stat(engine._ctx, ctypes.byref(opt), _ptr(sel_regs), _ptr(sel_info), _ptr(read_first),
+                                 len(read_first) - 1, _ptr(pes)))
+    return pes
+
+
+def pe_stat_resident(engine, d_sel_regs: int, d_sel_info: int, d_read_first: int, n_reads: int, n_regs: int,
+                     opt: PeOpt, stream: int = 0) -> np.ndarray:
+    """bsw_pe_stat_resident: the arrays bsw_regs_select_resident left, as device pointers."""
+    V = ctypes.c_void_p
+    pes = np.zeros(4, dtype=PESTAT_DTYPE)
+    _check(hip_lib().bsw_pe_stat_resident(engine._ctx, ctypes.byref(opt), V(d_sel_regs or None), V(d_sel_info or None),
+                                          V(d_read_first), n_reads, n_regs, _ptr(pes), V(stream or None)))
+    return pes
+
+
+def pe_pair(engine, pes, sel_regs, sel_info, read_first, opt: PeOpt):
+    """bsw_pe_pair on copies of the host arrays -> (sel_regs, sel_info, pairs PAIR_DTYPE [n_reads / 2])."""
+    sel_regs, sel_info, read_first = _pe_host(sel_regs, sel_info, read_first)
+    sel_regs, sel_info = sel_regs.copy(), sel_info.copy()
+    pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+    assert len(pes) == 4
+    n_reads = len(read_first) - 1
+    pairs = np.zeros(max(n_reads // 2, 1), dtype=PAIR_DTYPE)
+    _check(hip_lib().bsw_pe_pair(engine._ctx, ctypes.byref(opt), _ptr(pes), _ptr(sel_regs), _ptr(sel_info),
+                                 _ptr(read_first), n_reads, _ptr(pairs)))
+    return sel_regs, sel_info, pairs[:n_reads // 2]
+
+
+def pe_pair_resident(engine, pes, d_sel_regs: int, d_sel_info: int, d_read_first: int, n_reads: int, n_regs: int,
+                     d_pairs: int, opt: PeOpt, stream: int = 0):
+    """bsw_pe_pair_resident: d_sel_regs / d_sel_info are updated in place, d_pairs written."""
+    V = ctypes.c_void_p
+    pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+    assert len(pes) == 4
+    _check(hip_lib().bsw_pe_pair_resident(engine._ctx, ctypes.byref(opt), _ptr(pes), V(d_sel_regs or None),
+                                          V(d_sel_info or None), V(d_read_first), n_reads, n_regs, V(d_pairs or None),
+                                          V(stream or None)))
+
+
+def pe_last_stats(engine) -> PeStats:
+    st = PeStats()
+    _check(hip_lib().bsw_pe_last_stats(engine._ctx, ctypes.byref(st)))
     return st
 
 
