@@ -23,6 +23,7 @@
 #include "../../include/bsw_aln.h"
 #include "../../include/bsw_sel.h"
 #include "../../include/bsw_pe.h"
+#include "../../include/bsw_matesw.h"
 #include "bsw_kernels.h"
 #include "bsw_internal.h"
 
@@ -136,6 +137,8 @@ struct AlnState;
 struct SelW;
 struct SelRd;
 struct PeV;
+struct MswSt;
+struct MswJob;
 // Everything one call needs on one device.  Members are destroyed in reverse order: buffers, then
 // events, then streams.
 struct BSW_HIDDEN Slot {
@@ -154,6 +157,7 @@ struct BSW_HIDDEN Slot {
     Event evm;                          // class-count readback of the last run_plan
     Event evh;                          // inputs ready on the call's stream (pstream waits)
     Event evd;                          // host pipeline: a chunk's DP done (its outputs' readback waits)
+    Event evw0, evw1;                   // mate-rescue stage: its helper kernels (the batched ksw_align2 times itself with ev0..ev3)
     // device buffers (grown on demand)
     DevBuf<SeqPair> d_pairs;
     DevBuf<uint8_t> d_ref, d_qer;
@@ -207,6 +211,13 @@ struct BSW_HIDDEN Slot {
     DevBuf<int32_t> d_pmeta;            // kPeMetaWords
     DevBuf<int32_t> d_plist;            // pairs of the general path, n_pairs
     DevBuf<PeV> d_pv;                   // mem_pair's v (flat, a pair's at its first region)
+    // mate-rescue stage (bsw_matesw.h); its work lists are d_swork, its jobs d_apairs / d_aq / d_at and
+    // d_maln, its scans use d_tmp, its host form stages in d_aio
+    DevBuf<int32_t> d_wint;             // ncand, capv, coff, woff, nlist (n_reads + 1 each), two pair lists
+    DevBuf<int64_t> d_wcand;            // the candidates' rb, copied before any rescue
+    DevBuf<MswSt> d_wst;                // per pair: cursor and pending call
+    DevBuf<MswJob> d_wjobs;             // a round's jobs, at most 4 per pair
+    DevBuf<int32_t> d_wmeta;            // kMswSlots x kMswMetaWords
     bool timed = false;
     hipStream_t run_stream = nullptr;   // stream of the last run_device (finish_stats waits on it)
     bsw_stats_t stats{};
@@ -374,6 +385,7 @@ struct bsw_ctx {
     bsw_aln_stats_t aln_last{};
     bsw_sel_stats_t sel_last{};
     bsw_pe_stats_t pe_last{};
+    bsw_matesw_stats_t matesw_last{};
     struct Pinned { std::mutex mu; bsw::PinnedBuf<uint8_t> b; } pin[2];
     int glob_band = 0;                  // BSW_OPT_GLOB_BAND
     int64_t ext_chunk = 0;              // BSW_OPT_EXT_CHUNK (0: the int32-offset bound)

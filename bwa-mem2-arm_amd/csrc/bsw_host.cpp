@@ -31,6 +31,7 @@
 #include "bsw_aln_k.h"
 #include "bsw_sel_k.h"
 #include "bsw_pe_k.h"
+#include "bsw_matesw_k.h"
 
 namespace bsw {
 
@@ -1841,6 +1842,272 @@ int bsw_pe_last_stats(bsw_ctx_t *ctx, bsw_pe_stats_t *out)
     if (!ctx || !out) return BSW_E_INVAL;
     std::lock_guard<std::mutex> g(ctx->stats_mu);
     *out = ctx->pe_last;
+    return BSW_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- mate rescue stage (bsw_matesw.h)
+namespace bsw {
+
+// argument checks of both forms, before anything touches a device
+static int matesw_check_args(const bsw_ctx_t *ctx, const bsw_matesw_opt_t *opt, const bsw_pestat_t *pes,
+                             int32_t n_reads, int32_t n_regs, int32_t out_cap)
+{
+    if (!opt || !pes || n_reads < 0 || (n_reads & 1) || n_regs < 0 || out_cap < 0) return BSW_E_INVAL;
+    if (opt->l_pac <= 0 || opt->max_matesw < 0 || opt->min_seed_len <= 0 || opt->max_chain_gap < 0) return BSW_E_INVAL;
+    for (int d = 0; d < 4; ++d)
+        if (!pes[d].failed && pes[d].low > pes[d].high) return BSW_E_INVAL;
+    if (!ctx) return BSW_E_INVAL;
+    return mate_params_ok(ctx->params) ? BSW_OK : BSW_E_INVAL;
+}
+
+struct MswIo {
+    const uint8_t *reads;
+    const int64_t *read_off;
+    const int32_t *read_len;
+    const bsw_alnreg_t *regs;
+    const bsw_selinfo_t *info;
+    const int32_t *first;
+    bsw_alnreg_t *out_regs;
+    int32_t *out_read;
+    bsw_selinfo_t *out_info;
+    int32_t *out_first;
+};
+
+// count + scans -> round 0's step -> per round: one readback of the job count, build, the batched
+// ksw_align2, the next step -> the scan of the list lengths -> emit.  The caller holds dc.refmu shared.
+static int matesw_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st, const bsw_matesw_opt_t &opt,
+                         const bsw_pestat_t *pes, const MswIo &io, int32_t n_reads, int32_t n_regs, int32_t out_cap,
+                         int32_t *n_out, bsw_matesw_stats_t &ws)
+{
+    *n_out = 0;
+    const bsw_params_t &pr = ctx->params;
+    MswParams p;
+    memset(&p, 0, sizeof(p));
+    p.s.a = pr.mat[0];
+    p.s.max_chain_gap = opt.max_chain_gap; p.s.min_seed_len = opt.min_seed_len; p.s.patch = 0;
+    p.s.mask_level_redun = opt.mask_level_redun;
+    p.s.l_pac = opt.l_pac; p.s.n_reads = n_reads;
+    p.n_pairs = n_reads / 2; p.n_regs = n_regs;
+    p.max_matesw = opt.max_matesw; p.pen_unpaired = opt.pen_unpaired;
+    for (int d = 0; d < 4; ++d) {
+        p.pes[d].low = pes[d].low; p.pes[d].high = pes[d].high; p.pes[d].failed = pes[d].failed != 0;
+    }
+    MateParams mp;
+    make_mate_params(pr, mp);
+    if ((int64_t)n_regs * 5 > INT32_MAX) return BSW_E_RANGE;        // the work lists' offsets are int32
+    const size_t nr = (size_t)n_reads, np = nr / 2, n1 = nr + 1;
+    size_t scan_bytes = 0;
+    BSW_TRY(launch_sel_scan(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
+    BSW_TRY(s.d_tmp.grow(std::max<size_t>(scan_bytes, 16)));
+    BSW_TRY(s.d_wint.grow(5 * n1 + 2 * np + 1));
+    BSW_TRY(s.d_wmeta.grow(kMswSlots * kMswMetaWords));
+    BSW_TRY(s.d_wst.grow(std::max<size_t>(np, 1)));
+    BSW_TRY(s.d_wjobs.grow(std::max<size_t>(4 * np, 1)));
+    BSW_TRY(s.d_maln.grow(std::max<size_t>(4 * np, 1)));
+    if (!s.evw0) BSW_TRY(hipEventCreate(&s.evw0.p));
+    if (!s.evw1) BSW_TRY(hipEventCreate(&s.evw1.p));
+    static_assert(kMswSlots * kMswMetaWords <= kMetaWords, "the slot's pinned mirror holds the stage's counters");
+    int32_t *ncand = s.d_wint, *capv = ncand + n1, *coff = capv + n1, *woff = coff + n1, *nlist = woff + n1;
+    int32_t *lists = nlist + n1;
+    int32_t *h_meta = s.h_meta;
+    constexpr size_t kMetaBytes = kMswSlots * kMswMetaWords * sizeof(int32_t);
+    float ms = 0.f;
+    BSW_TRY(hipMemsetAsync(s.d_wint, 0, (5 * n1) * sizeof(int32_t), st));
+    BSW_TRY(hipMemsetAsync(s.d_wmeta, 0, kMetaBytes, st));
+    BSW_TRY(hipEventRecord(s.evw0, st));
+    BSW_TRY(launch_msw_count(p, io.regs, io.first, ncand, capv, s.d_wmeta, st));
+    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, ncand, coff, n_reads, st));
+    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, capv, woff, n_reads, st));
+    BSW_TRY(hipEventRecord(s.evw1, st));
+    BSW_TRY(hipMemcpyAsync(h_meta, s.d_wmeta, kMswMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_meta + kMswMetaWords, coff + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_meta + kMswMetaWords + 1, woff + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(hipEventElapsedTime(&ms, s.evw0, s.evw1));
+    ws.helper_ms += ms;
+    if (h_meta[kMswErr]) return BSW_E_RANGE;
+    const size_t n_cand = (size_t)h_meta[kMswMetaWords], n_work = (size_t)h_meta[kMswMetaWords + 1];
+    BSW_TRY(s.d_wcand.grow(std::max<size_t>(n_cand, 1)));
+    BSW_TRY(s.d_swork.grow(std::max<size_t>(n_work, 1)));
+    int32_t n_items = p.n_pairs;
+    const int32_t *list = nullptr;
+    for (int round = 0;; ++round) {
+        int32_t *next = lists + (size_t)(round & 1) * np;
+        BSW_TRY(hipEventRecord(s.evw0, st));
+        BSW_TRY(launch_msw_step(p, list, n_items, io.regs, io.info, io.first, io.read_len, ncand, coff, woff, s.d_wcand,
+                                s.d_swork, nlist, s.d_wst, s.d_maln, s.d_wjobs, next, s.d_wmeta, st));
+        BSW_TRY(hipEventRecord(s.evw1, st));
+        BSW_TRY(hipMemcpyAsync(h_meta, s.d_wmeta, kMetaBytes, hipMemcpyDeviceToHost, st));
+        BSW_TRY(hipStreamSynchronize(st));
+        BSW_TRY(hipEventElapsedTime(&ms, s.evw0, s.evw1));
+        ws.helper_ms += ms;
+        if (h_meta[kMswErr]) return BSW_E_RANGE;
+        const int32_t nj = h_meta[kMswNJobs];
+        if (nj == 0) break;
+        ++ws.rounds;
+        n_items = h_meta[kMswNext];
+        list = next;
+        p.qstride = std::max(h_meta[kMswMaxQ], 1);
+        p.tstride = std::max(h_meta[kMswMaxT], 1);
+        // SeqPair idr / idq are int32: chunk so j * stride stays below 2^31
+        const int32_t chunk = (int32_t)std::min<int64_t>(nj, (int64_t)INT32_MAX / std::max(p.tstride, p.qstride) - 1);
+        BSW_TRY(s.d_apairs.grow((size_t)chunk));
+        BSW_TRY(s.d_aq.grow((size_t)chunk * p.qstride));
+        BSW_TRY(s.d_at.grow((size_t)chunk * p.tstride));
+        BSW_TRY(hipMemsetAsync(s.d_wmeta + kMswNext, 0, 4 * sizeof(int32_t), st));      // the round's words
+        for (int32_t a = 0; a < nj; a += chunk) {
+            const int32_t b = std::min(nj, a + chunk);
+            BSW_TRY(hipEventRecord(s.evw0, st));
+            BSW_TRY(launch_msw_build(p, s.d_wjobs + a, b - a, io.reads, io.read_off, io.read_len, dc.d_refres, s.d_apairs,
+                                     s.d_aq, s.d_at, st));
+            BSW_TRY(hipEventRecord(s.evw1, st));
+            bsw_mate_stats_t mst;
+            if (int r = mate_device(mp, s, s.d_apairs, s.d_at, s.d_aq, b - a, s.d_maln + a, st, &mst)) return r;
+            ws.sw_ms += mst.fwd_ms + mst.rev_ms;
+            BSW_TRY(hipEventElapsedTime(&ms, s.evw0, s.evw1));
+            ws.helper_ms += ms;
+        }
+    }
+    for (int k = 0; k < kMswSlots; ++k) {
+        const int32_t *m = h_meta + k * kMswMetaWords;
+        ws.n_calls += m[kMswCalls];
+        ws.n_calls_all_skipped += m[kMswAllSkipped];
+        ws.n_jobs += m[kMswJobs];
+        ws.n_jobs_u8 += m[kMswJobsU8];
+        ws.n_short_window += m[kMswShort];
+        ws.n_pushed += m[kMswPushed];
+        ws.n_redundant += m[kMswRedundant];
+        ws.n_identical += m[kMswIdentical];
+        ws.n_lists_changed += m[kMswChanged];
+    }
+    BSW_TRY(hipEventRecord(s.evw0, st));
+    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, nlist, io.out_first, n_reads, st));
+    BSW_TRY(hipMemcpyAsync(h_meta, io.out_first + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    *n_out = ws.n_out = h_meta[0];
+    if (h_meta[0] > out_cap) return BSW_E_RANGE;
+    BSW_TRY(launch_msw_emit(p, woff, nlist, io.out_first, s.d_swork, io.out_regs, io.out_read, io.out_info, st));
+    BSW_TRY(hipEventRecord(s.evw1, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(hipEventElapsedTime(&ms, s.evw0, s.evw1));
+    ws.helper_ms += ms;
+    return BSW_OK;
+}
+
+static void set_matesw_stats(bsw_ctx_t *ctx, const bsw_matesw_stats_t &ws)
+{
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    ctx->matesw_last = ws;
+}
+
+}  // namespace bsw
+
+extern "C" {
+
+void bsw_matesw_opt_default(bsw_matesw_opt_t *opt)
+{
+    if (!opt) return;
+    memset(opt, 0, sizeof(*opt));
+    opt->max_matesw = 50;
+    opt->pen_unpaired = 17;
+    opt->min_seed_len = 19;
+    opt->max_chain_gap = 10000;
+    opt->mask_level_redun = 0.95f;
+}
+
+int bsw_matesw_resident(bsw_ctx_t *ctx, const bsw_matesw_opt_t *opt, const bsw_pestat_t *pes,
+                        const uint8_t *d_reads, const int64_t *d_read_off, const int32_t *d_read_len,
+                        int32_t n_reads, const bsw_alnreg_t *d_sel_regs, const bsw_selinfo_t *d_sel_info,
+                        const int32_t *d_read_first, int32_t n_regs, bsw_alnreg_t *d_out_regs,
+                        int32_t *d_out_read, bsw_selinfo_t *d_out_info, int32_t *d_out_first, int32_t out_cap,
+                        int32_t *n_out, void *stream)
+{
+    if (const int rc = bsw::matesw_check_args(ctx, opt, pes, n_reads, n_regs, out_cap)) return rc;
+    if (!n_out || !d_read_first || !d_out_first || (n_reads > 0 && (!d_reads || !d_read_off || !d_read_len)) ||
+        (n_regs > 0 && (!d_sel_regs || !d_sel_info)) || (out_cap > 0 && (!d_out_regs || !d_out_read || !d_out_info)))
+        return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the resident reference stays put
+    if (!dc.d_refres || dc.refres_len != 2 * opt->l_pac) return BSW_E_INVAL;
+    bsw_matesw_stats_t ws{};
+    ws.n_pairs = n_reads / 2;
+    const bsw::MswIo io = {d_reads, d_read_off, d_read_len, d_sel_regs, d_sel_info, d_read_first,
+                           d_out_regs, d_out_read, d_out_info, d_out_first};
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::matesw_device(ctx, dc, s, st, *opt, pes, io, n_reads, n_regs, out_cap, n_out, ws);
+    });
+    if (rc) return rc;
+    bsw::set_matesw_stats(ctx, ws);
+    return BSW_OK;
+}
+
+int bsw_matesw(bsw_ctx_t *ctx, const bsw_matesw_opt_t *opt, const bsw_pestat_t *pes, const uint8_t *reads,
+               const int64_t *read_off, const int32_t *read_len, int32_t n_reads, const bsw_alnreg_t *sel_regs,
+               const bsw_selinfo_t *sel_info, const int32_t *read_first, bsw_alnreg_t *out_regs,
+               int32_t *out_read, bsw_selinfo_t *out_info, int32_t *out_first, int32_t out_cap, int32_t *n_out)
+{
+    if (const int rc = bsw::matesw_check_args(ctx, opt, pes, n_reads, 0, out_cap)) return rc;
+    if (!n_out || !out_first || (n_reads > 0 && (!reads || !read_off || !read_len)) ||
+        (out_cap > 0 && (!out_regs || !out_read || !out_info)))
+        return BSW_E_INVAL;
+    int32_t n_regs = 0;
+    if (const int rc = bsw::pe_host_first(read_first, n_reads, n_regs)) return rc;
+    if (n_regs > 0 && (!sel_regs || !sel_info)) return BSW_E_INVAL;
+    int64_t rbytes = 0;
+    for (int32_t i = 0; i < n_reads; ++i) {
+        if (read_off[i] < 0 || read_len[i] < 0) return BSW_E_RANGE;
+        rbytes = std::max<int64_t>(rbytes, read_off[i] + read_len[i]);
+    }
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (!dc.d_refres || dc.refres_len != 2 * opt->l_pac) return BSW_E_INVAL;
+    bsw_matesw_stats_t ws{};
+    ws.n_pairs = n_reads / 2;
+    // one staged blob: inputs, then outputs, each part 16-B aligned
+    const size_t nr = (size_t)n_reads, ng = (size_t)n_regs, nc = (size_t)out_cap;
+    constexpr int kIn = 6, kAll = 10;
+    const size_t part[kAll] = {(size_t)rbytes, nr * sizeof(int64_t), nr * sizeof(int32_t), ng * sizeof(bsw_alnreg_t),
+                               ng * sizeof(bsw_selinfo_t), (nr + 1) * sizeof(int32_t), nc * sizeof(bsw_alnreg_t),
+                               nc * sizeof(int32_t), nc * sizeof(bsw_selinfo_t), (nr + 1) * sizeof(int32_t)};
+    size_t off[kAll + 1] = {0};
+    for (int k = 0; k < kAll; ++k) off[k + 1] = off[k] + ((part[k] + 15) & ~(size_t)15);
+    const void *src[kIn] = {reads, read_off, read_len, sel_regs, sel_info, read_first};
+    void *dst[4] = {out_regs, out_read, out_info, out_first};
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(s.d_aio.grow(off[kAll] + 16));
+        uint8_t *b = s.d_aio;
+        for (int k = 0; k < kIn; ++k)
+            if (part[k]) BSW_TRY(hipMemcpyAsync(b + off[k], src[k], part[k], hipMemcpyHostToDevice, s.stream));
+        const bsw::MswIo io = {b + off[0], (const int64_t *)(b + off[1]), (const int32_t *)(b + off[2]),
+                               (const bsw_alnreg_t *)(b + off[3]), (const bsw_selinfo_t *)(b + off[4]),
+                               (const int32_t *)(b + off[5]), (bsw_alnreg_t *)(b + off[6]), (int32_t *)(b + off[7]),
+                               (bsw_selinfo_t *)(b + off[8]), (int32_t *)(b + off[9])};
+        const int r = bsw::matesw_device(ctx, dc, s, s.stream, *opt, pes, io, n_reads, n_regs, out_cap, n_out, ws);
+        if (r == BSW_E_RANGE && *n_out > out_cap) {        // (d_out_first is still written)
+            BSW_TRY(hipMemcpyAsync(out_first, b + off[9], part[9], hipMemcpyDeviceToHost, s.stream));
+            BSW_TRY(hipStreamSynchronize(s.stream));
+        }
+        if (r) return r;
+        const size_t k = (size_t)*n_out;
+        const size_t got[4] = {k * sizeof(bsw_alnreg_t), k * sizeof(int32_t), k * sizeof(bsw_selinfo_t), part[9]};
+        for (int o = 0; o < 4; ++o)
+            if (got[o]) BSW_TRY(hipMemcpyAsync(dst[o], b + off[6 + o], got[o], hipMemcpyDeviceToHost, s.stream));
+        BSW_TRY(hipStreamSynchronize(s.stream));
+        return BSW_OK;
+    });
+    if (rc) return rc;
+    bsw::set_matesw_stats(ctx, ws);
+    return BSW_OK;
+}
+
+int bsw_matesw_last_stats(bsw_ctx_t *ctx, bsw_matesw_stats_t *out)
+{
+    if (!ctx || !out) return BSW_E_INVAL;
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    *out = ctx->matesw_last;
     return BSW_OK;
 }
 

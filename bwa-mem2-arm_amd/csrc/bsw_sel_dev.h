@@ -1,7 +1,8 @@
-// bsw_sel_dev.h -- device code shared by region selection (bsw_sel.hip) and the paired-end stage
-// (bsw_pe.hip): a region's moves as 16-byte words, klib's ks_introsort with its explicit stack in
-// LDS, bwa's hash_64, primary marking and MAPQ as include/bsw_sel.h states them.  Plain C++ with
-// vector stores only; no private arrays.
+// bsw_sel_dev.h -- device code shared by region selection (bsw_sel.hip), the paired-end stage
+// (bsw_pe.hip) and mate rescue (bsw_matesw.hip): a region's moves as 16-byte words, klib's
+// ks_introsort with its explicit stack in LDS, bwa's hash_64, primary marking and MAPQ, the dedup
+// loop and its drops and sorts as include/bsw_sel.h states them.  Plain C++ with vector stores only;
+// no private arrays.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -225,6 +226,128 @@ __device__ __forceinline__ void sel_mark_mapq(const SelParams &p, int r, SelW *W
         }
     }
     for (int k = 0; k < n; ++k) W[k].mapq = sel_mapq(p, W[k], frac_rep);
+}
+
+// The i / j loop of read r from (i, j); have: score answers the patch_reg it was suspended at (a
+// global score may be negative, so the score itself cannot say so).  Returns true when it
+// suspends again (st[r] holds where; lq / rl its job's spans).
+__device__ __forceinline__ bool sel_dedup(const SelParams &p, int r, SelW *W, int n, int i, int j, int w, bool have,
+                                          int score,
+                          const uint8_t *__restrict__ q_codes, const uint8_t *__restrict__ ref, const int8_t *s_mat,
+                          SelRd *st, int32_t *meta, int &lq_out, int &rl_out)
+{
+    for (; i < n; ++i, j = -2) {
+        if (j == -2) {
+            if (W[i].r.rb >= W[i - 1].r.re + p.max_chain_gap) continue;
+            j = i - 1;
+        }
+        for (; j >= 0 && W[i].r.rb < W[j].r.re + p.max_chain_gap; --j) {
+            const bsw_alnreg_t P = W[i].r, Q = W[j].r;
+            if (!have) {
+                if (Q.qe == Q.qb) continue;
+                const int64_t orr = Q.re - P.rb;
+                const int oq = Q.qb < P.qb ? Q.qe - P.qb : P.qe - Q.qb;
+                const int64_t mr = min(Q.re - Q.rb, P.re - P.rb);
+                const int mq = min(Q.qe - Q.qb, P.qe - P.qb);
+                if ((float)orr > p.mask_level_redun * (float)mr && (float)oq > p.mask_level_redun * (float)mq) {
+                    atomicAdd(&meta[kSelRedundant], 1);
+                    if (P.score < Q.score) {
+                        W[i].r.qe = P.qb;
+                        break;
+                    }
+                    W[j].r.qe = Q.qb;
+                    continue;
+                }
+                if (!(Q.rb < P.rb)) continue;
+                // patch_reg(a = Q, b = P)
+                if (p.patch == 0) continue;
+                if (Q.rb < p.l_pac && P.rb >= p.l_pac) continue;
+                if (Q.qb >= P.qb || Q.qe >= P.qe || Q.re >= P.re) continue;
+                int64_t w64 = (Q.re - P.rb) - (int64_t)(Q.qe - P.qb);
+                w64 = w64 > 0 ? w64 : -w64;
+                const double rr = fabs((double)(Q.re - P.rb) / (double)(P.re - Q.rb) -
+                                       (double)(Q.qe - P.qb) / (double)(P.qe - Q.qb));
+                if (Q.re < P.rb || Q.qe < P.qb) {
+                    if (w64 > (int64_t)(p.W << 1) || rr >= 0.05) continue;
+                } else {
+                    if (w64 > (int64_t)(p.W << 2) || rr >= 0.10) continue;
+                }
+                w = (int)min(w64 + Q.w + P.w, (int64_t)(p.W << 2));
+                atomicAdd(&meta[kSelTried], 1);
+                const int64_t lq = (int64_t)P.qe - Q.qb, rl = P.re - Q.rb;
+                if (lq > BSW_MAX_LEN || rl > BSW_MAX_LEN) {
+                    atomicOr(&meta[kSelErr], 1);
+                    continue;
+                }
+                if (lq <= 0 || rl <= 0 || (p.l_pac > 0 && Q.rb < p.l_pac && P.re > p.l_pac)) {
+                    score = 0;                              // gen_cigar2 rejects the span
+                } else if (lq == rl && w == 0) {
+                    score = 0;                              // gen_cigar2's gap-free shortcut
+                    for (int c = 0; c < (int)lq; ++c)
+                        score += s_mat[min((int)ref[Q.rb + c], 4) * 5 + min((int)q_codes[Q.qb + c], 4)];
+                } else {
+                    SelRd s;
+                    s.n = n; s.i = i; s.j = j; s.w = w;
+                    st[r] = s;
+                    lq_out = (int)lq; rl_out = (int)rl;
+                    return true;
+                }
+            }
+            // the rest of patch_reg, then its caller
+            const int sum = P.score + Q.score;
+            const int q_s = (int)((double)(P.qe - Q.qb) / ((P.qe - P.qb) + (Q.qe - Q.qb)) * sum + .499);
+            const int r_s = (int)((double)(P.re - Q.rb) / (double)((P.re - P.rb) + (Q.re - Q.rb)) * sum + .499);
+            const int sc = score;
+            have = false;
+            if ((double)sc / max(q_s, r_s) < 0.90) {
+                atomicAdd(&meta[kSelRatio], 1);
+                continue;
+            }
+            if (sc <= 0) continue;
+            atomicAdd(&meta[kSelOk], 1);
+            const int ync = W[j].n_comp, ycov = W[j].seedcov, ysub = W[j].sub, ycsub = W[j].csub;
+            W[i].n_comp += ync + 1;
+            W[i].seedcov = max(W[i].seedcov, ycov);
+            W[i].sub = max(W[i].sub, ysub);
+            W[i].csub = max(W[i].csub, ycsub);
+            W[i].r.qb = Q.qb; W[i].r.rb = Q.rb;
+            W[i].r.truesc = W[i].r.score = sc;
+            W[i].r.w = w;
+            W[j].r.qb = Q.qe;
+        }
+    }
+    return false;
+}
+
+// Steps 4..7 of DEDUP AND PATCH on a list whose i / j loop has ended: the drops, the score sort, the
+// identical-hit rule; returns the number kept.
+__device__ __forceinline__ int sel_dedup_drop(SelW *W, int n, int *stk, int32_t *meta)
+{
+    int m = 0;
+    for (int k = 0; k < n; ++k)
+        if (W[k].r.qe > W[k].r.qb) {
+            if (m != k) sel_copy(W + m, W + k);
+            ++m;
+        }
+    n = m;
+    sel_introsort(n, W, stk, LtScorePos());
+    int ident = 0;
+    for (int k = 1; k < n; ++k)
+        if (W[k].r.score == W[k - 1].r.score && W[k].r.rb == W[k - 1].r.rb && W[k].r.qb == W[k - 1].r.qb) {
+            W[k].r.qe = W[k].r.qb;
+            ++ident;
+        }
+    if (ident) {
+        atomicAdd(&meta[kSelIdentical], ident);
+        m = 1;
+        for (int k = 1; k < n; ++k)
+            if (W[k].r.qe > W[k].r.qb) {
+                if (m != k) sel_copy(W + m, W + k);
+                ++m;
+            }
+        n = m;
+    }
+    return n;
 }
 
 }  // namespace bsw

@@ -46,6 +46,8 @@ SEL_SYMBOLS = ("bsw_sel_opt_default", "bsw_regs_select", "bsw_regs_select_reside
 # include/bsw_pe.h (additive in the same way)
 PE_SYMBOLS = ("bsw_pe_opt_default", "bsw_pe_stat", "bsw_pe_stat_resident", "bsw_pe_pair", "bsw_pe_pair_resident",
               "bsw_pe_last_stats")
+# include/bsw_matesw.h (additive to ABI 8: BSW_MATESW_API)
+MATESW_SYMBOLS = ("bsw_matesw_opt_default", "bsw_matesw", "bsw_matesw_resident", "bsw_matesw_last_stats")
 
 # include/bsw.h engine options (bsw_set_option)
 OPT_KERNEL8, OPT_FORK, OPT_SORTKEY, OPT_GLOB_BAND, OPT_EXT_CHUNK, OPT_HOST_CHUNK, OPT_LONG, OPT_HOST_PACK = 1, 2, 3, 4, 5, 6, 7, 8
@@ -214,6 +216,14 @@ def hip_lib():
         L.bsw_pe_pair_resident.argtypes = [P, P, P, P, P, P, ctypes.c_int32, ctypes.c_int32, P, P]
         L.bsw_pe_last_stats.argtypes = [P, P]
         for f in PE_SYMBOLS[1:]:
+            getattr(L, f).restype = ctypes.c_int
+        L.bsw_matesw_opt_default.argtypes = [P]
+        L.bsw_matesw_opt_default.restype = None
+        L.bsw_matesw.argtypes = [P, P, P, P, P, P, ctypes.c_int32, P, P, P, P, P, P, P, ctypes.c_int32, P]
+        L.bsw_matesw_resident.argtypes = [P, P, P, P, P, P, ctypes.c_int32, P, P, P, ctypes.c_int32, P, P, P, P,
+                                          ctypes.c_int32, P, P]
+        L.bsw_matesw_last_stats.argtypes = [P, P]
+        for f in MATESW_SYMBOLS[1:]:
             getattr(L, f).restype = ctypes.c_int
         L.bsw_get_scores_packed_device.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int, P, P]
         for f in ("bsw_create", "bsw_create_on", "bsw_get_scores", "bsw_get_scores_device", "bsw_last_stats",
@@ -907,6 +917,95 @@ def pe_pair_resident(engine, pes, d_sel_regs: int, d_sel_info: int, d_read_first
 def pe_last_stats(engine) -> PeStats:
     st = PeStats()
     _check(hip_lib().bsw_pe_last_stats(engine._ctx, ctypes.byref(st)))
+    return st
+
+
+# ---------------------------------------------------------------- mate rescue stage (bsw_matesw.h)
+class MateswOpt(ctypes.Structure):
+    """Mirror of bsw_matesw_opt_t (include/bsw_matesw.h)."""
+    _fields_ = [("l_pac", ctypes.c_int64), ("max_matesw", ctypes.c_int32), ("pen_unpaired", ctypes.c_int32),
+                ("min_seed_len", ctypes.c_int32), ("max_chain_gap", ctypes.c_int32),
+                ("mask_level_redun", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+class MateswStats(ctypes.Structure):
+    _fields_ = [("n_pairs", ctypes.c_int32), ("n_calls", ctypes.c_int32), ("n_calls_all_skipped", ctypes.c_int32),
+                ("n_jobs", ctypes.c_int32), ("n_jobs_u8", ctypes.c_int32), ("n_short_window", ctypes.c_int32),
+                ("n_pushed", ctypes.c_int32), ("n_redundant", ctypes.c_int32), ("n_identical", ctypes.c_int32),
+                ("n_lists_changed", ctypes.c_int32), ("rounds", ctypes.c_int32), ("n_out", ctypes.c_int32),
+                ("sw_ms", ctypes.c_float), ("helper_ms", ctypes.c_float)]
+
+
+def matesw_opt(**kw) -> MateswOpt:
+    o = MateswOpt()
+    hip_lib().bsw_matesw_opt_default(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def _raise_needed(rc, n_out):
+    try:
+        _check(rc)
+    except BswError as e:
+        e.needed = n_out.value
+        raise
+
+
+def matesw(engine, pes, reads, read_off, read_len, sel_regs, sel_info, read_first, opt: MateswOpt,
+           out_cap: int | None = None):
+    """bsw_matesw (host arrays, resident reference required): the lists bsw_regs_select left and the
+    pes of bsw_pe_stat -> (regs ALNREG_DTYPE, reg_read int32, info SELINFO_DTYPE, first int32
+    [n_reads + 1]) for bsw_pe_pair / bsw_reg2aln.  An out_cap below the number needed raises BswError
+    with .needed set (and .first, the offsets, which are still written)."""
+    sel_regs, sel_info, read_first = _pe_host(sel_regs, sel_info, read_first)
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+    read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+    pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+    n_reads = len(read_first) - 1
+    assert len(pes) == 4 and len(read_off) == len(read_len) == n_reads
+    cap = len(sel_regs) + 4 * opt.max_matesw * n_reads if out_cap is None else out_cap
+    regs = np.zeros(max(cap, 1), dtype=ALNREG_DTYPE)
+    rd = np.zeros(max(cap, 1), dtype=np.int32)
+    info = np.zeros(max(cap, 1), dtype=SELINFO_DTYPE)
+    first = np.zeros(n_reads + 1, dtype=np.int32)
+    n_out = ctypes.c_int32(-1)
+    rc = hip_lib().bsw_matesw(engine._ctx, ctypes.byref(opt), _ptr(pes), _ptr(reads), _ptr(read_off), _ptr(read_len),
+                              n_reads, _ptr(sel_regs), _ptr(sel_info), _ptr(read_first), _ptr(regs), _ptr(rd),
+                              _ptr(info), _ptr(first), cap, ctypes.byref(n_out))
+    if rc != 0:
+        try:
+            _raise_needed(rc, n_out)
+        except BswError as e:
+            e.first = first
+            raise
+    k = n_out.value
+    return regs[:k], rd[:k], info[:k], first
+
+
+def matesw_resident(engine, pes, d_reads: int, d_off: int, d_len: int, n_reads: int, d_sel_regs: int, d_sel_info: int,
+                    d_read_first: int, n_regs: int, d_out_regs: int, d_out_read: int, d_out_info: int,
+                    d_out_first: int, out_cap: int, opt: MateswOpt, stream: int = 0) -> int:
+    """bsw_matesw_resident: every array a device pointer (the inputs as bsw_regs_select_resident took
+    and left them; the outputs feed bsw_pe_pair_resident and bsw_reg2aln_resident).  Returns n_out."""
+    V = ctypes.c_void_p
+    pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+    assert len(pes) == 4
+    n_out = ctypes.c_int32(-1)
+    rc = hip_lib().bsw_matesw_resident(engine._ctx, ctypes.byref(opt), _ptr(pes), V(d_reads or None), V(d_off or None),
+                                       V(d_len or None), n_reads, V(d_sel_regs or None), V(d_sel_info or None),
+                                       V(d_read_first), n_regs, V(d_out_regs or None), V(d_out_read or None),
+                                       V(d_out_info or None), V(d_out_first), out_cap, ctypes.byref(n_out),
+                                       V(stream or None))
+    if rc != 0:
+        _raise_needed(rc, n_out)
+    return n_out.value
+
+
+def matesw_last_stats(engine) -> MateswStats:
+    st = MateswStats()
+    _check(hip_lib().bsw_matesw_last_stats(engine._ctx, ctypes.byref(st)))
     return st
 
 

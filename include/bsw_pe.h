@@ -7,8 +7,8 @@
  * float option times an integer in single precision.  Reads 2p and 2p + 1 are the two ends of
  * pair p; "list" = a read's regions as bsw_regs_select* left them (bsw_sel.h), a[0] its first.
  * One reference sequence (rid = 0, no ALT: n_pri = n).  a = mat[0] and the gap penalties come from
- * the context, as in bsw_sel.h.  Mate rescue (mem_matesw) is NOT built: it will consume pes[] and
- * slot between the two calls below without changing them.
+ * the context, as in bsw_sel.h.  Mate rescue (mem_matesw) is bsw_matesw.h's: it consumes pes[] and
+ * slots between the two calls below without changing them.
  *
  * infer_dir(b1, b2) -> (dir, dist):  r1 = b1 >= l_pac;  r2 = b2 >= l_pac
  *   p2 = r1 == r2 ? b2 : 2 * l_pac - 1 - b2;  dist = |p2 - b1|
