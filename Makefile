@@ -20,7 +20,7 @@ HIP_HDRS := $(CSRC)/bsw_devcache.h $(CSRC)/bsw_pool.h $(CSRC)/bsw_kernels.h $(CS
 
 # the product's objects; the experiment libraries below are this list with one object swapped
 OBJS := $(addprefix $(LIBDIR)/,bsw_kernels.o bsw_pc.o bsw_wv.o bsw_gq.o bsw_mate.o bsw_global.o bsw_ext_dev.o bsw_aln.o bsw_sel.o bsw_pe.o bsw_matesw.o \
-          bsw_fmi.o bsw_fmi_build.o bsw_memchain.o bsw_chain.o bsw_dispatch.o bsw_pipeline.o bsw_host.o bsw_ext.o \
+          bsw_fmi.o bsw_fmi_build.o bsw_memchain.o bsw_chain.o bsw_dispatch.o bsw_pipeline.o bsw_host.o bsw_stages.o bsw_ext.o \
           bsw_pack.o bsw_devcache.o bsw_batch.o)
 LINK  = $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(1) -lpthread
 
@@ -41,10 +41,11 @@ $(LIBDIR):
 $(LIBDIR)/%.o: $(CSRC)/%.hip $(HIP_HDRS) | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# hipcc-compiled .cpp (bsw_host.cpp as HIP; bsw_ext.cpp and bsw_pack.cpp have g++ rules of their own below)
+# hipcc-compiled .cpp (bsw_host.cpp and bsw_stages.cpp as HIP; bsw_ext.cpp and bsw_pack.cpp have g++
+# rules of their own below)
 $(LIBDIR)/%.o: $(CSRC)/%.cpp $(HIP_HDRS) | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) $(XHIP) -c $< -o $@
-$(LIBDIR)/bsw_host.o: XHIP := -x hip
+$(LIBDIR)/bsw_host.o $(LIBDIR)/bsw_stages.o: XHIP := -x hip
 
 $(LIBDIR)/bsw_ext.o: $(CSRC)/bsw_ext.cpp $(HIP_HDRS) | $(LIBDIR)
 	g++ -O3 -std=c++17 -fPIC -Wall -Iinclude -c $< -o $@

@@ -3,7 +3,9 @@
 // engine's translation units:
 //   bsw_dispatch.hip : plan_kernel, run_plan / run_dp / run_device, finish_stats
 //   bsw_pipeline.hip : staging kernels, the chunked host pipeline (host_shard), cross-call coalescing
-//   bsw_host.cpp     : contexts, recovery, mate / global / extension wrappers, options, the C ABI
+//   bsw_host.cpp     : contexts, recovery, mate / global / extension wrappers, options, the core C ABI
+//   bsw_stages.cpp   : the stages behind the extension (final alignments, region selection, the
+//                      paired-end stage, mate rescue), both forms of each, on shared call helpers
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -369,6 +371,17 @@ BSW_HIDDEN int host_shard(const KParams &kp, DeviceCtx &dc, SeqPair *pairs, cons
 BSW_HIDDEN int coalesced_call(const KParams &kp, DeviceCtx &dc, SeqPair *pairs, const uint8_t *ref,
                               const uint8_t *qer, int32_t n, int32_t w, int cell_bits, int32_t chunk, bool two_bit,
                               bsw_stats_t *st);
+// ---- bsw_host.cpp
+struct MateParams;
+struct GlobParams;
+BSW_HIDDEN void make_mate_params(const bsw_params_t &p, MateParams &mp);
+BSW_HIDDEN bool mate_params_ok(const bsw_params_t &p);
+BSW_HIDDEN int mate_device(const MateParams &mp, Slot &s, const SeqPair *d_pairs, const uint8_t *d_ref,
+                           const uint8_t *d_qer, int32_t n, bsw_kswr_t *d_aln, hipStream_t st, bsw_mate_stats_t *stats);
+BSW_HIDDEN void make_glob_params(const bsw_params_t &p, int prefer_band, GlobParams &gp);
+BSW_HIDDEN int glob_device(const GlobParams &gp, Slot &s, SeqPair *d_pairs, const uint8_t *d_ref, const uint8_t *d_qer,
+                           int32_t n, uint32_t *d_cigar, int32_t stride, int32_t *d_ncig, hipStream_t st,
+                           bsw_global_stats_t *stats);
 
 }  // namespace bsw
 
@@ -397,3 +410,21 @@ struct bsw_ctx {
     int32_t coalesce = 8192;            // BSW_OPT_COALESCE: calls of <= this many pairs coalesce
     std::atomic<unsigned> rr{0};        // tie-break rotation of the one-device pick
 };
+
+namespace bsw {
+// a call's stats into / out of the context's x_last member (every bsw_*_last_stats and its setter)
+template <class T>
+static inline void put_stats(bsw_ctx *ctx, T bsw_ctx::*last, const T &v)
+{
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    ctx->*last = v;
+}
+template <class T>
+static inline int get_stats(bsw_ctx *ctx, T bsw_ctx::*last, T *out)
+{
+    if (!ctx || !out) return BSW_E_INVAL;
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    *out = ctx->*last;
+    return BSW_OK;
+}
+}  // namespace bsw

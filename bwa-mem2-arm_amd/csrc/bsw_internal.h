@@ -49,4 +49,15 @@ void pack_2bit(uint8_t *dst, const uint8_t *src, size_t nbytes, uint32_t pos0, s
 void fast_keys(const SeqPair *pairs, int32_t n, const uint8_t *ref, const uint8_t *qer, uint32_t *keys);
 // kv[i] = (the bits of keys[i] selected by `vary`, compacted: pext) << 32 | i, for i in [a0, a1)
 void compact_keys(const uint32_t *keys, int32_t a0, int32_t a1, uint32_t vary, uint64_t *kv);
+// Layout of a staged blob (the host-array forms of the stages, bsw_stages.cpp): parts end to end
+// in the order added, each starting on a 16-byte boundary; a part of 0 bytes takes no room
+struct BlobLayout {
+    size_t total = 0;                   // bytes laid out so far = the next part's offset
+    size_t add(size_t bytes)            // -> the part's offset
+    {
+        const size_t at = total;
+        total += (bytes + 15) & ~(size_t)15;
+        return at;
+    }
+};
 }  // namespace bsw

@@ -1,0 +1,1094 @@
+// bsw_stages.cpp -- the stages behind the extension, each in a device-resident form and a
+// host-array form behind the C ABI: final alignments (bsw_aln.h), region selection (bsw_sel.h),
+// the paired-end stage (bsw_pe.h) and mate rescue (bsw_matesw.h).  Their kernels are in
+// bsw_aln.hip, bsw_sel.hip, bsw_pe.hip and bsw_matesw.hip; what the calls share is below.
+// (Layout of the engine: bsw_engine.h.)
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <shared_mutex>
+#include <vector>
+#include "bsw_engine.h"
+#include "bsw_mate_k.h"
+#include "bsw_global_k.h"
+#include "bsw_aln_k.h"
+#include "bsw_sel_k.h"
+#include "bsw_pe_k.h"
+#include "bsw_matesw_k.h"
+
+// ---------------------------------------------------------------- shared by the stages
+namespace bsw {
+
+// A host-array call's arrays staged through ONE device blob (the slot's d_aio, BlobLayout).  The
+// call declares each array once, before it has a slot -- in: copied in, out: copied back, inout:
+// both; n elements each -- and gets a Part that converts to the array's device pointer once grow()
+// has run.  An _opt array whose host pointer is null takes no room and converts to nullptr.
+// Copies run on the slot's stream in the order of declaration and skip empty parts; the call
+// site waits for the stream after its last back().
+struct BSW_HIDDEN StagedIo {
+    template <class T>
+    struct Part {
+        const StagedIo *io;
+        int k;                          // index into recs, -1: an absent optional array
+        operator T *() const { return k < 0 ? nullptr : (T *)(io->base + io->recs[k].at); }
+    };
+    struct Rec { void *host; size_t bytes, at; bool in; };
+    std::vector<Rec> recs;
+    BlobLayout lay;
+    uint8_t *base = nullptr;
+    hipStream_t st = nullptr;
+
+    template <class T>
+    Part<T> add(T *host, size_t n, bool in, bool optional = false)
+    {
+        if (optional && !host) return {this, -1};
+        recs.push_back({(void *)host, n * sizeof(T), lay.add(n * sizeof(T)), in});
+        return {this, (int)recs.size() - 1};
+    }
+    template <class T> Part<const T> in(const T *host, size_t n) { return add(host, n, true); }
+    template <class T> Part<const T> in_opt(const T *host, size_t n) { return add(host, n, true, true); }
+    template <class T> Part<T> inout(T *host, size_t n) { return add(host, n, true); }
+    template <class T> Part<T> out(T *host, size_t n) { return add(host, n, false); }
+    template <class T> Part<T> out_opt(T *host, size_t n) { return add(host, n, false, true); }
+
+    hipError_t grow(Slot &s)            // the slot's first growth in every host form
+    {
+        const hipError_t e = s.d_aio.grow(lay.total + 16);
+        base = s.d_aio;
+        st = s.stream;
+        return e;
+    }
+    hipError_t upload() const
+    {
+        for (const Rec &r : recs)
+            if (r.in && r.bytes)
+                if (hipError_t e = hipMemcpyAsync(base + r.at, r.host, r.bytes, hipMemcpyHostToDevice, st)) return e;
+        return hipSuccess;
+    }
+    hipError_t stage(Slot &s) { const hipError_t e = grow(s); return e ? e : upload(); }
+    // the part's first n elements (default: all) back into its host array
+    template <class T>
+    hipError_t back(const Part<T> &p, size_t n = SIZE_MAX) const
+    {
+        if (p.k < 0) return hipSuccess;
+        const size_t bytes = std::min(n, recs[p.k].bytes / sizeof(T)) * sizeof(T);
+        return bytes ? hipMemcpyAsync(recs[p.k].host, (T *)p, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+    }
+    // bytes from the part's start to the blob's end (the padding between parts included)
+    template <class T>
+    size_t bytes_from(const Part<T> &p) const { return lay.total - recs[p.k].at; }
+};
+
+// host forms: the bytes of `reads` that the offsets and lengths span
+static int reads_extent(const int64_t *read_off, const int32_t *read_len, int32_t n_reads, int64_t *rbytes)
+{
+    *rbytes = 0;
+    for (int32_t i = 0; i < n_reads; ++i) {
+        if (read_off[i] < 0 || read_len[i] < 0) return BSW_E_RANGE;
+        *rbytes = std::max<int64_t>(*rbytes, read_off[i] + read_len[i]);
+    }
+    return BSW_OK;
+}
+
+// Times a stage's helper kernels on `st` with one event pair of the slot (ev2 / ev3; mate rescue
+// evw0 / evw1: its batched ksw_align2 times itself with ev0..ev3).  begin() .. end() bracket a
+// region; add() reads it once the stream has been waited for -- it does not wait itself.
+struct BSW_HIDDEN HelperTimer {
+    hipEvent_t a = nullptr, b = nullptr;
+    hipStream_t st = nullptr;
+    hipError_t init(Event &ea, Event &eb, hipStream_t stream)
+    {
+        hipError_t e = ea ? hipSuccess : hipEventCreate(&ea.p);
+        if (e == hipSuccess && !eb) e = hipEventCreate(&eb.p);
+        a = ea; b = eb; st = stream;
+        return e;
+    }
+    hipError_t begin() const { return hipEventRecord(a, st); }
+    hipError_t end() const { return hipEventRecord(b, st); }
+    hipError_t add(float &total) const
+    {
+        float ms = 0.f;                 // (stays 0 on an error)
+        const hipError_t e = hipEventElapsedTime(&ms, a, b);
+        total += ms;
+        return e;
+    }
+};
+
+// The slot's buffers for a round of nj DP jobs of strides qstride / tstride; *chunk = the jobs per batch
+static hipError_t dp_job_buffers(Slot &s, int32_t nj, int32_t qstride, int32_t tstride, int32_t *chunk)
+{
+    // SeqPair idr / idq are int32: chunk so j * stride stays below 2^31
+    *chunk = (int32_t)std::min<int64_t>(nj, (int64_t)INT32_MAX / std::max(tstride, qstride) - 1);
+    if (hipError_t e = s.d_apairs.grow((size_t)*chunk)) return e;
+    if (hipError_t e = s.d_aq.grow((size_t)*chunk * qstride)) return e;
+    return s.d_at.grow((size_t)*chunk * tstride);
+}
+
+// A batch of n DP jobs (d_apairs / d_at / d_aq) through ksw_global2; its time onto dp_ms, its stats
+// published as the context's last global-alignment call (bsw_global_last_stats: the last DP batch)
+static int dp_batch(bsw_ctx_t *ctx, const GlobParams &gp, Slot &s, int32_t n, uint32_t *d_cigar, int32_t stride,
+                    int32_t *d_ncig, hipStream_t st, float &dp_ms)
+{
+    bsw_global_stats_t gs;
+    if (int r = glob_device(gp, s, s.d_apairs, s.d_at, s.d_aq, n, d_cigar, stride, d_ncig, st, &gs)) return r;
+    dp_ms += gs.kernel_ms;
+    put_stats(ctx, &bsw_ctx::glob_last, gs);
+    return BSW_OK;
+}
+
+// the resident reference is the forward + reverse strands of an l_pac-base genome; the caller
+// holds dc.refmu shared
+static bool ref_ok(const DeviceCtx &dc, int64_t l_pac) { return dc.d_refres && dc.refres_len == 2 * l_pac; }
+
+}  // namespace bsw
+
+// ---------------------------------------------------------------- final alignments (bsw_aln.h)
+namespace bsw {
+
+static_assert(kAlnMetaSpread * 16 <= kMetaMaxq && kMetaMaxq + kAlnCntWords <= kMetaWords, "aln meta fits d_meta");
+
+// plan + gap-free -> per pass: build -> ksw_global2 (glob_device) -> finish.  Everything on `st`;
+// the host waits once for the plan's counts and once per pass for the next pass's job count.
+static int reg2aln_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st, const bsw_ext_opt_t &opt,
+                          const uint8_t *d_reads, const int64_t *d_read_off, const int32_t *d_read_len,
+                          int32_t n_reads, const bsw_alnreg_t *d_regs, const int32_t *d_reg_read, int32_t n,
+                          bsw_aln_t *d_aln, uint32_t *d_cigar, int32_t cigar_stride, uint8_t *d_md,
+                          int32_t md_stride, bsw_aln_stats_t &as)
+{
+    const bsw_params_t &pr = ctx->params;
+    AlnParams p{};
+    p.W = opt.w; p.a = pr.mat[0];
+    p.o_del = pr.o_del; p.e_del = pr.e_del; p.o_ins = pr.o_ins; p.e_ins = pr.e_ins;
+    p.n_reads = n_reads;
+    p.cigar_stride = cigar_stride; p.md_stride = md_stride;
+    p.ref_len = dc.refres_len; p.l_pac = opt.l_pac;
+    memcpy(p.mat, pr.mat, 25);
+    GlobParams gp;
+    make_glob_params(pr, ctx->glob_band, gp);
+    BSW_TRY(s.d_ast.grow((size_t)n));
+    BSW_TRY(s.d_alist.grow(2 * (size_t)n));
+    BSW_TRY(s.d_acnt.grow(kAlnCntWords));
+    HelperTimer tm;
+    BSW_TRY(tm.init(s.ev2, s.ev3, st));
+    int32_t *h_cnt = s.h_meta + kMetaMaxq;
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_aln_plan(p, d_read_len, d_regs, d_reg_read, n, s.d_ast, s.d_alist, s.d_acnt, s.d_meta, d_aln, st));
+    BSW_TRY(hipMemcpyAsync(s.h_meta, s.d_meta, kAlnMetaSpread * 16 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_cnt, s.d_acnt, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    // (regions the plan found in error are marked rejected: the gap-free kernel skips them)
+    BSW_TRY(launch_aln_gapfree(p, d_reads, d_read_off, d_read_len, d_regs, d_reg_read, n, s.d_ast, dc.d_refres, d_aln,
+                               d_cigar, d_md, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(as.helper_ms));
+    int32_t m[5] = {0, 0, 0, 0, 0};
+    for (int sl = 0; sl < kAlnMetaSpread; ++sl) {
+        const int32_t *v = s.h_meta + sl * 16;
+        m[0] |= v[0]; m[1] += v[1]; m[2] += v[2]; m[3] = std::max(m[3], v[3]); m[4] = std::max(m[4], v[4]);
+    }
+    if (m[0]) return BSW_E_RANGE;
+    as.n_rejected = m[1];
+    as.n_gapfree = m[2];
+    p.qstride = std::max(m[3], 1);                      // longest DP query / reference span
+    p.tstride = std::max(m[4], 1);
+    int32_t nj = h_cnt[0];
+    for (int pass = 0; pass < 3 && nj > 0; ++pass) {
+        as.n_dp[pass] = nj;
+        const int32_t *list = s.d_alist + (size_t)(pass & 1) * n;
+        int32_t *next = s.d_alist + (size_t)((pass + 1) & 1) * n;
+        int32_t chunk;
+        BSW_TRY(dp_job_buffers(s, nj, p.qstride, p.tstride, &chunk));
+        BSW_TRY(s.d_gcig.grow((size_t)chunk * (size_t)cigar_stride));
+        BSW_TRY(s.d_gncig.grow((size_t)chunk));
+        for (int32_t a = 0; a < nj; a += chunk) {
+            const int32_t b = std::min(nj, a + chunk);
+            BSW_TRY(tm.begin());
+            BSW_TRY(launch_aln_build(p, d_reads, d_read_off, d_regs, d_reg_read, s.d_ast, list + a, b - a, dc.d_refres,
+                                     s.d_apairs, s.d_aq, s.d_at, st));
+            BSW_TRY(tm.end());
+            if (int r = dp_batch(ctx, gp, s, b - a, s.d_gcig, cigar_stride, s.d_gncig, st, as.dp_ms)) return r;
+            BSW_TRY(tm.add(as.helper_ms));              // (the batch waited for the stream)
+            BSW_TRY(tm.begin());
+            BSW_TRY(launch_aln_finish(p, d_read_len, d_regs, d_reg_read, s.d_ast, list + a, b - a, s.d_apairs, s.d_aq,
+                                      s.d_at, s.d_gcig, s.d_gncig, next, s.d_acnt + pass + 1, d_aln, d_cigar, d_md, st));
+            BSW_TRY(tm.end());
+            BSW_TRY(hipMemcpyAsync(h_cnt, s.d_acnt + pass + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            BSW_TRY(hipStreamSynchronize(st));
+            BSW_TRY(tm.add(as.helper_ms));
+        }
+        nj = pass < 2 ? h_cnt[0] : 0;
+    }
+    return BSW_OK;
+}
+
+// argument checks shared by both forms; the caller holds dc.refmu shared
+static int reg2aln_check(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, DeviceCtx &dc, int32_t n_reads, int32_t n_regs,
+                         int32_t cigar_stride, const void *md, int32_t md_stride)
+{
+    if (n_reads < 0 || n_regs < 0 || cigar_stride < 1 || md_stride < 0 || (md == nullptr) != (md_stride == 0))
+        return BSW_E_INVAL;
+    if (!dc.d_refres) return BSW_E_INVAL;
+    if (opt->w < 0 || opt->w > (1 << 28) || opt->l_pac < 0 || (opt->l_pac > 0 && !ref_ok(dc, opt->l_pac)))
+        return BSW_E_INVAL;
+    return BSW_OK;
+}
+
+}  // namespace bsw
+
+extern "C" {
+
+int bsw_reg2aln_resident(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint8_t *d_reads,
+                         const int64_t *d_read_off, const int32_t *d_read_len, int32_t n_reads,
+                         const bsw_alnreg_t *d_regs, const int32_t *d_reg_read, int32_t n_regs,
+                         bsw_aln_t *d_aln, uint32_t *d_cigar, int32_t cigar_stride, uint8_t *d_md,
+                         int32_t md_stride, void *stream)
+{
+    if (!ctx || !opt) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the resident reference stays put
+    if (const int rc = bsw::reg2aln_check(ctx, opt, dc, n_reads, n_regs, cigar_stride, d_md, md_stride)) return rc;
+    if (n_regs > 0 && (!d_reads || !d_read_off || !d_read_len || !d_regs || !d_reg_read || !d_aln || !d_cigar))
+        return BSW_E_INVAL;
+    bsw_aln_stats_t as{};
+    as.n_regs = n_regs;
+    if (n_regs > 0) {
+        const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+            hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+            return bsw::reg2aln_device(ctx, dc, s, st, *opt, d_reads, d_read_off, d_read_len, n_reads, d_regs,
+                                       d_reg_read, n_regs, d_aln, d_cigar, cigar_stride, d_md, md_stride, as);
+        });
+        if (rc) return rc;
+    }
+    bsw::put_stats(ctx, &bsw_ctx::aln_last, as);
+    return BSW_OK;
+}
+
+int bsw_reg2aln(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint8_t *reads, const int64_t *read_off,
+                const int32_t *read_len, int32_t n_reads, const bsw_alnreg_t *regs, const int32_t *reg_read,
+                int32_t n_regs, bsw_aln_t *aln, uint32_t *cigar, int32_t cigar_stride, uint8_t *md,
+                int32_t md_stride)
+{
+    if (!ctx || !opt) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::reg2aln_check(ctx, opt, dc, n_reads, n_regs, cigar_stride, md, md_stride)) return rc;
+    if (n_regs > 0 && (!reads || !read_off || !read_len || !regs || !reg_read || !aln || !cigar)) return BSW_E_INVAL;
+    bsw_aln_stats_t as{};
+    as.n_regs = n_regs;
+    if (n_regs > 0) {
+        int64_t rbytes;
+        if (const int rc = bsw::reads_extent(read_off, read_len, n_reads, &rbytes)) return rc;
+        const size_t n = (size_t)n_regs, nr = (size_t)n_reads;
+        bsw::StagedIo io;
+        const auto d_reads = io.in(reads, (size_t)rbytes);
+        const auto d_read_off = io.in(read_off, nr);
+        const auto d_read_len = io.in(read_len, nr);
+        const auto d_regs = io.in(regs, n);
+        const auto d_reg_read = io.in(reg_read, n);
+        const auto d_aln = io.out(aln, n);
+        const auto d_cigar = io.out(cigar, n * (size_t)cigar_stride);
+        const auto d_md = io.out_opt(md, n * (size_t)md_stride);
+        const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+            BSW_TRY(io.grow(s));
+            // (rows the kernels leave unwritten -- rejected regions, overflows -- read back as zeros:
+            // cigar and md, the blob's last two parts)
+            BSW_TRY(hipMemsetAsync(d_cigar, 0, io.bytes_from(d_cigar), s.stream));
+            BSW_TRY(io.upload());
+            if (int r = bsw::reg2aln_device(ctx, dc, s, s.stream, *opt, d_reads, d_read_off, d_read_len, n_reads, d_regs,
+                                            d_reg_read, n_regs, d_aln, d_cigar, cigar_stride, d_md, md_stride, as))
+                return r;
+            BSW_TRY(io.back(d_aln));
+            BSW_TRY(io.back(d_cigar));
+            BSW_TRY(io.back(d_md));
+            BSW_TRY(hipStreamSynchronize(s.stream));
+            return BSW_OK;
+        });
+        if (rc) return rc;
+    }
+    bsw::put_stats(ctx, &bsw_ctx::aln_last, as);
+    return BSW_OK;
+}
+
+int bsw_aln_last_stats(bsw_ctx_t *ctx, bsw_aln_stats_t *out) { return bsw::get_stats(ctx, &bsw_ctx::aln_last, out); }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- region selection (bsw_sel.h)
+namespace bsw {
+
+struct SelIo {                          // device pointers of one call, either form
+    const uint8_t *reads;
+    const int64_t *read_off;
+    const int32_t *read_len;
+    const bsw_seed_t *seeds;
+    const int32_t *seed_read, *seed_chain;
+    const bsw_alnreg_t *regs;
+    const int32_t *extended, *csub;
+    const float *frac_rep;
+    bsw_alnreg_t *sel_regs;
+    int32_t *sel_read;
+    bsw_selinfo_t *sel_info;
+    int32_t *read_first;
+};
+
+// runs -> gather -> step; per patch round: build -> score-only ksw_global2 (glob_device) -> step
+// over the suspended reads; then scan of the kept counts -> emit.  Everything on `st`; the host
+// waits once per round for the next round's job count and once for the total.
+static int regs_select_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st, const bsw_sel_opt_t &opt,
+                              const SelIo &io, int32_t n_reads, int32_t n_seeds, int32_t sel_cap, int32_t *n_sel,
+                              bsw_sel_stats_t &ss)
+{
+    const bsw_params_t &pr = ctx->params;
+    SelParams p{};
+    p.W = opt.w; p.a = pr.mat[0]; p.b = opt.b;
+    p.o_del = pr.o_del; p.e_del = pr.e_del; p.o_ins = pr.o_ins; p.e_ins = pr.e_ins;
+    p.n_reads = n_reads; p.n_seeds = n_seeds;
+    p.max_chain_gap = opt.max_chain_gap; p.min_seed_len = opt.min_seed_len;
+    p.mapQ_coef_len = opt.mapQ_coef_len; p.mapQ_coef_fac = opt.mapQ_coef_fac; p.patch = opt.patch;
+    p.mask_level_redun = opt.mask_level_redun; p.mask_level = opt.mask_level;
+    p.ref_len = dc.refres_len; p.l_pac = opt.l_pac; p.id0 = opt.id0;
+    memcpy(p.mat, pr.mat, 25);
+    GlobParams gp;
+    make_glob_params(pr, ctx->glob_band, gp);
+    const size_t nr = (size_t)n_reads, ns = (size_t)n_seeds;
+    size_t scan_bytes = 0;
+    BSW_TRY(launch_sel_scan(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
+    BSW_TRY(s.d_swork.grow(std::max<size_t>(ns, 1)));
+    BSW_TRY(s.d_sz.grow(std::max<size_t>(ns, 1)));
+    BSW_TRY(s.d_sst.grow(std::max<size_t>(nr, 1)));
+    BSW_TRY(s.d_srun.grow(2 * nr + 1));
+    BSW_TRY(s.d_skept.grow(nr + 1));
+    BSW_TRY(s.d_slist.grow(2 * nr + 1));
+    BSW_TRY(s.d_smeta.grow(kSelMetaWords));
+    BSW_TRY(s.d_tmp.grow(std::max<size_t>(scan_bytes, 16)));
+    HelperTimer tm;
+    BSW_TRY(tm.init(s.ev2, s.ev3, st));
+    int32_t *sbeg = s.d_srun, *send = s.d_srun + nr;
+    int32_t *h_meta = s.h_meta;
+    BSW_TRY(tm.begin());
+    BSW_TRY(hipMemsetAsync(s.d_srun, 0, (2 * nr + 1) * sizeof(int32_t), st));
+    BSW_TRY(hipMemsetAsync(s.d_skept, 0, (nr + 1) * sizeof(int32_t), st));
+    BSW_TRY(hipMemsetAsync(s.d_smeta, 0, kSelMetaWords * sizeof(int32_t), st));
+    BSW_TRY(launch_sel_runs(io.seed_read, n_seeds, n_reads, sbeg, send, s.d_smeta, st));
+    BSW_TRY(launch_sel_gather(p, sbeg, send, io.read_len, io.seeds, io.seed_chain, io.regs, io.extended, io.csub,
+                              s.d_swork, s.d_sst, s.d_smeta, st));
+    BSW_TRY(launch_sel_step(p, nullptr, n_reads, nullptr, sbeg, io.reads, io.read_off, io.frac_rep, dc.d_refres,
+                            s.d_swork, s.d_sst, s.d_sz, s.d_slist, s.d_smeta + kSelCnt, s.d_skept, s.d_smeta, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipMemcpyAsync(h_meta, s.d_smeta, kSelMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(ss.helper_ms));
+    if (h_meta[kSelErr]) return BSW_E_RANGE;
+    int32_t nj = h_meta[kSelCnt];
+    for (int round = 0; nj > 0; ++round) {
+        ss.rounds++;
+        ss.n_dp += nj;
+        const int cur = round & 1, nxt = cur ^ 1;
+        const int32_t *list = s.d_slist + (size_t)cur * nr;
+        int32_t *next = s.d_slist + (size_t)nxt * nr;
+        p.qstride = std::max(h_meta[kSelMaxQ], 1);          // longest patch query / reference span so far
+        p.tstride = std::max(h_meta[kSelMaxT], 1);
+        int32_t chunk;
+        BSW_TRY(dp_job_buffers(s, nj, p.qstride, p.tstride, &chunk));
+        BSW_TRY(hipMemsetAsync(s.d_smeta + kSelCnt + nxt, 0, sizeof(int32_t), st));
+        for (int32_t a = 0; a < nj; a += chunk) {
+            const int32_t b = std::min(nj, a + chunk);
+            BSW_TRY(tm.begin());
+            BSW_TRY(launch_sel_build(p, list + a, b - a, sbeg, io.reads, io.read_off, s.d_swork, s.d_sst, dc.d_refres,
+                                     s.d_apairs, s.d_aq, s.d_at, st));
+            BSW_TRY(tm.end());
+            if (int r = dp_batch(ctx, gp, s, b - a, nullptr, 0, nullptr, st, ss.dp_ms)) return r;
+            BSW_TRY(tm.add(ss.helper_ms));              // (the batch waited for the stream)
+            BSW_TRY(tm.begin());
+            BSW_TRY(launch_sel_step(p, list + a, b - a, s.d_apairs, sbeg, io.reads, io.read_off, io.frac_rep,
+                                    dc.d_refres, s.d_swork, s.d_sst, s.d_sz, next, s.d_smeta + kSelCnt + nxt, s.d_skept,
+                                    s.d_smeta, st));
+            BSW_TRY(tm.end());
+            BSW_TRY(hipMemcpyAsync(h_meta, s.d_smeta, kSelMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            BSW_TRY(hipStreamSynchronize(st));
+            BSW_TRY(tm.add(ss.helper_ms));
+            if (h_meta[kSelErr]) return BSW_E_RANGE;
+        }
+        nj = h_meta[kSelCnt + nxt];
+    }
+    ss.n_regs_in = h_meta[kSelRegsIn];
+    ss.n_redundant = h_meta[kSelRedundant];
+    ss.n_identical = h_meta[kSelIdentical];
+    ss.n_patch_tried = h_meta[kSelTried];
+    ss.n_patch_ok = h_meta[kSelOk];
+    ss.n_patch_ratio = h_meta[kSelRatio];
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, s.d_skept, io.read_first, n_reads, st));
+    BSW_TRY(hipMemcpyAsync(h_meta, io.read_first + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    *n_sel = ss.n_sel = h_meta[0];
+    if (h_meta[0] > sel_cap) return BSW_E_RANGE;
+    BSW_TRY(launch_sel_emit(p, io.seed_read, sbeg, s.d_skept, io.read_first, s.d_swork, io.frac_rep, io.sel_regs,
+                            io.sel_read, io.sel_info, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(ss.helper_ms));
+    return BSW_OK;
+}
+
+// argument checks shared by both forms; the caller holds dc.refmu shared
+static int regs_select_check(const bsw_sel_opt_t *opt, DeviceCtx &dc, int32_t n_reads, int32_t n_seeds,
+                             int32_t sel_cap)
+{
+    if (n_reads < 0 || n_seeds < 0 || sel_cap < 0) return BSW_E_INVAL;
+    if (!dc.d_refres) return BSW_E_INVAL;
+    if (opt->w < 0 || opt->w > (1 << 28) || opt->l_pac < 0 || (opt->l_pac > 0 && !ref_ok(dc, opt->l_pac)))
+        return BSW_E_INVAL;
+    if (opt->max_chain_gap < 0 || opt->mapQ_coef_len < 0 || opt->b < 0 || opt->min_seed_len < 0) return BSW_E_INVAL;
+    return BSW_OK;
+}
+
+}  // namespace bsw
+
+extern "C" {
+
+void bsw_sel_opt_default(bsw_sel_opt_t *opt)
+{
+    if (!opt) return;
+    memset(opt, 0, sizeof(*opt));
+    opt->w = 100;
+    opt->max_chain_gap = 10000;
+    opt->l_pac = 0;
+    opt->mask_level_redun = 0.95f;
+    opt->mask_level = 0.5f;
+    opt->min_seed_len = 19;
+    opt->b = 4;
+    opt->mapQ_coef_len = 50;
+    opt->mapQ_coef_fac = 3;
+    opt->patch = 1;
+    opt->id0 = 0;
+}
+
+int bsw_regs_select_resident(bsw_ctx_t *ctx, const bsw_sel_opt_t *opt, const uint8_t *d_reads,
+                             const int64_t *d_read_off, const int32_t *d_read_len, int32_t n_reads,
+                             const bsw_seed_t *d_seeds, const int32_t *d_seed_read, const int32_t *d_seed_chain,
+                             const bsw_alnreg_t *d_regs, const int32_t *d_extended, int32_t n_seeds,
+                             const int32_t *d_csub, const float *d_frac_rep, bsw_alnreg_t *d_sel_regs,
+                             int32_t *d_sel_read, bsw_selinfo_t *d_sel_info, int32_t *d_read_first,
+                             int32_t sel_cap, int32_t *n_sel, void *stream)
+{
+    if (!ctx || !opt || !n_sel) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the resident reference stays put
+    if (const int rc = bsw::regs_select_check(opt, dc, n_reads, n_seeds, sel_cap)) return rc;
+    if (!d_read_first || (n_reads > 0 && (!d_read_off || !d_read_len)) ||
+        (n_seeds > 0 && (!d_reads || !d_seeds || !d_seed_read || !d_seed_chain || !d_regs || !d_extended)) ||
+        (sel_cap > 0 && (!d_sel_regs || !d_sel_read || !d_sel_info)))
+        return BSW_E_INVAL;
+    bsw_sel_stats_t ss{};
+    ss.n_reads = n_reads;
+    const bsw::SelIo io = {d_reads, d_read_off, d_read_len, d_seeds, d_seed_read, d_seed_chain, d_regs, d_extended,
+                           d_csub, d_frac_rep, d_sel_regs, d_sel_read, d_sel_info, d_read_first};
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::regs_select_device(ctx, dc, s, st, *opt, io, n_reads, n_seeds, sel_cap, n_sel, ss);
+    });
+    if (rc) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::sel_last, ss);
+    return BSW_OK;
+}
+
+int bsw_regs_select(bsw_ctx_t *ctx, const bsw_sel_opt_t *opt, const uint8_t *reads, const int64_t *read_off,
+                    const int32_t *read_len, int32_t n_reads, const bsw_seed_t *seeds, const int32_t *seed_read,
+                    const int32_t *seed_chain, const bsw_alnreg_t *regs, const int32_t *extended, int32_t n_seeds,
+                    const int32_t *csub, const float *frac_rep, bsw_alnreg_t *sel_regs, int32_t *sel_read,
+                    bsw_selinfo_t *sel_info, int32_t *read_first, int32_t sel_cap, int32_t *n_sel)
+{
+    if (!ctx || !opt || !n_sel) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::regs_select_check(opt, dc, n_reads, n_seeds, sel_cap)) return rc;
+    if (!read_first || (n_reads > 0 && (!read_off || !read_len)) ||
+        (n_seeds > 0 && (!reads || !seeds || !seed_read || !seed_chain || !regs || !extended)) ||
+        (sel_cap > 0 && (!sel_regs || !sel_read || !sel_info)))
+        return BSW_E_INVAL;
+    int64_t rbytes;
+    if (const int rc = bsw::reads_extent(read_off, read_len, n_reads, &rbytes)) return rc;
+    bsw_sel_stats_t ss{};
+    ss.n_reads = n_reads;
+    const size_t ns = (size_t)n_seeds, nr = (size_t)n_reads, nc = (size_t)sel_cap;
+    bsw::StagedIo io;
+    const auto d_reads = io.in(reads, (size_t)rbytes);
+    const auto d_read_off = io.in(read_off, nr);
+    const auto d_read_len = io.in(read_len, nr);
+    const auto d_seeds = io.in(seeds, ns);
+    const auto d_seed_read = io.in(seed_read, ns);
+    const auto d_seed_chain = io.in(seed_chain, ns);
+    const auto d_regs = io.in(regs, ns);
+    const auto d_extended = io.in(extended, ns);
+    const auto d_csub = io.in_opt(csub, ns);
+    const auto d_frac_rep = io.in_opt(frac_rep, nr);
+    const auto d_sel_regs = io.out(sel_regs, nc);
+    const auto d_sel_read = io.out(sel_read, nc);
+    const auto d_sel_info = io.out(sel_info, nc);
+    const auto d_read_first = io.out(read_first, nr + 1);
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(io.stage(s));
+        const bsw::SelIo dio = {d_reads, d_read_off, d_read_len, d_seeds, d_seed_read, d_seed_chain, d_regs, d_extended,
+                                d_csub, d_frac_rep, d_sel_regs, d_sel_read, d_sel_info, d_read_first};
+        if (int r = bsw::regs_select_device(ctx, dc, s, s.stream, *opt, dio, n_reads, n_seeds, sel_cap, n_sel, ss))
+            return r;
+        BSW_TRY(io.back(d_sel_regs, (size_t)*n_sel));   // (the rows emitted, not sel_cap of them)
+        BSW_TRY(io.back(d_sel_read, (size_t)*n_sel));
+        BSW_TRY(io.back(d_sel_info, (size_t)*n_sel));
+        BSW_TRY(io.back(d_read_first));
+        BSW_TRY(hipStreamSynchronize(s.stream));
+        return BSW_OK;
+    });
+    if (rc) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::sel_last, ss);
+    return BSW_OK;
+}
+
+int bsw_sel_last_stats(bsw_ctx_t *ctx, bsw_sel_stats_t *out) { return bsw::get_stats(ctx, &bsw_ctx::sel_last, out); }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- paired-end stage (bsw_pe.h)
+namespace bsw {
+
+// argument checks of both calls and both forms, before anything touches a device
+static int pe_check_args(const bsw_pe_opt_t *opt, int32_t n_reads, int32_t n_regs)
+{
+    if (!opt || n_reads < 0 || (n_reads & 1) || n_regs < 0) return BSW_E_INVAL;
+    if (opt->l_pac <= 0 || (opt->id0 & 1) || opt->max_ins < 1 || opt->max_ins > BSW_PE_MAX_INS) return BSW_E_INVAL;
+    if (opt->min_seed_len < 0 || opt->b < 0 || opt->mapQ_coef_len < 0) return BSW_E_INVAL;
+    return BSW_OK;
+}
+
+static int pe_check_pes(const bsw_pestat_t *pes)
+{
+    if (!pes) return BSW_E_INVAL;
+    for (int d = 0; d < 4; ++d)
+        if (!pes[d].failed && !(std::isfinite(pes[d].std) && pes[d].std > 0 && std::isfinite(pes[d].avg)))
+            return BSW_E_INVAL;
+    return BSW_OK;
+}
+
+// the stage reads no reference; one that is resident has to be the l_pac the call names
+static int pe_check_ref(const bsw_pe_opt_t &opt, DeviceCtx &dc)
+{
+    return !dc.d_refres || ref_ok(dc, opt.l_pac) ? BSW_OK : BSW_E_INVAL;
+}
+
+static void make_pe_params(const bsw_ctx_t *ctx, const bsw_pe_opt_t &opt, int32_t n_reads, int32_t n_regs, PeParams &p)
+{
+    const bsw_params_t &pr = ctx->params;
+    memset(&p, 0, sizeof(p));
+    p.s.a = pr.mat[0]; p.s.b = opt.b;
+    p.s.o_del = pr.o_del; p.s.e_del = pr.e_del; p.s.o_ins = pr.o_ins; p.s.e_ins = pr.e_ins;
+    p.s.n_reads = n_reads;
+    p.s.min_seed_len = opt.min_seed_len; p.s.mapQ_coef_len = opt.mapQ_coef_len; p.s.mapQ_coef_fac = opt.mapQ_coef_fac;
+    p.s.mask_level = opt.mask_level;
+    p.s.l_pac = opt.l_pac; p.s.id0 = opt.id0;
+    p.n_pairs = n_reads / 2; p.n_regs = n_regs;
+    p.max_ins = opt.max_ins; p.T = opt.T; p.pen_unpaired = opt.pen_unpaired;
+}
+
+// mem_pestat's per-direction arithmetic over the counts c[v] of insert size v (bsw_pe.h)
+static void pestat_of_counts(const int32_t *hist, int bins, bsw_pestat_t *pes)
+{
+    int64_t nmax = 0;
+    for (int d = 0; d < 4; ++d) {
+        const int32_t *c = hist + (size_t)d * bins;
+        int64_t n = 0;
+        for (int v = 0; v < bins; ++v) n += c[v];
+        bsw_pestat_t r{};
+        r.n = (int32_t)n;
+        nmax = std::max(nmax, n);
+        if (n < 10) {
+            r.failed = 1;
+            pes[d] = r;
+            continue;
+        }
+        auto at = [&](int k) {                      // the k-th smallest value
+            int64_t acc = 0;
+            for (int v = 0; v < bins; ++v) {
+                acc += c[v];
+                if (acc > k) return v;
+            }
+            return bins - 1;
+        };
+        const int p25 = at((int)(.25 * n + .499)), p75 = at((int)(.75 * n + .499));
+        r.low = (int)(p25 - 2.0 * (p75 - p25) + .499);
+        if (r.low < 1) r.low = 1;
+        r.high = (int)(p75 + 2.0 * (p75 - p25) + .499);
+        int64_t x = 0;
+        const int v0 = std::max(r.low, 0), v1 = std::min(r.high, bins - 1);
+        for (int v = v0; v <= v1; ++v) {
+            r.avg += (double)c[v] * v;              // (sums of integers: exact in any order)
+            x += c[v];
+        }
+        r.avg /= x;
+        for (int v = v0; v <= v1; ++v) r.std += (double)c[v] * ((v - r.avg) * (v - r.avg));
+        r.std = sqrt(r.std / x);
+        r.low = (int)(p25 - 3.0 * (p75 - p25) + .499);
+        r.high = (int)(p75 + 3.0 * (p75 - p25) + .499);
+        if (r.low > r.avg - 4.0 * r.std) r.low = (int)(r.avg - 4.0 * r.std + .499);
+        if (r.high < r.avg + 4.0 * r.std) r.high = (int)(r.avg + 4.0 * r.std + .499);
+        if (r.low < 1) r.low = 1;
+        pes[d] = r;
+    }
+    for (int d = 0; d < 4; ++d)
+        if (pes[d].failed == 0 && pes[d].n < nmax * 0.05) pes[d].failed = 1;
+}
+
+// count kernel -> the four count arrays and the error word back -> the statistics on the host
+static int pe_stat_device(bsw_ctx_t *ctx, Slot &s, hipStream_t st, const bsw_pe_opt_t &opt, const bsw_alnreg_t *regs,
+                          const int32_t *first, int32_t n_reads, int32_t n_regs, bsw_pestat_t *pes, bsw_pe_stats_t &ps)
+{
+    PeParams p;
+    make_pe_params(ctx, opt, n_reads, n_regs, p);
+    const int bins = opt.max_ins + 1;
+    BSW_TRY(s.d_phist.grow((size_t)4 * bins));
+    BSW_TRY(s.d_pmeta.grow(kPeSlots * kPeMetaWords));
+    HelperTimer tm;
+    BSW_TRY(tm.init(s.ev2, s.ev3, st));
+    std::vector<int32_t> h((size_t)4 * bins);
+    int32_t *h_meta = s.h_meta;
+    BSW_TRY(hipMemsetAsync(s.d_phist, 0, h.size() * sizeof(int32_t), st));
+    BSW_TRY(hipMemsetAsync(s.d_pmeta, 0, kPeSlots * kPeMetaWords * sizeof(int32_t), st));
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_pe_stat(p, regs, first, s.d_phist, s.d_pmeta, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipMemcpyAsync(h_meta, s.d_pmeta, kPeSlots * kPeMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h.data(), s.d_phist, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(ps.kernel_ms));
+    if (h_meta[kPeErr]) return BSW_E_RANGE;
+    pestat_of_counts(h.data(), bins, pes);
+    for (int d = 0; d < 4; ++d) ps.n_cand[d] = pes[d].n;
+    return BSW_OK;
+}
+
+// fast kernel over every pair -> general kernel over the pairs it listed (their count stays on
+// the device) -> the counters back
+static int pe_pair_device(bsw_ctx_t *ctx, Slot &s, hipStream_t st, const bsw_pe_opt_t &opt, const bsw_pestat_t *pes,
+                          bsw_alnreg_t *regs, bsw_selinfo_t *info, const int32_t *first, int32_t n_reads,
+                          int32_t n_regs, bsw_pair_t *pairs, bsw_pe_stats_t &ps)
+{
+    PeParams p;
+    make_pe_params(ctx, opt, n_reads, n_regs, p);
+    for (int d = 0; d < 4; ++d) {
+        p.pes[d].avg = pes[d].avg; p.pes[d].std = pes[d].std;
+        p.pes[d].low = pes[d].low; p.pes[d].high = pes[d].high; p.pes[d].failed = pes[d].failed != 0;
+    }
+    const size_t ng = std::max<size_t>((size_t)n_regs, 1);
+    BSW_TRY(s.d_swork.grow(ng));
+    BSW_TRY(s.d_sz.grow(ng));
+    BSW_TRY(s.d_pv.grow(ng));
+    BSW_TRY(s.d_plist.grow(std::max<size_t>((size_t)p.n_pairs, 1)));
+    BSW_TRY(s.d_pmeta.grow(kPeSlots * kPeMetaWords));
+    HelperTimer tm;
+    BSW_TRY(tm.init(s.ev2, s.ev3, st));
+    int32_t *h_meta = s.h_meta;
+    BSW_TRY(hipMemsetAsync(s.d_pmeta, 0, kPeSlots * kPeMetaWords * sizeof(int32_t), st));
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_pe_pair_fast(p, regs, info, first, pairs, s.d_plist, s.d_pmeta, st));
+    BSW_TRY(launch_pe_pair_general(p, regs, info, first, pairs, s.d_plist, s.d_swork, s.d_sz, s.d_pv, s.d_pmeta, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipMemcpyAsync(h_meta, s.d_pmeta, kPeSlots * kPeMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(ps.kernel_ms));
+    if (h_meta[kPeErr]) return BSW_E_RANGE;
+    static_assert(kPeSlots * kPeMetaWords <= kMetaWords, "the slot's pinned mirror holds the pair counters");
+    for (int k = 0; k < kPeSlots; ++k) {
+        const int32_t *m = h_meta + k * kPeMetaWords;
+        int64_t nu;
+        memcpy(&nu, m + kPeNu, sizeof(nu));
+        ps.n_pairing_tried += m[kPeTried];
+        ps.n_paired += m[kPePaired];
+        ps.n_multi += m[kPeMulti];
+        ps.n_unpaired_preferred += m[kPeUnpaired];
+        ps.n_proper += m[kPeProper];
+        ps.n_u += nu;
+    }
+    return BSW_OK;
+}
+
+// host forms: read_first as the device will check it, so the staged sizes can be trusted
+static int pe_host_first(const int32_t *read_first, int32_t n_reads, int32_t &n_regs)
+{
+    if (!read_first) return BSW_E_INVAL;
+    if (read_first[0] < 0) return BSW_E_RANGE;
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (read_first[r + 1] < read_first[r]) return BSW_E_RANGE;
+    n_regs = read_first[n_reads];
+    return BSW_OK;
+}
+
+}  // namespace bsw
+
+extern "C" {
+
+void bsw_pe_opt_default(bsw_pe_opt_t *opt)
+{
+    if (!opt) return;
+    memset(opt, 0, sizeof(*opt));
+    opt->max_ins = 10000;
+    opt->min_seed_len = 19;
+    opt->b = 4;
+    opt->T = 30;
+    opt->pen_unpaired = 17;
+    opt->mapQ_coef_len = 50;
+    opt->mapQ_coef_fac = 3;
+    opt->mask_level = 0.5f;
+}
+
+int bsw_pe_stat_resident(bsw_ctx_t *ctx, const bsw_pe_opt_t *opt, const bsw_alnreg_t *d_sel_regs,
+                         const bsw_selinfo_t *d_sel_info, const int32_t *d_read_first, int32_t n_reads,
+                         int32_t n_regs, bsw_pestat_t *pes, void *stream)
+{
+    (void)d_sel_info;                   // (the statistics read the regions alone)
+    if (const int rc = bsw::pe_check_args(opt, n_reads, n_regs)) return rc;
+    if (!ctx || !pes || !d_read_first || (n_regs > 0 && !d_sel_regs)) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::pe_check_ref(*opt, dc)) return rc;
+    bsw_pe_stats_t ps{};
+    ps.n_pairs = n_reads / 2;
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::pe_stat_device(ctx, s, st, *opt, d_sel_regs, d_read_first, n_reads, n_regs, pes, ps);
+    });
+    if (rc) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::pe_last, ps);
+    return BSW_OK;
+}
+
+int bsw_pe_stat(bsw_ctx_t *ctx, const bsw_pe_opt_t *opt, const bsw_alnreg_t *sel_regs, const bsw_selinfo_t *sel_info,
+                const int32_t *read_first, int32_t n_reads, bsw_pestat_t *pes)
+{
+    (void)sel_info;
+    if (const int rc = bsw::pe_check_args(opt, n_reads, 0)) return rc;
+    if (!ctx || !pes) return BSW_E_INVAL;
+    int32_t n_regs = 0;
+    if (const int rc = bsw::pe_host_first(read_first, n_reads, n_regs)) return rc;
+    if (n_regs > 0 && !sel_regs) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::pe_check_ref(*opt, dc)) return rc;
+    bsw_pe_stats_t ps{};
+    ps.n_pairs = n_reads / 2;
+    bsw::StagedIo io;
+    const auto d_sel_regs = io.in(sel_regs, (size_t)n_regs);
+    const auto d_read_first = io.in(read_first, (size_t)n_reads + 1);
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(io.stage(s));
+        return bsw::pe_stat_device(ctx, s, s.stream, *opt, d_sel_regs, d_read_first, n_reads, n_regs, pes, ps);
+    });
+    if (rc) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::pe_last, ps);
+    return BSW_OK;
+}
+
+int bsw_pe_pair_resident(bsw_ctx_t *ctx, const bsw_pe_opt_t *opt, const bsw_pestat_t *pes, bsw_alnreg_t *d_sel_regs,
+                         bsw_selinfo_t *d_sel_info, const int32_t *d_read_first, int32_t n_reads, int32_t n_regs,
+                         bsw_pair_t *d_pairs, void *stream)
+{
+    if (const int rc = bsw::pe_check_args(opt, n_reads, n_regs)) return rc;
+    if (const int rc = bsw::pe_check_pes(pes)) return rc;
+    if (!ctx || !d_read_first || (n_regs > 0 && (!d_sel_regs || !d_sel_info)) || (n_reads > 0 && !d_pairs))
+        return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::pe_check_ref(*opt, dc)) return rc;
+    bsw_pe_stats_t ps{};
+    ps.n_pairs = n_reads / 2;
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::pe_pair_device(ctx, s, st, *opt, pes, d_sel_regs, d_sel_info, d_read_first, n_reads, n_regs, d_pairs,
+                                   ps);
+    });
+    if (rc) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::pe_last, ps);
+    return BSW_OK;
+}
+
+int bsw_pe_pair(bsw_ctx_t *ctx, const bsw_pe_opt_t *opt, const bsw_pestat_t *pes, bsw_alnreg_t *sel_regs,
+                bsw_selinfo_t *sel_info, const int32_t *read_first, int32_t n_reads, bsw_pair_t *pairs)
+{
+    if (const int rc = bsw::pe_check_args(opt, n_reads, 0)) return rc;
+    if (const int rc = bsw::pe_check_pes(pes)) return rc;
+    if (!ctx || (n_reads > 0 && !pairs)) return BSW_E_INVAL;
+    int32_t n_regs = 0;
+    if (const int rc = bsw::pe_host_first(read_first, n_reads, n_regs)) return rc;
+    if (n_regs > 0 && (!sel_regs || !sel_info)) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (const int rc = bsw::pe_check_ref(*opt, dc)) return rc;
+    bsw_pe_stats_t ps{};
+    ps.n_pairs = n_reads / 2;
+    bsw::StagedIo io;
+    const auto d_sel_regs = io.inout(sel_regs, (size_t)n_regs);     // (marked and re-scored in place)
+    const auto d_sel_info = io.inout(sel_info, (size_t)n_regs);
+    const auto d_read_first = io.in(read_first, (size_t)n_reads + 1);
+    const auto d_pairs = io.out(pairs, (size_t)(n_reads / 2));
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(io.stage(s));
+        if (int r = bsw::pe_pair_device(ctx, s, s.stream, *opt, pes, d_sel_regs, d_sel_info, d_read_first, n_reads, n_regs,
+                                        d_pairs, ps))
+            return r;
+        BSW_TRY(io.back(d_sel_regs));
+        BSW_TRY(io.back(d_sel_info));
+        BSW_TRY(io.back(d_pairs));
+        BSW_TRY(hipStreamSynchronize(s.stream));
+        return BSW_OK;
+    });
+    if (rc) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::pe_last, ps);
+    return BSW_OK;
+}
+
+int bsw_pe_last_stats(bsw_ctx_t *ctx, bsw_pe_stats_t *out) { return bsw::get_stats(ctx, &bsw_ctx::pe_last, out); }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- mate rescue stage (bsw_matesw.h)
+namespace bsw {
+
+// argument checks of both forms, before anything touches a device
+static int matesw_check_args(const bsw_ctx_t *ctx, const bsw_matesw_opt_t *opt, const bsw_pestat_t *pes,
+                             int32_t n_reads, int32_t n_regs, int32_t out_cap)
+{
+    if (!opt || !pes || n_reads < 0 || (n_reads & 1) || n_regs < 0 || out_cap < 0) return BSW_E_INVAL;
+    if (opt->l_pac <= 0 || opt->max_matesw < 0 || opt->min_seed_len <= 0 || opt->max_chain_gap < 0) return BSW_E_INVAL;
+    for (int d = 0; d < 4; ++d)
+        if (!pes[d].failed && pes[d].low > pes[d].high) return BSW_E_INVAL;
+    if (!ctx) return BSW_E_INVAL;
+    return mate_params_ok(ctx->params) ? BSW_OK : BSW_E_INVAL;
+}
+
+struct MswIo {
+    const uint8_t *reads;
+    const int64_t *read_off;
+    const int32_t *read_len;
+    const bsw_alnreg_t *regs;
+    const bsw_selinfo_t *info;
+    const int32_t *first;
+    bsw_alnreg_t *out_regs;
+    int32_t *out_read;
+    bsw_selinfo_t *out_info;
+    int32_t *out_first;
+};
+
+// count + scans -> round 0's step -> per round: one readback of the job count, build, the batched
+// ksw_align2, the next step -> the scan of the list lengths -> emit.  The caller holds dc.refmu shared.
+static int matesw_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st, const bsw_matesw_opt_t &opt,
+                         const bsw_pestat_t *pes, const MswIo &io, int32_t n_reads, int32_t n_regs, int32_t out_cap,
+                         int32_t *n_out, bsw_matesw_stats_t &ws)
+{
+    *n_out = 0;
+    const bsw_params_t &pr = ctx->params;
+    MswParams p;
+    memset(&p, 0, sizeof(p));
+    p.s.a = pr.mat[0];
+    p.s.max_chain_gap = opt.max_chain_gap; p.s.min_seed_len = opt.min_seed_len; p.s.patch = 0;
+    p.s.mask_level_redun = opt.mask_level_redun;
+    p.s.l_pac = opt.l_pac; p.s.n_reads = n_reads;
+    p.n_pairs = n_reads / 2; p.n_regs = n_regs;
+    p.max_matesw = opt.max_matesw; p.pen_unpaired = opt.pen_unpaired;
+    for (int d = 0; d < 4; ++d) {
+        p.pes[d].low = pes[d].low; p.pes[d].high = pes[d].high; p.pes[d].failed = pes[d].failed != 0;
+    }
+    MateParams mp;
+    make_mate_params(pr, mp);
+    if ((int64_t)n_regs * 5 > INT32_MAX) return BSW_E_RANGE;        // the work lists' offsets are int32
+    const size_t nr = (size_t)n_reads, np = nr / 2, n1 = nr + 1;
+    size_t scan_bytes = 0;
+    BSW_TRY(launch_sel_scan(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
+    BSW_TRY(s.d_tmp.grow(std::max<size_t>(scan_bytes, 16)));
+    BSW_TRY(s.d_wint.grow(5 * n1 + 2 * np + 1));
+    BSW_TRY(s.d_wmeta.grow(kMswSlots * kMswMetaWords));
+    BSW_TRY(s.d_wst.grow(std::max<size_t>(np, 1)));
+    BSW_TRY(s.d_wjobs.grow(std::max<size_t>(4 * np, 1)));
+    BSW_TRY(s.d_maln.grow(std::max<size_t>(4 * np, 1)));
+    HelperTimer tm;
+    BSW_TRY(tm.init(s.evw0, s.evw1, st));
+    static_assert(kMswSlots * kMswMetaWords <= kMetaWords, "the slot's pinned mirror holds the stage's counters");
+    int32_t *ncand = s.d_wint, *capv = ncand + n1, *coff = capv + n1, *woff = coff + n1, *nlist = woff + n1;
+    int32_t *lists = nlist + n1;
+    int32_t *h_meta = s.h_meta;
+    constexpr size_t kMetaBytes = kMswSlots * kMswMetaWords * sizeof(int32_t);
+    BSW_TRY(hipMemsetAsync(s.d_wint, 0, (5 * n1) * sizeof(int32_t), st));
+    BSW_TRY(hipMemsetAsync(s.d_wmeta, 0, kMetaBytes, st));
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_msw_count(p, io.regs, io.first, ncand, capv, s.d_wmeta, st));
+    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, ncand, coff, n_reads, st));
+    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, capv, woff, n_reads, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipMemcpyAsync(h_meta, s.d_wmeta, kMswMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_meta + kMswMetaWords, coff + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_meta + kMswMetaWords + 1, woff + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(ws.helper_ms));
+    if (h_meta[kMswErr]) return BSW_E_RANGE;
+    const size_t n_cand = (size_t)h_meta[kMswMetaWords], n_work = (size_t)h_meta[kMswMetaWords + 1];
+    BSW_TRY(s.d_wcand.grow(std::max<size_t>(n_cand, 1)));
+    BSW_TRY(s.d_swork.grow(std::max<size_t>(n_work, 1)));
+    int32_t n_items = p.n_pairs;
+    const int32_t *list = nullptr;
+    for (int round = 0;; ++round) {
+        int32_t *next = lists + (size_t)(round & 1) * np;
+        BSW_TRY(tm.begin());
+        BSW_TRY(launch_msw_step(p, list, n_items, io.regs, io.info, io.first, io.read_len, ncand, coff, woff, s.d_wcand,
+                                s.d_swork, nlist, s.d_wst, s.d_maln, s.d_wjobs, next, s.d_wmeta, st));
+        BSW_TRY(tm.end());
+        BSW_TRY(hipMemcpyAsync(h_meta, s.d_wmeta, kMetaBytes, hipMemcpyDeviceToHost, st));
+        BSW_TRY(hipStreamSynchronize(st));
+        BSW_TRY(tm.add(ws.helper_ms));
+        if (h_meta[kMswErr]) return BSW_E_RANGE;
+        const int32_t nj = h_meta[kMswNJobs];
+        if (nj == 0) break;
+        ++ws.rounds;
+        n_items = h_meta[kMswNext];
+        list = next;
+        p.qstride = std::max(h_meta[kMswMaxQ], 1);
+        p.tstride = std::max(h_meta[kMswMaxT], 1);
+        int32_t chunk;
+        BSW_TRY(dp_job_buffers(s, nj, p.qstride, p.tstride, &chunk));
+        BSW_TRY(hipMemsetAsync(s.d_wmeta + kMswNext, 0, 4 * sizeof(int32_t), st));      // the round's words
+        for (int32_t a = 0; a < nj; a += chunk) {
+            const int32_t b = std::min(nj, a + chunk);
+            BSW_TRY(tm.begin());
+            BSW_TRY(launch_msw_build(p, s.d_wjobs + a, b - a, io.reads, io.read_off, io.read_len, dc.d_refres, s.d_apairs,
+                                     s.d_aq, s.d_at, st));
+            BSW_TRY(tm.end());
+            bsw_mate_stats_t mst;
+            if (int r = mate_device(mp, s, s.d_apairs, s.d_at, s.d_aq, b - a, s.d_maln + a, st, &mst)) return r;
+            ws.sw_ms += mst.fwd_ms + mst.rev_ms;
+            BSW_TRY(tm.add(ws.helper_ms));          // (the batch waited for the stream)
+        }
+    }
+    for (int k = 0; k < kMswSlots; ++k) {
+        const int32_t *m = h_meta + k * kMswMetaWords;
+        ws.n_calls += m[kMswCalls];
+        ws.n_calls_all_skipped += m[kMswAllSkipped];
+        ws.n_jobs += m[kMswJobs];
+        ws.n_jobs_u8 += m[kMswJobsU8];
+        ws.n_short_window += m[kMswShort];
+        ws.n_pushed += m[kMswPushed];
+        ws.n_redundant += m[kMswRedundant];
+        ws.n_identical += m[kMswIdentical];
+        ws.n_lists_changed += m[kMswChanged];
+    }
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, nlist, io.out_first, n_reads, st));
+    BSW_TRY(hipMemcpyAsync(h_meta, io.out_first + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    *n_out = ws.n_out = h_meta[0];
+    if (h_meta[0] > out_cap) return BSW_E_RANGE;
+    BSW_TRY(launch_msw_emit(p, woff, nlist, io.out_first, s.d_swork, io.out_regs, io.out_read, io.out_info, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(ws.helper_ms));
+    return BSW_OK;
+}
+
+}  // namespace bsw
+
+extern "C" {
+
+void bsw_matesw_opt_default(bsw_matesw_opt_t *opt)
+{
+    if (!opt) return;
+    memset(opt, 0, sizeof(*opt));
+    opt->max_matesw = 50;
+    opt->pen_unpaired = 17;
+    opt->min_seed_len = 19;
+    opt->max_chain_gap = 10000;
+    opt->mask_level_redun = 0.95f;
+}
+
+int bsw_matesw_resident(bsw_ctx_t *ctx, const bsw_matesw_opt_t *opt, const bsw_pestat_t *pes,
+                        const uint8_t *d_reads, const int64_t *d_read_off, const int32_t *d_read_len,
+                        int32_t n_reads, const bsw_alnreg_t *d_sel_regs, const bsw_selinfo_t *d_sel_info,
+                        const int32_t *d_read_first, int32_t n_regs, bsw_alnreg_t *d_out_regs,
+                        int32_t *d_out_read, bsw_selinfo_t *d_out_info, int32_t *d_out_first, int32_t out_cap,
+                        int32_t *n_out, void *stream)
+{
+    if (const int rc = bsw::matesw_check_args(ctx, opt, pes, n_reads, n_regs, out_cap)) return rc;
+    if (!n_out || !d_read_first || !d_out_first || (n_reads > 0 && (!d_reads || !d_read_off || !d_read_len)) ||
+        (n_regs > 0 && (!d_sel_regs || !d_sel_info)) || (out_cap > 0 && (!d_out_regs || !d_out_read || !d_out_info)))
+        return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the resident reference stays put
+    if (!bsw::ref_ok(dc, opt->l_pac)) return BSW_E_INVAL;
+    bsw_matesw_stats_t ws{};
+    ws.n_pairs = n_reads / 2;
+    const bsw::MswIo io = {d_reads, d_read_off, d_read_len, d_sel_regs, d_sel_info, d_read_first,
+                           d_out_regs, d_out_read, d_out_info, d_out_first};
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::matesw_device(ctx, dc, s, st, *opt, pes, io, n_reads, n_regs, out_cap, n_out, ws);
+    });
+    if (rc) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::matesw_last, ws);
+    return BSW_OK;
+}
+
+int bsw_matesw(bsw_ctx_t *ctx, const bsw_matesw_opt_t *opt, const bsw_pestat_t *pes, const uint8_t *reads,
+               const int64_t *read_off, const int32_t *read_len, int32_t n_reads, const bsw_alnreg_t *sel_regs,
+               const bsw_selinfo_t *sel_info, const int32_t *read_first, bsw_alnreg_t *out_regs,
+               int32_t *out_read, bsw_selinfo_t *out_info, int32_t *out_first, int32_t out_cap, int32_t *n_out)
+{
+    if (const int rc = bsw::matesw_check_args(ctx, opt, pes, n_reads, 0, out_cap)) return rc;
+    if (!n_out || !out_first || (n_reads > 0 && (!reads || !read_off || !read_len)) ||
+        (out_cap > 0 && (!out_regs || !out_read || !out_info)))
+        return BSW_E_INVAL;
+    int32_t n_regs = 0;
+    if (const int rc = bsw::pe_host_first(read_first, n_reads, n_regs)) return rc;
+    if (n_regs > 0 && (!sel_regs || !sel_info)) return BSW_E_INVAL;
+    int64_t rbytes;
+    if (const int rc = bsw::reads_extent(read_off, read_len, n_reads, &rbytes)) return rc;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (!bsw::ref_ok(dc, opt->l_pac)) return BSW_E_INVAL;
+    bsw_matesw_stats_t ws{};
+    ws.n_pairs = n_reads / 2;
+    const size_t nr = (size_t)n_reads, ng = (size_t)n_regs, nc = (size_t)out_cap;
+    bsw::StagedIo io;
+    const auto d_reads = io.in(reads, (size_t)rbytes);
+    const auto d_read_off = io.in(read_off, nr);
+    const auto d_read_len = io.in(read_len, nr);
+    const auto d_sel_regs = io.in(sel_regs, ng);
+    const auto d_sel_info = io.in(sel_info, ng);
+    const auto d_read_first = io.in(read_first, nr + 1);
+    const auto d_out_regs = io.out(out_regs, nc);
+    const auto d_out_read = io.out(out_read, nc);
+    const auto d_out_info = io.out(out_info, nc);
+    const auto d_out_first = io.out(out_first, nr + 1);
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(io.stage(s));
+        const bsw::MswIo dio = {d_reads, d_read_off, d_read_len, d_sel_regs, d_sel_info, d_read_first,
+                                d_out_regs, d_out_read, d_out_info, d_out_first};
+        const int r = bsw::matesw_device(ctx, dc, s, s.stream, *opt, pes, dio, n_reads, n_regs, out_cap, n_out, ws);
+        if (r == BSW_E_RANGE && *n_out > out_cap) {        // (d_out_first is still written)
+            BSW_TRY(io.back(d_out_first));
+            BSW_TRY(hipStreamSynchronize(s.stream));
+        }
+        if (r) return r;
+        BSW_TRY(io.back(d_out_regs, (size_t)*n_out));  // (the rows emitted, not out_cap of them)
+        BSW_TRY(io.back(d_out_read, (size_t)*n_out));
+        BSW_TRY(io.back(d_out_info, (size_t)*n_out));
+        BSW_TRY(io.back(d_out_first));
+        BSW_TRY(hipStreamSynchronize(s.stream));
+        return BSW_OK;
+    });
+    if (rc) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::matesw_last, ws);
+    return BSW_OK;
+}
+
+int bsw_matesw_last_stats(bsw_ctx_t *ctx, bsw_matesw_stats_t *out)
+{
+    return bsw::get_stats(ctx, &bsw_ctx::matesw_last, out);
+}
+
+}  // extern "C"

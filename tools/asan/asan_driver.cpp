@@ -5,6 +5,8 @@
 //                    (the 2-bit wire form) on random batches packed into exact-size heap buffers,
 //                    decoded and compared, permuted / empty / N-rich batches, extents one below and
 //                    at the 2^30-byte bound, cap < total_bytes and bad records rejected
+//   bsw_internal.h   BlobLayout (the staged blob of the stages' host-array forms): offsets aligned,
+//                    parts disjoint, total and offsets as the recurrence they replace
 //   bsw_batch.c      .bswb write / read round trip, truncated and corrupted files rejected
 //   bsw_synth.c      every generator
 //   bsw_ext.cpp      bsw_extend_seeds (chunked) and bsw_chain2aln through an oracle-backed engine
@@ -271,6 +273,34 @@ static void test_pack_batch()
     }
 }
 
+static void test_blob_layout()
+{
+    const std::vector<std::vector<size_t>> lists = {
+        {}, {0}, {1}, {15}, {16}, {17}, {0, 1, 15, 16, 17}, {17, 0, 1}, {16, 0, 0, 15, 0}, {1, 1, 1, 1},
+        {4096, 33, 0, 7, 160, 0}, {0, 0, 0}, {(size_t)3 << 32, 5, 0, 31}};
+    for (size_t li = 0; li < lists.size(); ++li) {
+        const std::vector<size_t> &part = lists[li];
+        bsw::BlobLayout lay;
+        std::vector<size_t> off;
+        for (size_t b : part) off.push_back(lay.add(b));
+        size_t want = 0;                                // off[k + 1] = off[k] + ((part[k] + 15) & ~15)
+        for (size_t k = 0; k < part.size(); ++k) {
+            CHECK(off[k] == want, "list %zu part %zu: offset %zu, the recurrence gives %zu", li, k, off[k], want);
+            CHECK(off[k] % 16 == 0, "list %zu part %zu: offset %zu not 16-byte aligned", li, k, off[k]);
+            if (k > 0) CHECK(off[k - 1] + part[k - 1] <= off[k], "list %zu: parts %zu and %zu overlap", li, k - 1, k);
+            want += (part[k] + 15) & ~(size_t)15;
+        }
+        CHECK(lay.total == want, "list %zu: total %zu, the recurrence gives %zu", li, lay.total, want);
+        if (!part.empty()) {
+            const size_t padded = (part.back() + 15) / 16 * 16;
+            CHECK(lay.total == off.back() + padded, "list %zu: total %zu != last offset + padded size", li, lay.total);
+            CHECK(off.back() + part.back() <= lay.total, "list %zu: the last part ends past the total", li);
+        } else {
+            CHECK(lay.total == 0, "empty list: total %zu", lay.total);
+        }
+    }
+}
+
 static void test_batch_file()
 {
     bsw_params_t p;
@@ -434,6 +464,7 @@ int main()
 {
     test_pack();
     test_pack_batch();
+    test_blob_layout();
     test_batch_file();
     test_extension_and_synth();
     printf("asan_driver: %s (%d failed checks)\n", g_fail ? "FAIL" : "ok", g_fail);
