@@ -650,6 +650,70 @@ __device__ __forceinline__ int pc_ubscan(std::integer_sequence<int, G...>, const
     return (int)max(ub & 0xffffu, ub >> 16);
 }
 
+// Left skip: groups that lie wholly inside the all-zero left prefix common
+// to the wave's live lanes are dropped from the row's entered set -- computing them rewrites zeros
+// (§3 item 1).  gz is wave-uniform and never decreases; at the start of every row each live lane
+// holds H == 0 and E <= 0 (bytes: E == 0) in every slot s < 4 gz, slot 0 (the column -1 boundary)
+// included.  gz is refreshed at the row end, behind one uniform test, on rows with
+// (i & BSW_PC_SKIP_MASK) == BSW_PC_SKIP_ROW: while group gz is zero in both planes for every lane
+// that stays alive it advances, an unrolled walk over compile-time register indices with uniform
+// skips (segments of 8 groups, then the group), as pc_ubscan and pc_lastpos.
+//   BSW_PC_LEFT_SKIP 0 : off (make ab AB_FLAGS=-DBSW_PC_LEFT_SKIP=0)
+//   BSW_PC_SKIP_QMIN   : the smallest QMAX class that carries the skip (the classes below it would
+//                        pay for gz and the walk with a wave per SIMD)
+#ifndef BSW_PC_LEFT_SKIP
+#define BSW_PC_LEFT_SKIP 1
+#endif
+#ifndef BSW_PC_SKIP_MASK
+#define BSW_PC_SKIP_MASK 3
+#endif
+#ifndef BSW_PC_SKIP_ROW
+#define BSW_PC_SKIP_ROW 1
+#endif
+#ifndef BSW_PC_SKIP_QMIN
+#define BSW_PC_SKIP_QMIN 96
+#endif
+template <int QMAX> constexpr bool pc_left_skip() { return BSW_PC_LEFT_SKIP && QMAX >= BSW_PC_SKIP_QMIN; }
+
+// group G of the walk: taken only when gz == G (uniform); z = the group's H registers or-ed with
+// the positive parts of its E registers (the int16 E plane is unclamped, PC_PH1)
+template <int QMAX, bool BY, int G>
+__device__ __forceinline__ void pc_gz_group(const uint32_t (&hh)[(BY ? QMAX / 4 : QMAX / 2)],
+                                            const uint32_t (&ee)[(BY ? QMAX / 4 : QMAX / 2)], bool live, int &gz)
+{
+    if constexpr (G < QMAX / 4) {
+        if (gz != G) return;
+        uint32_t z;
+        if constexpr (BY) {
+            asm volatile("v_or_b32_e32 %0, %1, %2" : "=v"(z) : "v"(hh[G]), "v"(ee[G]));
+        } else {
+            uint32_t t;
+            asm volatile("v_pk_max_i16 %0, %2, 0\n\t"
+                         "v_pk_max_i16 %1, %3, 0\n\t"
+                         "v_or3_b32 %0, %0, %1, %4\n\t"
+                         "v_or_b32_e32 %0, %0, %5"
+                         : "=&v"(z), "=&v"(t)
+                         : "v"(ee[2 * G]), "v"(ee[2 * G + 1]), "v"(hh[2 * G]), "v"(hh[2 * G + 1]));
+        }
+        if (__ballot(live && z != 0u) == 0) gz = G + 1;
+    }
+}
+
+template <int QMAX, bool BY, int S, int... K>
+__device__ __forceinline__ void pc_gz_seg(std::integer_sequence<int, K...>, const uint32_t (&hh)[(BY ? QMAX / 4 : QMAX / 2)],
+                                          const uint32_t (&ee)[(BY ? QMAX / 4 : QMAX / 2)], bool live, int &gz)
+{
+    if ((gz >> 3) != S) return;                            // uniform
+    (pc_gz_group<QMAX, BY, 8 * S + K>(hh, ee, live, gz), ...);
+}
+
+template <int QMAX, bool BY, int... S>
+__device__ __forceinline__ void pc_gz_refresh(std::integer_sequence<int, S...>, const uint32_t (&hh)[(BY ? QMAX / 4 : QMAX / 2)],
+                                              const uint32_t (&ee)[(BY ? QMAX / 4 : QMAX / 2)], bool live, int &gz)
+{
+    (pc_gz_seg<QMAX, BY, S>(std::make_integer_sequence<int, 8>{}, hh, ee, live, gz), ...);
+}
+
 // WPB waves per workgroup: with 1, a wave's slot (and its LDS) is reused as soon as that wave
 // ends, instead of when the slowest of its block's waves ends.
 template <int QMAX, int WPB, bool BY>
@@ -785,6 +849,8 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
     int emax = 0, emin = 0;                 // (experiment: the row head's state outlives its row)
     PcRow r{0, 0, 0};
 #endif
+    int gz = 0;                             // left skip: groups below gz are all-zero in every live lane
+    (void)gz;
     for (int i = 0;; ++i) {
         const bool act = alive && i < tlen;
         alive = act;
@@ -844,6 +910,11 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
             r.enter = gbits(glo, gsp + 1);
             r.fast = gbits(gfa, gfn);
             r.left = gbits(glo, gln + 1);
+            if constexpr (pc_left_skip<QMAX>()) {   // groups below gz leave the entered set; the FAST
+                const uint64_t keep = ~0ull << gz;  // test comes first in a group, so its set too
+                r.enter &= keep;
+                r.fast &= keep;
+            }
         }
 #if BSW_PC_EXP_HALFHEAD
     row_body:
@@ -929,6 +1000,10 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
 #endif
             }
 #endif
+            if constexpr (pc_left_skip<QMAX>()) {
+                if ((i & BSW_PC_SKIP_MASK) == BSW_PC_SKIP_ROW)
+                    pc_gz_refresh<QMAX, BY>(std::make_integer_sequence<int, (NG + 7) / 8>{}, hh, ee, alive, gz);
+            }
 #ifdef BSW_PC_STATS
             nrows += act;
             nue += act && (emax == emin);  // every live lane has the same band end
