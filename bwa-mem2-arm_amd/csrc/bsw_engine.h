@@ -5,7 +5,8 @@
 //   bsw_pipeline.hip : staging kernels, the chunked host pipeline (host_shard), cross-call coalescing
 //   bsw_host.cpp     : contexts, recovery, mate / global / extension wrappers, options, the core C ABI
 //   bsw_stages.cpp   : the stages behind the extension (final alignments, region selection, the
-//                      paired-end stage, mate rescue), both forms of each, on shared call helpers
+//                      paired-end stage, mate rescue, SAM records), both forms of each, on shared call
+//                      helpers
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -26,6 +27,7 @@
 #include "../../include/bsw_sel.h"
 #include "../../include/bsw_pe.h"
 #include "../../include/bsw_matesw.h"
+#include "../../include/bsw_rec.h"
 #include "bsw_kernels.h"
 #include "bsw_internal.h"
 
@@ -220,6 +222,14 @@ struct BSW_HIDDEN Slot {
     DevBuf<MswSt> d_wst;                // per pair: cursor and pending call
     DevBuf<MswJob> d_wjobs;             // a round's jobs, at most 4 per pair
     DevBuf<int32_t> d_wmeta;            // kMswSlots x kMswMetaWords
+    // record stage (bsw_rec.h); its alignments are reg2aln_device's on the same lease (the final-alignment
+    // buffers above), its scans use d_tmp, its host forms stage in d_aio, its helper kernels are timed with
+    // evw0 / evw1
+    DevBuf<int32_t> d_rcnt;             // nrec, naln, aln_first: n_reads + 1 each
+    DevBuf<bsw_alnreg_t> d_rregs;       // the needed regions, compact
+    DevBuf<int32_t> d_rread;            // their reads
+    DevBuf<int64_t> d_rlen;             // text: the lines' lengths, n_rec + 1
+    DevBuf<int32_t> d_rmeta;            // kRecMetaWords
     bool timed = false;
     hipStream_t run_stream = nullptr;   // stream of the last run_device (finish_stats waits on it)
     bsw_stats_t stats{};
@@ -399,6 +409,7 @@ struct bsw_ctx {
     bsw_sel_stats_t sel_last{};
     bsw_pe_stats_t pe_last{};
     bsw_matesw_stats_t matesw_last{};
+    bsw_rec_stats_t rec_last{};
     struct Pinned { std::mutex mu; bsw::PinnedBuf<uint8_t> b; } pin[2];
     int glob_band = 0;                  // BSW_OPT_GLOB_BAND
     int64_t ext_chunk = 0;              // BSW_OPT_EXT_CHUNK (0: the int32-offset bound)

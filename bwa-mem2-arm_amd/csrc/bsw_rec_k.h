@@ -1,0 +1,68 @@
+// bsw_rec_k.h -- launch interface of the record-stage kernels (bsw_rec.hip, include/bsw_rec.h).
+#pragma once
+#include <stdint.h>
+#include <hip/hip_runtime.h>
+#include "../../include/bsw_rec.h"
+
+namespace bsw {
+
+struct RecParams {
+    int32_t n_reads, n_regs;
+    int32_t T, max_XA_hits, flags;
+    float mask_level;
+    double xa_ratio;                    // (double)opt->XA_drop_ratio
+};
+
+struct RecLists {                       // the lists of one call, either form
+    const bsw_alnreg_t *regs;
+    const bsw_selinfo_t *info;
+    const int32_t *first;
+    const bsw_pair_t *pairs;            // nullptr: single-end
+};
+
+struct RecText {                        // call 2's arrays and options
+    const bsw_rec_t *recs;
+    const int32_t *rec_first;
+    const bsw_aln_t *aln;
+    const uint32_t *cigar;
+    const uint8_t *md;
+    const uint8_t *reads, *names, *quals;
+    const uint8_t *rname;               // opt->rname in device memory (a by-value array would live in scratch)
+    const int64_t *read_off, *name_off;
+    const int32_t *read_len;
+    int32_t n_rec, n_aln, n_reads, n_names, cigar_stride, md_stride, paired, flags, rname_len;
+};
+
+// meta words (one int32 array, zeroed per call); the counters are added once per block
+constexpr int kRecErr = 0, kRecUnmapped = 1, kRecSupp = 2, kRecXa = 3, kRecOverflow = 4, kRecRejected = 5,
+              kRecMetaWords = 16,
+              kRecNameWords = (BSW_REC_MAX_RNAME + 1) / 4;   // opt->rname, behind the meta words
+#ifndef BSW_REC_TEXT_GROUP
+#define BSW_REC_TEXT_GROUP 4            // measured: 4 / 8 / 16 / 32 / 64 lanes (`make abrec AB_FLAGS=-DBSW_REC_TEXT_GROUP=N`)
+#endif
+constexpr int kRecTextGroup = BSW_REC_TEXT_GROUP;       // lanes per record in the write kernel
+constexpr int kRecTextBlock = 256;      // its block: 256 / kRecTextGroup records, consecutive in the text
+static_assert(kRecTextGroup >= 4 && 64 % kRecTextGroup == 0, "a group is lanes of one wave, four of them take the edge bytes");
+
+// One work item per read.  Count pass: nrec[r] and naln[r] (nrec[n_reads] = naln[n_reads] = 0),
+// validation into meta[kRecErr].  Fill pass (rec_first / aln_first = their exclusive scans): the
+// records but for what cross-linking gives, aln_reg, and the needed regions compact in creg /
+// creg_read for the alignment stage.
+hipError_t launch_rec_count(const RecParams &p, const RecLists &l, int32_t *nrec, int32_t *naln, int32_t *meta,
+                            hipStream_t s);
+hipError_t launch_rec_fill(const RecParams &p, const RecLists &l, const int32_t *rec_first, const int32_t *aln_first,
+                           bsw_rec_t *recs, int32_t *aln_reg, bsw_alnreg_t *creg, int32_t *creg_read, hipStream_t s);
+// out[0 .. n] = exclusive scan of in[0 .. n]; tmp == nullptr only sizes *tmp_bytes
+hipError_t launch_rec_scan32(void *tmp, size_t *tmp_bytes, const int32_t *in, int32_t *out, int32_t n, hipStream_t s);
+hipError_t launch_rec_scan64(void *tmp, size_t *tmp_bytes, const int64_t *in, int64_t *out, int32_t n, hipStream_t s);
+// One work item per record and per alignment: cross-linking, TLEN, the printed flag; rejected and
+// overflowing alignments and the stage's counters into meta.
+hipError_t launch_rec_finish(const RecLists &l, const int32_t *rec_first, bsw_rec_t *recs, int32_t n_rec,
+                             const bsw_aln_t *aln, const uint32_t *cigar, int32_t cigar_stride, int32_t n_aln,
+                             int32_t *meta, hipStream_t s);
+// len[i] = the bytes of record i's line (len[n_rec] = 0); validation into meta[kRecErr]
+hipError_t launch_rec_text_len(const RecText &t, int64_t *len, int32_t *meta, hipStream_t s);
+// the lines at text + text_off[i]; text is 4-byte aligned
+hipError_t launch_rec_text_write(const RecText &t, const int64_t *text_off, uint8_t *text, hipStream_t s);
+
+}  // namespace bsw

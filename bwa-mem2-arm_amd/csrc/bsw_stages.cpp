@@ -1,7 +1,8 @@
 // bsw_stages.cpp -- the stages behind the extension, each in a device-resident form and a
 // host-array form behind the C ABI: final alignments (bsw_aln.h), region selection (bsw_sel.h),
-// the paired-end stage (bsw_pe.h) and mate rescue (bsw_matesw.h).  Their kernels are in
-// bsw_aln.hip, bsw_sel.hip, bsw_pe.hip and bsw_matesw.hip; what the calls share is below.
+// the paired-end stage (bsw_pe.h), mate rescue (bsw_matesw.h) and SAM records (bsw_rec.h).  Their
+// kernels are in bsw_aln.hip, bsw_sel.hip, bsw_pe.hip, bsw_matesw.hip and bsw_rec.hip; what the calls
+// share is below.
 // (Layout of the engine: bsw_engine.h.)
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -16,6 +17,7 @@
 #include "bsw_sel_k.h"
 #include "bsw_pe_k.h"
 #include "bsw_matesw_k.h"
+#include "bsw_rec_k.h"
 
 // ---------------------------------------------------------------- shared by the stages
 namespace bsw {
@@ -1090,5 +1092,381 @@ int bsw_matesw_last_stats(bsw_ctx_t *ctx, bsw_matesw_stats_t *out)
 {
     return bsw::get_stats(ctx, &bsw_ctx::matesw_last, out);
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- SAM records (bsw_rec.h)
+namespace bsw {
+
+// the options both calls read, before anything touches a device
+static int rec_check_opt(const bsw_rec_opt_t *opt)
+{
+    if (!opt || (opt->flags & ~(BSW_REC_SOFTCLIP | BSW_REC_NO_MULTI | BSW_REC_KEEP_SUPP_MAPQ))) return BSW_E_INVAL;
+    const size_t l = strnlen(opt->rname, sizeof(opt->rname));
+    return l >= 1 && l <= BSW_REC_MAX_RNAME ? BSW_OK : BSW_E_INVAL;
+}
+
+static int records_check_args(const bsw_rec_opt_t *opt, int32_t n_reads, int32_t n_regs, bool paired,
+                              int32_t cigar_stride, int32_t md_stride, int32_t rec_cap, int32_t aln_cap)
+{
+    if (const int rc = rec_check_opt(opt)) return rc;
+    if (n_reads < 0 || n_regs < 0 || rec_cap < 0 || aln_cap < 0 || (paired && (n_reads & 1))) return BSW_E_INVAL;
+    if (opt->l_pac <= 0 || opt->w < 0 || opt->w > (1 << 28) || opt->max_XA_hits < 0 || !std::isfinite(opt->XA_drop_ratio))
+        return BSW_E_INVAL;
+    return cigar_stride >= 1 && md_stride >= 1 ? BSW_OK : BSW_E_INVAL;
+}
+
+struct RecIo {                          // device pointers of one records call, either form
+    const uint8_t *reads;
+    const int64_t *read_off;
+    const int32_t *read_len;
+    RecLists lists;
+    bsw_rec_t *recs;
+    int32_t *rec_first;
+    bsw_aln_t *aln;
+    int32_t *aln_reg;
+    uint32_t *cigar;
+    uint8_t *md;
+};
+
+// count -> two scans -> one readback of the totals -> fill (records, the needed regions compact) ->
+// reg2aln_device over those on this lease -> finish.  The caller holds dc.refmu shared.
+static int records_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st, const bsw_rec_opt_t &opt,
+                          const RecIo &io, int32_t n_reads, int32_t n_regs, int32_t cigar_stride, int32_t md_stride,
+                          int32_t rec_cap, int32_t aln_cap, int32_t *n_rec, int32_t *n_aln, bsw_rec_stats_t &rs)
+{
+    *n_rec = *n_aln = 0;
+    RecParams p{};
+    p.n_reads = n_reads; p.n_regs = n_regs;
+    p.T = opt.T; p.max_XA_hits = opt.max_XA_hits; p.flags = opt.flags;
+    p.mask_level = opt.mask_level; p.xa_ratio = (double)opt.XA_drop_ratio;
+    const size_t nr = (size_t)n_reads, n1 = nr + 1;
+    size_t scan_bytes = 0;
+    BSW_TRY(launch_rec_scan32(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
+    BSW_TRY(s.d_tmp.grow(std::max<size_t>(scan_bytes, 16)));
+    BSW_TRY(s.d_rcnt.grow(3 * n1));
+    BSW_TRY(s.d_rmeta.grow(kRecMetaWords + kRecNameWords));
+    HelperTimer tm;
+    BSW_TRY(tm.init(s.evw0, s.evw1, st));
+    static_assert(kRecMetaWords + 2 <= kMetaWords, "the slot's pinned mirror holds the stage's counters");
+    int32_t *nrec = s.d_rcnt, *naln = nrec + n1, *aln_first = naln + n1;
+    int32_t *h_meta = s.h_meta;
+    BSW_TRY(hipMemsetAsync(s.d_rmeta, 0, kRecMetaWords * sizeof(int32_t), st));
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_rec_count(p, io.lists, nrec, naln, s.d_rmeta, st));
+    BSW_TRY(launch_rec_scan32(s.d_tmp, &scan_bytes, nrec, io.rec_first, n_reads, st));
+    BSW_TRY(launch_rec_scan32(s.d_tmp, &scan_bytes, naln, aln_first, n_reads, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipMemcpyAsync(h_meta, s.d_rmeta, kRecMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_meta + kRecMetaWords, io.rec_first + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_meta + kRecMetaWords + 1, aln_first + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(rs.helper_ms));
+    if (h_meta[kRecErr]) return BSW_E_RANGE;
+    const int32_t nrc = h_meta[kRecMetaWords], na = h_meta[kRecMetaWords + 1];
+    *n_rec = rs.n_rec = nrc;
+    *n_aln = rs.n_aln = na;
+    if (nrc > rec_cap || na > aln_cap) return BSW_E_RANGE;
+    BSW_TRY(s.d_rregs.grow(std::max<size_t>((size_t)na, 1)));
+    BSW_TRY(s.d_rread.grow(std::max<size_t>((size_t)na, 1)));
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_rec_fill(p, io.lists, io.rec_first, aln_first, io.recs, io.aln_reg, s.d_rregs, s.d_rread, st));
+    BSW_TRY(tm.end());
+    if (na > 0) {
+        bsw_ext_opt_t eo;
+        bsw_ext_opt_default(&eo);
+        eo.w = opt.w; eo.l_pac = opt.l_pac;
+        bsw_aln_stats_t as{};
+        as.n_regs = na;
+        if (int r = reg2aln_device(ctx, dc, s, st, eo, io.reads, io.read_off, io.read_len, n_reads, s.d_rregs, s.d_rread,
+                                   na, io.aln, io.cigar, cigar_stride, io.md, md_stride, as))
+            return r;
+        rs.aln_ms = as.dp_ms + as.helper_ms;    // (bsw_aln_last_stats stays the last bsw_reg2aln* call's)
+    } else {
+        BSW_TRY(hipStreamSynchronize(st));
+    }
+    BSW_TRY(tm.add(rs.helper_ms));
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_rec_finish(io.lists, io.rec_first, io.recs, nrc, io.aln, io.cigar, cigar_stride, na, s.d_rmeta, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipMemcpyAsync(h_meta, s.d_rmeta, kRecMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(rs.helper_ms));
+    rs.n_unmapped = h_meta[kRecUnmapped];
+    rs.n_supp = h_meta[kRecSupp];
+    rs.n_xa = h_meta[kRecXa];
+    rs.n_overflow = h_meta[kRecOverflow];
+    return h_meta[kRecRejected] || h_meta[kRecOverflow] ? BSW_E_RANGE : BSW_OK;
+}
+
+struct TextIo {                         // call 2's outputs
+    uint8_t *text;
+    int64_t *text_off;
+};
+
+static int sam_text_check_args(const bsw_rec_opt_t *opt, int32_t n_rec, int32_t n_aln, int32_t n_reads, int32_t paired,
+                               int32_t cigar_stride, int32_t md_stride, int64_t text_cap)
+{
+    if (const int rc = rec_check_opt(opt)) return rc;
+    if (n_rec < 0 || n_aln < 0 || n_reads < 0 || text_cap < 0 || cigar_stride < 1 || md_stride < 1) return BSW_E_INVAL;
+    return paired && (n_reads & 1) ? BSW_E_INVAL : BSW_OK;
+}
+
+static void make_rec_text(const bsw_rec_opt_t &opt, int32_t n_rec, int32_t n_aln, int32_t n_reads, int32_t paired,
+                          int32_t cigar_stride, int32_t md_stride, RecText &t)
+{
+    t.n_rec = n_rec; t.n_aln = n_aln; t.n_reads = n_reads;
+    t.n_names = paired ? n_reads / 2 : n_reads;
+    t.cigar_stride = cigar_stride; t.md_stride = md_stride;
+    t.paired = paired != 0; t.flags = opt.flags;
+    t.rname_len = (int32_t)strnlen(opt.rname, sizeof(opt.rname));
+}
+
+// lengths -> scan -> one readback of the total -> write
+static int sam_text_device(Slot &s, hipStream_t st, const bsw_rec_opt_t &opt, RecText &t, const TextIo &io,
+                           int64_t text_cap, int64_t *n_bytes, float &text_ms)
+{
+    *n_bytes = 0;
+    size_t scan_bytes = 0;
+    BSW_TRY(launch_rec_scan64(nullptr, &scan_bytes, nullptr, nullptr, t.n_rec, st));
+    BSW_TRY(s.d_tmp.grow(std::max<size_t>(scan_bytes, 16)));
+    BSW_TRY(s.d_rlen.grow((size_t)t.n_rec + 1));
+    BSW_TRY(s.d_rmeta.grow(kRecMetaWords + kRecNameWords));
+    HelperTimer tm;
+    BSW_TRY(tm.init(s.evw0, s.evw1, st));
+    static_assert(2 * kRecMetaWords + kRecNameWords <= kMetaWords, "the slot's pinned mirror holds the name");
+    int64_t *h_tot = (int64_t *)(s.h_meta + kRecMetaWords);
+    int32_t *h_name = s.h_meta + 2 * kRecMetaWords;
+    memcpy(h_name, opt.rname, sizeof(opt.rname));
+    BSW_TRY(hipMemsetAsync(s.d_rmeta, 0, kRecMetaWords * sizeof(int32_t), st));
+    BSW_TRY(hipMemcpyAsync(s.d_rmeta + kRecMetaWords, h_name, sizeof(opt.rname), hipMemcpyHostToDevice, st));
+    t.rname = (const uint8_t *)(s.d_rmeta + kRecMetaWords);
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_rec_text_len(t, s.d_rlen, s.d_rmeta, st));
+    BSW_TRY(launch_rec_scan64(s.d_tmp, &scan_bytes, s.d_rlen, io.text_off, t.n_rec, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipMemcpyAsync(s.h_meta, s.d_rmeta, kRecMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_tot, io.text_off + t.n_rec, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(text_ms));
+    if (s.h_meta[kRecErr]) return BSW_E_RANGE;
+    *n_bytes = *h_tot;
+    if (*n_bytes > text_cap) return BSW_E_RANGE;
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_rec_text_write(t, io.text_off, io.text, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(text_ms));
+    return BSW_OK;
+}
+
+// the text call's counters onto the last stats, whose other fields are the last records call's
+static void put_text_stats(bsw_ctx_t *ctx, int64_t n_bytes, float text_ms)
+{
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    ctx->rec_last.n_bytes = n_bytes;
+    ctx->rec_last.text_ms = text_ms;
+}
+
+}  // namespace bsw
+
+extern "C" {
+
+void bsw_rec_opt_default(bsw_rec_opt_t *opt)
+{
+    if (!opt) return;
+    memset(opt, 0, sizeof(*opt));
+    opt->w = 100;
+    opt->T = 30;
+    opt->max_XA_hits = 5;
+    opt->XA_drop_ratio = 0.8f;
+    opt->mask_level = 0.5f;
+}
+
+int bsw_records_resident(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const uint8_t *d_reads,
+                         const int64_t *d_read_off, const int32_t *d_read_len, int32_t n_reads,
+                         const bsw_alnreg_t *d_sel_regs, const bsw_selinfo_t *d_sel_info,
+                         const int32_t *d_read_first, int32_t n_regs, const bsw_pair_t *d_pairs,
+                         bsw_rec_t *d_recs, int32_t *d_rec_first, int32_t rec_cap, bsw_aln_t *d_aln,
+                         int32_t *d_aln_reg, uint32_t *d_cigar, int32_t cigar_stride, uint8_t *d_md,
+                         int32_t md_stride, int32_t aln_cap, int32_t *n_rec, int32_t *n_aln, void *stream)
+{
+    if (const int rc = bsw::records_check_args(opt, n_reads, n_regs, d_pairs != nullptr, cigar_stride, md_stride, rec_cap,
+                                               aln_cap))
+        return rc;
+    if (!ctx || !n_rec || !n_aln || !d_read_first || !d_rec_first ||
+        (n_reads > 0 && (!d_reads || !d_read_off || !d_read_len)) || (n_regs > 0 && (!d_sel_regs || !d_sel_info)) ||
+        (rec_cap > 0 && !d_recs) || (aln_cap > 0 && (!d_aln || !d_aln_reg || !d_cigar || !d_md)))
+        return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the resident reference stays put
+    if (!bsw::ref_ok(dc, opt->l_pac)) return BSW_E_INVAL;
+    bsw_rec_stats_t rs{};
+    const bsw::RecIo io = {d_reads, d_read_off, d_read_len, {d_sel_regs, d_sel_info, d_read_first, d_pairs},
+                           d_recs, d_rec_first, d_aln, d_aln_reg, d_cigar, d_md};
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::records_device(ctx, dc, s, st, *opt, io, n_reads, n_regs, cigar_stride, md_stride, rec_cap, aln_cap,
+                                   n_rec, n_aln, rs);
+    });
+    if (rc != BSW_OK && !(rc == BSW_E_RANGE && rs.n_overflow)) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::rec_last, rs);        // (a stride overflow leaves its count in the stats)
+    return rc;
+}
+
+int bsw_records(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const uint8_t *reads, const int64_t *read_off,
+                const int32_t *read_len, int32_t n_reads, const bsw_alnreg_t *sel_regs,
+                const bsw_selinfo_t *sel_info, const int32_t *read_first, const bsw_pair_t *pairs,
+                bsw_rec_t *recs, int32_t *rec_first, int32_t rec_cap, bsw_aln_t *aln, int32_t *aln_reg,
+                uint32_t *cigar, int32_t cigar_stride, uint8_t *md, int32_t md_stride, int32_t aln_cap,
+                int32_t *n_rec, int32_t *n_aln)
+{
+    if (const int rc = bsw::records_check_args(opt, n_reads, 0, pairs != nullptr, cigar_stride, md_stride, rec_cap, aln_cap))
+        return rc;
+    if (!ctx || !n_rec || !n_aln || !rec_first || (n_reads > 0 && (!reads || !read_off || !read_len)) ||
+        (rec_cap > 0 && !recs) || (aln_cap > 0 && (!aln || !aln_reg || !cigar || !md)))
+        return BSW_E_INVAL;
+    int32_t n_regs = 0;
+    if (const int rc = bsw::pe_host_first(read_first, n_reads, n_regs)) return rc;
+    if (n_regs > 0 && (!sel_regs || !sel_info)) return BSW_E_INVAL;
+    int64_t rbytes;
+    if (const int rc = bsw::reads_extent(read_off, read_len, n_reads, &rbytes)) return rc;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (!bsw::ref_ok(dc, opt->l_pac)) return BSW_E_INVAL;
+    bsw_rec_stats_t rs{};
+    const size_t nr = (size_t)n_reads, ng = (size_t)n_regs, nc = (size_t)rec_cap, na = (size_t)aln_cap;
+    bsw::StagedIo io;
+    const auto d_reads = io.in(reads, (size_t)rbytes);
+    const auto d_read_off = io.in(read_off, nr);
+    const auto d_read_len = io.in(read_len, nr);
+    const auto d_sel_regs = io.in(sel_regs, ng);
+    const auto d_sel_info = io.in(sel_info, ng);
+    const auto d_read_first = io.in(read_first, nr + 1);
+    const auto d_pairs = io.in_opt(pairs, nr / 2);
+    const auto d_recs = io.out(recs, nc);
+    const auto d_rec_first = io.out(rec_first, nr + 1);
+    const auto d_aln = io.out(aln, na);
+    const auto d_aln_reg = io.out(aln_reg, na);
+    const auto d_cigar = io.out(cigar, na * (size_t)cigar_stride);
+    const auto d_md = io.out(md, na * (size_t)md_stride);
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(io.grow(s));
+        // (what the alignment kernels leave unwritten past a CIGAR or an MD reads back as zeros: cigar and
+        // md, the blob's last two parts)
+        BSW_TRY(hipMemsetAsync(d_cigar, 0, io.bytes_from(d_cigar), s.stream));
+        BSW_TRY(io.upload());
+        const bsw::RecIo dio = {d_reads, d_read_off, d_read_len, {d_sel_regs, d_sel_info, d_read_first, d_pairs},
+                                d_recs, d_rec_first, d_aln, d_aln_reg, d_cigar, d_md};
+        const int r = bsw::records_device(ctx, dc, s, s.stream, *opt, dio, n_reads, n_regs, cigar_stride, md_stride,
+                                          rec_cap, aln_cap, n_rec, n_aln, rs);
+        if (r == BSW_E_RANGE && (*n_rec > rec_cap || *n_aln > aln_cap)) {   // (d_rec_first is still written)
+            BSW_TRY(io.back(d_rec_first));
+            BSW_TRY(hipStreamSynchronize(s.stream));
+        }
+        if (r) return r;
+        BSW_TRY(io.back(d_recs, (size_t)*n_rec));           // (the rows written, not the capacities)
+        BSW_TRY(io.back(d_rec_first));
+        BSW_TRY(io.back(d_aln, (size_t)*n_aln));
+        BSW_TRY(io.back(d_aln_reg, (size_t)*n_aln));
+        BSW_TRY(io.back(d_cigar, (size_t)*n_aln * (size_t)cigar_stride));
+        BSW_TRY(io.back(d_md, (size_t)*n_aln * (size_t)md_stride));
+        BSW_TRY(hipStreamSynchronize(s.stream));
+        return BSW_OK;
+    });
+    if (rc != BSW_OK && !(rc == BSW_E_RANGE && rs.n_overflow)) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::rec_last, rs);
+    return rc;
+}
+
+int bsw_sam_text_resident(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *d_recs,
+                          const int32_t *d_rec_first, int32_t n_rec, const bsw_aln_t *d_aln,
+                          const uint32_t *d_cigar, int32_t cigar_stride, const uint8_t *d_md, int32_t md_stride,
+                          int32_t n_aln, const uint8_t *d_reads, const int64_t *d_read_off,
+                          const int32_t *d_read_len, int32_t n_reads, const uint8_t *d_names,
+                          const int64_t *d_name_off, const uint8_t *d_quals, int32_t paired, uint8_t *d_text,
+                          int64_t *d_text_off, int64_t text_cap, int64_t *n_bytes, void *stream)
+{
+    if (const int rc = bsw::sam_text_check_args(opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, text_cap))
+        return rc;
+    if (!ctx || !n_bytes || !d_text_off || !d_name_off || (n_rec > 0 && (!d_recs || !d_rec_first)) ||
+        (n_aln > 0 && (!d_aln || !d_cigar || !d_md)) || (n_reads > 0 && (!d_reads || !d_read_off || !d_read_len || !d_names)) ||
+        (text_cap > 0 && !d_text) || ((uintptr_t)d_text & 3))
+        return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    bsw::RecText t{};
+    t.recs = d_recs; t.rec_first = d_rec_first; t.aln = d_aln; t.cigar = d_cigar; t.md = d_md;
+    t.reads = d_reads; t.names = d_names; t.quals = d_quals;
+    t.read_off = d_read_off; t.name_off = d_name_off; t.read_len = d_read_len;
+    bsw::make_rec_text(*opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, t);
+    float text_ms = 0.f;
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::sam_text_device(s, st, *opt, t, {d_text, d_text_off}, text_cap, n_bytes, text_ms);
+    });
+    if (rc) return rc;
+    bsw::put_text_stats(ctx, *n_bytes, text_ms);
+    return BSW_OK;
+}
+
+int bsw_sam_text(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *recs, const int32_t *rec_first,
+                 int32_t n_rec, const bsw_aln_t *aln, const uint32_t *cigar, int32_t cigar_stride,
+                 const uint8_t *md, int32_t md_stride, int32_t n_aln, const uint8_t *reads,
+                 const int64_t *read_off, const int32_t *read_len, int32_t n_reads, const uint8_t *names,
+                 const int64_t *name_off, const uint8_t *quals, int32_t paired, uint8_t *text, int64_t *text_off,
+                 int64_t text_cap, int64_t *n_bytes)
+{
+    if (const int rc = bsw::sam_text_check_args(opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, text_cap))
+        return rc;
+    if (!ctx || !n_bytes || !text_off || !name_off || (n_rec > 0 && (!recs || !rec_first)) ||
+        (n_aln > 0 && (!aln || !cigar || !md)) || (n_reads > 0 && (!reads || !read_off || !read_len || !names)) ||
+        (text_cap > 0 && !text))
+        return BSW_E_INVAL;
+    int64_t rbytes;
+    if (const int rc = bsw::reads_extent(read_off, read_len, n_reads, &rbytes)) return rc;
+    const size_t nn = (size_t)(paired ? n_reads / 2 : n_reads);
+    for (size_t i = 0; i < nn; ++i)
+        if (name_off[i] < 0 || name_off[i + 1] < name_off[i]) return BSW_E_RANGE;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    const size_t nr = (size_t)n_reads, nc = (size_t)n_rec, na = (size_t)n_aln;
+    bsw::StagedIo io;
+    const auto d_recs = io.in(recs, nc);
+    const auto d_rec_first = io.in(rec_first, n_rec > 0 ? nr + 1 : 0);
+    const auto d_aln = io.in(aln, na);
+    const auto d_cigar = io.in(cigar, na * (size_t)cigar_stride);
+    const auto d_md = io.in(md, na * (size_t)md_stride);
+    const auto d_reads = io.in(reads, (size_t)rbytes);
+    const auto d_read_off = io.in(read_off, nr);
+    const auto d_read_len = io.in(read_len, nr);
+    const auto d_names = io.in(names, (size_t)name_off[nn]);
+    const auto d_name_off = io.in(name_off, nn + 1);
+    const auto d_quals = io.in_opt(quals, (size_t)rbytes);
+    const auto d_text = io.out(text, (size_t)text_cap);
+    const auto d_text_off = io.out(text_off, nc + 1);
+    bsw::RecText t{};
+    bsw::make_rec_text(*opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, t);
+    float text_ms = 0.f;
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(io.stage(s));
+        t.recs = d_recs; t.rec_first = d_rec_first; t.aln = d_aln; t.cigar = d_cigar; t.md = d_md;
+        t.reads = d_reads; t.names = d_names; t.quals = d_quals;
+        t.read_off = d_read_off; t.name_off = d_name_off; t.read_len = d_read_len;
+        const int r = bsw::sam_text_device(s, s.stream, *opt, t, {d_text, d_text_off}, text_cap, n_bytes, text_ms);
+        if (r == BSW_E_RANGE && *n_bytes > text_cap) {     // (d_text_off is still written)
+            BSW_TRY(io.back(d_text_off));
+            BSW_TRY(hipStreamSynchronize(s.stream));
+        }
+        if (r) return r;
+        BSW_TRY(io.back(d_text, (size_t)*n_bytes));
+        BSW_TRY(io.back(d_text_off));
+        BSW_TRY(hipStreamSynchronize(s.stream));
+        return BSW_OK;
+    });
+    if (rc) return rc;
+    bsw::put_text_stats(ctx, *n_bytes, text_ms);
+    return BSW_OK;
+}
+
+int bsw_rec_last_stats(bsw_ctx_t *ctx, bsw_rec_stats_t *out) { return bsw::get_stats(ctx, &bsw_ctx::rec_last, out); }
 
 }  // extern "C"

@@ -48,6 +48,9 @@ PE_SYMBOLS = ("bsw_pe_opt_default", "bsw_pe_stat", "bsw_pe_stat_resident", "bsw_
               "bsw_pe_last_stats")
 # include/bsw_matesw.h (additive to ABI 8: BSW_MATESW_API)
 MATESW_SYMBOLS = ("bsw_matesw_opt_default", "bsw_matesw", "bsw_matesw_resident", "bsw_matesw_last_stats")
+# include/bsw_rec.h (additive to ABI 8: BSW_REC_API)
+REC_SYMBOLS = ("bsw_rec_opt_default", "bsw_records", "bsw_records_resident", "bsw_sam_text", "bsw_sam_text_resident",
+               "bsw_rec_last_stats")
 
 # include/bsw.h engine options (bsw_set_option)
 OPT_KERNEL8, OPT_FORK, OPT_SORTKEY, OPT_GLOB_BAND, OPT_EXT_CHUNK, OPT_HOST_CHUNK, OPT_LONG, OPT_HOST_PACK = 1, 2, 3, 4, 5, 6, 7, 8
@@ -87,6 +90,14 @@ PAIR_DTYPE = np.dtype([("paired", np.int32), ("z", np.int32, (2,)), ("mapq", np.
                        ("score", np.int32), ("sub", np.int32), ("n_sub", np.int32), ("q_pe", np.int32)])
 assert PESTAT_DTYPE.itemsize == 32 and PAIR_DTYPE.itemsize == 40
 PE_MAX_INS = 1 << 16
+# include/bsw_rec.h
+REC_DTYPE = np.dtype([("pos", np.int64), ("mpos", np.int64), ("tlen", np.int64), ("read", np.int32), ("reg", np.int32),
+                      ("aln", np.int32), ("which", np.int32), ("n_list", np.int32), ("flag", np.int32),
+                      ("sam_flag", np.int32), ("is_rev", np.int32), ("mapq", np.int32), ("score", np.int32),
+                      ("sub", np.int32), ("m_is_rev", np.int32), ("m_aln", np.int32), ("xa_first", np.int32),
+                      ("xa_n", np.int32), ("reserved", np.int32)])
+assert REC_DTYPE.itemsize == 88
+REC_SOFTCLIP, REC_NO_MULTI, REC_KEEP_SUPP_MAPQ = 1, 2, 4
 
 # include/bsw_mate.h
 KSW_XBYTE, KSW_XSTOP, KSW_XSUBO, KSW_XSTART = 0x10000, 0x20000, 0x40000, 0x80000
@@ -224,6 +235,17 @@ def hip_lib():
                                           ctypes.c_int32, P, P]
         L.bsw_matesw_last_stats.argtypes = [P, P]
         for f in MATESW_SYMBOLS[1:]:
+            getattr(L, f).restype = ctypes.c_int
+        i32, i64 = ctypes.c_int32, ctypes.c_int64
+        L.bsw_rec_opt_default.argtypes = [P]
+        L.bsw_rec_opt_default.restype = None
+        L.bsw_records.argtypes = [P, P, P, P, P, i32, P, P, P, P, P, P, i32, P, P, P, i32, P, i32, i32, P, P]
+        L.bsw_records_resident.argtypes = [P, P, P, P, P, i32, P, P, P, i32, P, P, P, i32, P, P, P, i32, P, i32, i32, P, P,
+                                           P]
+        L.bsw_sam_text.argtypes = [P, P, P, P, i32, P, P, i32, P, i32, i32, P, P, P, i32, P, P, P, i32, P, P, i64, P]
+        L.bsw_sam_text_resident.argtypes = L.bsw_sam_text.argtypes + [P]
+        L.bsw_rec_last_stats.argtypes = [P, P]
+        for f in REC_SYMBOLS[1:]:
             getattr(L, f).restype = ctypes.c_int
         L.bsw_get_scores_packed_device.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int, P, P]
         for f in ("bsw_create", "bsw_create_on", "bsw_get_scores", "bsw_get_scores_device", "bsw_last_stats",
@@ -1006,6 +1028,159 @@ def matesw_resident(engine, pes, d_reads: int, d_off: int, d_len: int, n_reads: 
 def matesw_last_stats(engine) -> MateswStats:
     st = MateswStats()
     _check(hip_lib().bsw_matesw_last_stats(engine._ctx, ctypes.byref(st)))
+    return st
+
+
+# ---------------------------------------------------------------- SAM records (bsw_rec.h)
+class RecOpt(ctypes.Structure):
+    """Mirror of bsw_rec_opt_t (include/bsw_rec.h)."""
+    _fields_ = [("l_pac", ctypes.c_int64), ("w", ctypes.c_int32), ("T", ctypes.c_int32), ("max_XA_hits", ctypes.c_int32),
+                ("XA_drop_ratio", ctypes.c_float), ("mask_level", ctypes.c_float), ("flags", ctypes.c_int32),
+                ("rname", ctypes.c_char * 64)]
+
+
+class RecStats(ctypes.Structure):
+    _fields_ = [("n_rec", ctypes.c_int32), ("n_unmapped", ctypes.c_int32), ("n_supp", ctypes.c_int32),
+                ("n_xa", ctypes.c_int32), ("n_aln", ctypes.c_int32), ("n_overflow", ctypes.c_int32),
+                ("n_bytes", ctypes.c_int64), ("aln_ms", ctypes.c_float), ("helper_ms", ctypes.c_float),
+                ("text_ms", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+def rec_opt(**kw) -> RecOpt:
+    o = RecOpt()
+    hip_lib().bsw_rec_opt_default(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v.encode() if isinstance(v, str) else v)
+    return o
+
+
+def _raise_rec(rc, n_rec, n_aln, rec_first=None):
+    try:
+        _check(rc)
+    except BswError as e:
+        e.needed = (n_rec.value, n_aln.value)
+        e.rec_first = rec_first
+        raise
+
+
+def records(engine, reads, read_off, read_len, sel_regs, sel_info, read_first, pairs, opt: RecOpt, cigar_stride: int = 16,
+            md_stride: int = 64, rec_cap: int | None = None, aln_cap: int | None = None):
+    """bsw_records (host arrays, resident reference required): the lists bsw_pe_pair (with its pairs) or
+    bsw_regs_select (pairs=None) left -> (recs REC_DTYPE, rec_first int32 [n_reads + 1], aln ALN_DTYPE, aln_reg
+    int32, cigar [n_aln, cigar_stride] uint32, md [n_aln, md_stride] uint8).  A capacity below what is needed
+    raises BswError with .needed = (n_rec, n_aln) and .rec_first set."""
+    sel_regs, sel_info, read_first = _pe_host(sel_regs, sel_info, read_first)
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+    read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+    pairs = None if pairs is None else np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+    n_reads = len(read_first) - 1
+    assert len(read_off) == len(read_len) == n_reads and (pairs is None or len(pairs) == n_reads // 2)
+    rc_ = n_reads + len(sel_regs) if rec_cap is None else rec_cap
+    ac = len(sel_regs) if aln_cap is None else aln_cap
+    recs = np.zeros(max(rc_, 1), dtype=REC_DTYPE)
+    first = np.zeros(n_reads + 1, dtype=np.int32)
+    aln = np.zeros(max(ac, 1), dtype=ALN_DTYPE)
+    aln_reg = np.zeros(max(ac, 1), dtype=np.int32)
+    cig = np.zeros((max(ac, 1), cigar_stride), dtype=np.uint32)
+    md = np.zeros((max(ac, 1), max(md_stride, 1)), dtype=np.uint8)
+    n_rec, n_aln = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    rc = hip_lib().bsw_records(engine._ctx, ctypes.byref(opt), _ptr(reads), _ptr(read_off), _ptr(read_len), n_reads,
+                               _ptr(sel_regs), _ptr(sel_info), _ptr(read_first), _ptr(pairs) if pairs is not None else None,
+                               _ptr(recs), _ptr(first), rc_, _ptr(aln), _ptr(aln_reg), _ptr(cig), cigar_stride, _ptr(md),
+                               md_stride, ac, ctypes.byref(n_rec), ctypes.byref(n_aln))
+    if rc != 0:
+        _raise_rec(rc, n_rec, n_aln, first)
+    k, m = n_rec.value, n_aln.value
+    return recs[:k], first, aln[:m], aln_reg[:m], cig[:m], md[:m]
+
+
+def records_resident(engine, d_reads: int, d_off: int, d_len: int, n_reads: int, d_sel_regs: int, d_sel_info: int,
+                     d_read_first: int, n_regs: int, d_pairs: int, d_recs: int, d_rec_first: int, rec_cap: int,
+                     d_aln: int, d_aln_reg: int, d_cigar: int, cigar_stride: int, d_md: int, md_stride: int,
+                     aln_cap: int, opt: RecOpt, stream: int = 0):
+    """bsw_records_resident: every array a device pointer (the inputs as bsw_pe_pair_resident or
+    bsw_regs_select_resident left them; d_pairs = 0 for single-end).  Returns (n_rec, n_aln)."""
+    V = ctypes.c_void_p
+    n_rec, n_aln = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    rc = hip_lib().bsw_records_resident(engine._ctx, ctypes.byref(opt), V(d_reads or None), V(d_off or None),
+                                        V(d_len or None), n_reads, V(d_sel_regs or None), V(d_sel_info or None),
+                                        V(d_read_first), n_regs, V(d_pairs or None), V(d_recs or None), V(d_rec_first),
+                                        rec_cap, V(d_aln or None), V(d_aln_reg or None), V(d_cigar or None), cigar_stride,
+                                        V(d_md or None), md_stride, aln_cap, ctypes.byref(n_rec), ctypes.byref(n_aln),
+                                        V(stream or None))
+    if rc != 0:
+        _raise_rec(rc, n_rec, n_aln)
+    return n_rec.value, n_aln.value
+
+
+def _names_host(names):
+    """list of bytes -> (bytes uint8, offsets int64 [n + 1])"""
+    off = np.zeros(len(names) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(x) for x in names])
+    flat = np.frombuffer(b"".join(names), dtype=np.uint8).copy() if len(names) else np.zeros(0, np.uint8)
+    return np.ascontiguousarray(flat if len(flat) else np.zeros(1, np.uint8)), off
+
+
+def sam_text(engine, recs, rec_first, aln, cigar, md, reads, read_off, read_len, names, quals, opt: RecOpt,
+             paired: bool, text_cap: int | None = None):
+    """bsw_sam_text (host arrays): bsw_records' outputs, the reads, names (a list of bytes, one per read or per
+    pair) and quals (uint8 parallel to reads, or None) -> (text bytes, text_off int64 [n_rec + 1]).  A text_cap
+    below what is needed raises BswError with .needed set."""
+    recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+    rec_first = np.ascontiguousarray(rec_first, dtype=np.int32)
+    aln = np.ascontiguousarray(aln, dtype=ALN_DTYPE)
+    cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+    md = np.ascontiguousarray(md, dtype=np.uint8)
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+    read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+    quals = None if quals is None else np.ascontiguousarray(quals, dtype=np.uint8)
+    nm, nm_off = _names_host(names)
+    n_reads = len(read_len)
+    assert len(names) == (n_reads // 2 if paired else n_reads) and (quals is None or len(quals) == len(reads))
+    cs = cigar.shape[1] if cigar.ndim == 2 else 1
+    ms = md.shape[1] if md.ndim == 2 else 1
+    if text_cap is None:        # a bound on any line: the name, the fixed fields, SEQ + QUAL, MD, and 12 bytes per CIGAR op printed
+        per = 256 + 160 + 2 * int(read_len.max(initial=0)) + ms + 12 * cs * 16
+        text_cap = per * max(len(recs), 1)
+    text = np.zeros(max(text_cap, 1), dtype=np.uint8)
+    text_off = np.zeros(len(recs) + 1, dtype=np.int64)
+    n_bytes = ctypes.c_int64(-1)
+    rc = hip_lib().bsw_sam_text(engine._ctx, ctypes.byref(opt), _ptr(recs), _ptr(rec_first), len(recs), _ptr(aln),
+                                _ptr(cigar), cs, _ptr(md), ms, len(aln), _ptr(reads), _ptr(read_off), _ptr(read_len),
+                                n_reads, _ptr(nm), _ptr(nm_off), _ptr(quals) if quals is not None else None, int(paired),
+                                _ptr(text), _ptr(text_off), text_cap, ctypes.byref(n_bytes))
+    if rc != 0:
+        try:
+            _raise_needed(rc, n_bytes)
+        except BswError as e:
+            e.text_off = text_off
+            raise
+    return text[:n_bytes.value].tobytes(), text_off
+
+
+def sam_text_resident(engine, d_recs: int, d_rec_first: int, n_rec: int, d_aln: int, d_cigar: int, cigar_stride: int,
+                      d_md: int, md_stride: int, n_aln: int, d_reads: int, d_off: int, d_len: int, n_reads: int,
+                      d_names: int, d_name_off: int, d_quals: int, paired: bool, d_text: int, d_text_off: int,
+                      text_cap: int, opt: RecOpt, stream: int = 0) -> int:
+    """bsw_sam_text_resident: every array a device pointer.  Returns n_bytes."""
+    V = ctypes.c_void_p
+    n_bytes = ctypes.c_int64(-1)
+    rc = hip_lib().bsw_sam_text_resident(engine._ctx, ctypes.byref(opt), V(d_recs or None), V(d_rec_first or None), n_rec,
+                                         V(d_aln or None), V(d_cigar or None), cigar_stride, V(d_md or None), md_stride,
+                                         n_aln, V(d_reads or None), V(d_off or None), V(d_len or None), n_reads,
+                                         V(d_names or None), V(d_name_off), V(d_quals or None), int(paired),
+                                         V(d_text or None), V(d_text_off), text_cap, ctypes.byref(n_bytes),
+                                         V(stream or None))
+    if rc != 0:
+        _raise_needed(rc, n_bytes)
+    return n_bytes.value
+
+
+def rec_last_stats(engine) -> RecStats:
+    st = RecStats()
+    _check(hip_lib().bsw_rec_last_stats(engine._ctx, ctypes.byref(st)))
     return st
 
 

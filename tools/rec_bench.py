@@ -1,0 +1,180 @@
+#!/usr/bin/env python3
+"""The record stage (include/bsw_rec.h) on paired reads in the style of bench.py::pe_reads: --pairs
+fragments (2 x 150 bp, insert 400-600) against a --ref-mb reference, taken through the resident front
+end (bsw_mem_collect_intv_device -> bsw_mem_chain_device -> bsw_chain2aln_resident).  Legs alternating
+in one process, --reps times each:
+  (a) bsw_regs_select_resident   -- the yardstick of the helper kernels (it also renews the arrays the
+                                    pair call updates in place); then stat and pair, untimed
+  (b) bsw_reg2aln_resident over ALL of the reads' regions -- the only route to the records' CIGARs
+                                    without this stage
+  (c) bsw_records_resident       -- aln_ms beside (b), helper_ms beside (a)
+  (d) bsw_sam_text_resident      -- its kernels' bytes/s
+  (e) a device-to-device hipMemcpy of the same byte count
+Prints one JSON line (and writes it to --out).  --only-new: just (c) and (d) (for a kernel trace).
+
+    python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 7 --out profiles/rec/bench.json
+"""
+
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "bwa-mem2-arm_amd", "py"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, ROOT)
+import bsw  # noqa: E402
+import hiprt  # noqa: E402
+from bench import pe_reads  # noqa: E402
+from reg2aln_bench import spread  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=1_000_000)
+    ap.add_argument("--read-len", type=int, default=150)
+    ap.add_argument("--ref-mb", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--w", type=int, default=100)
+    ap.add_argument("--only-new", action="store_true")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    log = lambda m: print(f"[rec_bench] {m}", file=sys.stderr, flush=True)  # noqa: E731
+    ref = bsw.synth_reference(args.ref_mb * 1_000_000, seed=7)
+    nb = ref > 3
+    ref[nb] = np.random.default_rng(1).integers(0, 4, int(nb.sum()), dtype=np.uint8)
+    reads, off, lens = pe_reads(ref, args.pairs, args.read_len, seed=42)
+    n = len(lens)
+    T = np.concatenate([ref, (3 - ref[::-1])]).astype(np.uint8)
+    l_pac = len(ref)
+    t0 = time.perf_counter()
+    fmi = bsw.Fmi(ref)
+    log(f"index of {len(ref)} bases built in {time.perf_counter() - t0:.1f} s")
+    eng = bsw.Engine()
+    bsw.set_reference(eng, T)
+    opt = bsw.ext_opt(w=args.w, l_pac=l_pac)
+    sopt = bsw.sel_opt(w=args.w, l_pac=l_pac)
+    popt = bsw.pe_opt(l_pac=l_pac)
+    ropt = bsw.rec_opt(w=args.w, l_pac=l_pac, rname="chrS")
+    d_reads = hiprt.DeviceBuffer.from_array(reads)
+    d_quals = hiprt.DeviceBuffer.from_array((33 + (np.arange(len(reads)) * 7) % 41).astype(np.uint8))
+    names = [b"frag%08d" % i for i in range(n // 2)]
+    nm, nm_off = bsw._names_host(names)
+    d_nm, d_nmo = hiprt.DeviceBuffer.from_array(nm), hiprt.DeviceBuffer.from_array(nm_off)
+    (_, sr, _), (d_seeds, d_sr, d_sc), (d_off, d_len) = bsw.seed_and_chain(fmi, d_reads, off, lens)
+    ns = len(sr)
+    d_regs, d_ext = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(ns * 4)
+    bsw.chain2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr, ns, d_regs.ptr,
+                           d_ext.ptr, opt)
+    log(f"{n} reads -> {ns} region slots (skipped seeds included)")
+    d_sreg, d_srd = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(ns * 4)
+    d_info, d_first = hiprt.DeviceBuffer(ns * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((n + 1) * 4)
+    d_pairs = hiprt.DeviceBuffer((n // 2) * bsw.PAIR_DTYPE.itemsize)
+    cs, ms = 16, 64
+    state = {}
+
+    def select():
+        state["k"] = bsw.regs_select_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr,
+                                              d_regs.ptr, d_ext.ptr, ns, d_sreg.ptr, d_srd.ptr, d_info.ptr, d_first.ptr,
+                                              ns, sopt)
+
+    def stat_pair():
+        pes = bsw.pe_stat_resident(eng, d_sreg.ptr, d_info.ptr, d_first.ptr, n, state["k"], popt)
+        bsw.pe_pair_resident(eng, pes, d_sreg.ptr, d_info.ptr, d_first.ptr, n, state["k"], d_pairs.ptr, popt)
+
+    select()
+    stat_pair()
+    k = state["k"]
+    rc, ac = n + k, k
+    d_aln, d_cig, d_md = hiprt.DeviceBuffer(ac * 40), hiprt.DeviceBuffer(ac * cs * 4), hiprt.DeviceBuffer(ac * ms)
+    d_recs, d_rfirst, d_areg = hiprt.DeviceBuffer(rc * 88), hiprt.DeviceBuffer((n + 1) * 4), hiprt.DeviceBuffer(ac * 4)
+    # (b) writes arrays of its own: the records' alignments stay what (c) left for (d)
+    b_aln, b_cig, b_md = hiprt.DeviceBuffer(ac * 40), hiprt.DeviceBuffer(ac * cs * 4), hiprt.DeviceBuffer(ac * ms)
+
+    def all_regions():
+        bsw.reg2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_sreg.ptr, d_srd.ptr, k, b_aln.ptr, b_cig.ptr, cs,
+                             b_md.ptr, ms, opt)
+
+    def records():
+        state["n"] = bsw.records_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_sreg.ptr, d_info.ptr, d_first.ptr, k,
+                                          d_pairs.ptr, d_recs.ptr, d_rfirst.ptr, rc, d_aln.ptr, d_areg.ptr, d_cig.ptr, cs,
+                                          d_md.ptr, ms, ac, ropt)
+
+    records()                                                # warm-up, and the size of the text
+    n_rec, n_aln = state["n"]
+    d_toff = hiprt.DeviceBuffer((n_rec + 1) * 8)
+    try:
+        bsw.sam_text_resident(eng, d_recs.ptr, d_rfirst.ptr, n_rec, d_aln.ptr, d_cig.ptr, cs, d_md.ptr, ms, n_aln,
+                              d_reads.ptr, d_off.ptr, d_len.ptr, n, d_nm.ptr, d_nmo.ptr, d_quals.ptr, True, 0, d_toff.ptr,
+                              0, ropt)
+        n_bytes = 0
+    except bsw.BswError as e:
+        n_bytes = e.needed
+    d_text, d_copy = hiprt.DeviceBuffer(n_bytes), hiprt.DeviceBuffer(n_bytes)
+
+    def text():
+        return bsw.sam_text_resident(eng, d_recs.ptr, d_rfirst.ptr, n_rec, d_aln.ptr, d_cig.ptr, cs, d_md.ptr, ms, n_aln,
+                                     d_reads.ptr, d_off.ptr, d_len.ptr, n, d_nm.ptr, d_nmo.ptr, d_quals.ptr, True,
+                                     d_text.ptr, d_toff.ptr, n_bytes, ropt)
+
+    def copy():
+        hiprt.check(hiprt.rt().hipMemcpy(ctypes.c_void_p(d_copy.ptr), ctypes.c_void_p(d_text.ptr), n_bytes, hiprt.D2D))
+        hiprt.synchronize()
+
+    def timed(f):
+        t = time.perf_counter()
+        f()
+        return time.perf_counter() - t
+
+    all_regions()
+    text()
+    copy()
+    ta, tb, tc, td, te, b_ms, c_aln, c_help, d_ms = [], [], [], [], [], [], [], [], []
+    for _ in range(args.reps):
+        if args.only_new:
+            select()
+        else:
+            ta.append(timed(select))
+        stat_pair()
+        if not args.only_new:
+            tb.append(timed(all_regions))
+            a = bsw.aln_last_stats(eng)
+            b_ms.append(a.dp_ms + a.helper_ms)
+        tc.append(timed(records))
+        st = bsw.rec_last_stats(eng)
+        c_aln.append(st.aln_ms)
+        c_help.append(st.helper_ms)
+        td.append(timed(text))
+        d_ms.append(bsw.rec_last_stats(eng).text_ms)
+        if not args.only_new:
+            te.append(timed(copy))
+    st = bsw.rec_last_stats(eng)
+    out = {"tool": "rec_bench", "pairs": n // 2, "reads": n, "read_len": args.read_len, "ref_mb": args.ref_mb,
+           "regions": int(k), "records": st.n_rec, "unmapped": st.n_unmapped, "supplementary": st.n_supp, "xa_members": st.n_xa,
+           "regions_aligned": st.n_aln, "text_bytes": int(n_bytes), "bytes_per_record": round(n_bytes / max(st.n_rec, 1), 1),
+           "c_records_s": spread(tc), "c_records_aln_ms": spread(c_aln), "c_records_helper_ms": spread(c_help),
+           "d_text_s": spread(td), "d_text_kernel_ms": spread(d_ms),
+           "d_text_kernels_gb_per_s": round(n_bytes / (spread(d_ms)["median"] * 1e-3) / 1e9, 1)}
+    if not args.only_new:
+        out.update({"a_regs_select_s": spread(ta), "b_reg2aln_all_regions_s": spread(tb),
+                    "b_reg2aln_all_regions_kernel_ms": spread(b_ms), "e_memcpy_d2d_s": spread(te),
+                    "e_memcpy_d2d_gb_per_s": round(n_bytes / spread(te)["median"] / 1e9, 1),
+                    "c_helper_over_a_median": round(spread(c_help)["median"] * 1e-3 / spread(ta)["median"], 3),
+                    "c_aln_over_b_median": round(spread(c_aln)["median"] / spread(b_ms)["median"], 3)})
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    eng.close()
+    fmi.close()
+
+
+if __name__ == "__main__":
+    main()
