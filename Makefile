@@ -16,10 +16,10 @@ SYNTH    := $(LIBDIR)/libbsw_synth.so
 SHIMTEST := $(LIBDIR)/bsw_shim_example
 ORACLE   := oracle/liboracle.so
 
-HIP_HDRS := $(CSRC)/bsw_devcache.h $(CSRC)/bsw_pool.h $(CSRC)/bsw_kernels.h $(CSRC)/bsw_mate_k.h include/bsw_mate.h $(CSRC)/bsw_global_k.h include/bsw_global.h $(CSRC)/bsw_ext_k.h $(CSRC)/bsw_aln_k.h include/bsw_aln.h $(CSRC)/bsw_sel_k.h $(CSRC)/bsw_sel_dev.h include/bsw_sel.h $(CSRC)/bsw_pe_k.h include/bsw_pe.h $(CSRC)/bsw_matesw_k.h include/bsw_matesw.h $(CSRC)/bsw_rec_k.h include/bsw_rec.h $(CSRC)/bsw_wave.h $(CSRC)/bsw_internal.h $(CSRC)/bsw_engine.h $(CSRC)/bsw_fmi_internal.h include/bsw.h include/bsw_seqpair.h include/bsw_ext.h include/bsw_batch.h include/bsw_fmi.h
+HIP_HDRS := $(CSRC)/bsw_devcache.h $(CSRC)/bsw_pool.h $(CSRC)/bsw_kernels.h $(CSRC)/bsw_mate_k.h include/bsw_mate.h $(CSRC)/bsw_global_k.h include/bsw_global.h $(CSRC)/bsw_ext_k.h $(CSRC)/bsw_aln_k.h include/bsw_aln.h $(CSRC)/bsw_sel_k.h $(CSRC)/bsw_sel_dev.h include/bsw_sel.h $(CSRC)/bsw_pe_k.h include/bsw_pe.h $(CSRC)/bsw_matesw_k.h include/bsw_matesw.h $(CSRC)/bsw_rec_k.h include/bsw_rec.h $(CSRC)/bsw_wave.h $(CSRC)/bsw_formulas.h $(CSRC)/bsw_stage_k.h $(CSRC)/bsw_internal.h $(CSRC)/bsw_engine.h $(CSRC)/bsw_fmi_internal.h include/bsw.h include/bsw_seqpair.h include/bsw_ext.h include/bsw_batch.h include/bsw_fmi.h
 
 # the product's objects; the experiment libraries below are this list with one object swapped
-OBJS := $(addprefix $(LIBDIR)/,bsw_kernels.o bsw_pc.o bsw_wv.o bsw_gq.o bsw_mate.o bsw_global.o bsw_ext_dev.o bsw_aln.o bsw_sel.o bsw_pe.o bsw_matesw.o bsw_rec.o \
+OBJS := $(addprefix $(LIBDIR)/,bsw_kernels.o bsw_pc.o bsw_wv.o bsw_gq.o bsw_mate.o bsw_global.o bsw_ext_dev.o bsw_aln.o bsw_sel.o bsw_pe.o bsw_matesw.o bsw_rec.o bsw_stage.o \
           bsw_fmi.o bsw_fmi_build.o bsw_memchain.o bsw_chain.o bsw_dispatch.o bsw_pipeline.o bsw_host.o bsw_stages.o bsw_ext.o \
           bsw_pack.o bsw_devcache.o bsw_batch.o)
 LINK  = $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(1) -lpthread
@@ -101,7 +101,7 @@ ASAN_BIN   := $(ASAN_DIR)/asan_driver
 ASAN_C     := $(CSRC)/bsw_batch.c $(CSRC)/bsw_synth.c oracle/ksw_ext_ref.c oracle/ext_ref.c oracle/ksw_align_ref.c oracle/ksw_global_ref.c oracle/fmi_ref.c oracle/chain_ref.c
 ASAN_SSE   := oracle/bsw_sse41.c oracle/bsw_avx512.c
 ASAN_CXX   := $(ASAN_DIR)/asan_driver.cpp $(ASAN_DIR)/engine_stub.cpp $(CSRC)/bsw_ext.cpp $(CSRC)/bsw_pack.cpp
-$(ASAN_BIN): $(ASAN_C) $(ASAN_SSE) oracle/bsw_simd_batch.inc oracle/bsw_simd_common.h $(ASAN_CXX) $(CSRC)/bsw_internal.h include/bsw_ext.h include/bsw_fmi.h
+$(ASAN_BIN): $(ASAN_C) $(ASAN_SSE) oracle/bsw_simd_batch.inc oracle/bsw_simd_common.h $(ASAN_CXX) $(CSRC)/bsw_internal.h $(CSRC)/bsw_formulas.h include/bsw_ext.h include/bsw_fmi.h
 	mkdir -p $(ASAN_DIR)/obj
 	for f in $(ASAN_C); do gcc $(ASAN_FLAGS) -std=gnu11 -c $$f -o $(ASAN_DIR)/obj/$$(basename $$f).o || exit 1; done
 	for f in $(ASAN_SSE); do gcc $(ASAN_FLAGS) -std=gnu11 -msse4.1 -c $$f -o $(ASAN_DIR)/obj/$$(basename $$f).o || exit 1; done

@@ -8,9 +8,9 @@
 //   aln_gapfree_kernel : lq == re - rb with w_ == 0 -- score, NM, MD straight from the read and the
 //                        text, 16 lanes per region (one load instruction covers 16 consecutive
 //                        bytes of 4 regions, as ext_copy_kernel), mismatch columns by ballot
-//   aln_build_kernel   : SeqPair (h0 = bwa_gen_cigar2's band) + query slice / reference span copied
-//                        into per-job strides (idr is 32 bits, the text is not), reversed on the
-//                        reverse strand so that indels come out left-aligned
+//   aln_build_kernel   : one region's job through dp_job_write (bsw_stage_k.h): SeqPair (h0 =
+//                        bwa_gen_cigar2's band) + query slice / reference span in per-job strides,
+//                        reversed on the reverse strand
 //   aln_finish_kernel  : one wave per job -- the band loop's decision after the DP; regions that go
 //                        round again are compacted into the next pass's list, the others get the
 //                        NM / MD walk over the traced CIGAR, the deletion squeeze, clips and pos
@@ -18,27 +18,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bsw_aln_k.h"
+#include "bsw_stage_k.h"
 #include "bsw_wave.h"
 
 namespace bsw {
-
-__device__ __forceinline__ int infer_bw_d(int l1, int l2, int score, int a, int q, int r)
-{
-    if (l1 == l2 && l1 * a - score < (q + r - a) * 2) return 0;
-    const int w = (int)((double)(min(l1, l2) * a - score - q) / r + 2.);
-    return max(w, abs(l1 - l2));
-}
-
-// bsw_gen_cigar_band (include/bsw_global.h), device form
-__device__ __forceinline__ int gen_cigar_band_d(const AlnParams &p, int lq, int rlen, int w_)
-{
-    const int max_ins = (int)((double)(((lq + 1) >> 1) * p.a - p.o_ins) / p.e_ins + 1.);
-    const int max_del = (int)((double)(((lq + 1) >> 1) * p.a - p.o_del) / p.e_del + 1.);
-    const int max_gap = max(max(max_ins, max_del), 1);
-    const int d = abs(rlen - lq);
-    const int w = min((max_gap + d + 1) >> 1, w_);
-    return max(w, d + 3);
-}
 
 // "ACGTN"[c] on the forward strand, "TGCAN"[c] on the reverse strand
 __device__ __forceinline__ uint8_t base_letter(int c, bool rev)
@@ -156,8 +139,8 @@ __global__ void aln_plan_kernel(const AlnParams p, const int32_t *__restrict__ r
                 err = 1;
             } else {
                 lq = (int)lq64; rl = (int)rl64;
-                int w2 = max(infer_bw_d(lq, rl, r.truesc, p.a, p.o_del, p.e_del),
-                             infer_bw_d(lq, rl, r.truesc, p.a, p.o_ins, p.e_ins));
+                int w2 = max(infer_bw(lq, rl, r.truesc, p.a, p.o_del, p.e_del),
+                             infer_bw(lq, rl, r.truesc, p.a, p.o_ins, p.e_ins));
                 if (w2 > p.W) w2 = min(w2, r.w);
                 x.w2 = min(w2, p.W << 2);
                 gf = lq == rl && x.w2 == 0;
@@ -279,23 +262,8 @@ __global__ void aln_build_kernel(const AlnParams p, const uint8_t *__restrict__ 
     if (j >= nj) return;
     const int rg = list[j];
     const bsw_alnreg_t r = regs[rg];
-    const int lq = r.qe - r.qb, rl = (int)(r.re - r.rb);
-    const uint8_t *q = reads + read_off[reg_read[rg]];
-    uint8_t *qd = qbuf + (int64_t)j * p.qstride, *td = tbuf + (int64_t)j * p.tstride;
-    if (sub == 0) {
-        SeqPair sp{};
-        sp.idr = j * p.tstride; sp.idq = j * p.qstride; sp.id = j;
-        sp.len1 = rl; sp.len2 = lq;
-        sp.h0 = gen_cigar_band_d(p, lq, rl, st[rg].w2);
-        pairs[j] = sp;
-    }
-    if (p.l_pac > 0 && r.rb >= p.l_pac) {
-        for (int k = sub; k < lq; k += 16) qd[k] = q[r.qe - 1 - k];
-        for (int k = sub; k < rl; k += 16) td[k] = ref[r.re - 1 - k];
-    } else {
-        for (int k = sub; k < lq; k += 16) qd[k] = q[r.qb + k];
-        for (int k = sub; k < rl; k += 16) td[k] = ref[r.rb + k];
-    }
+    dp_job_write(p, j, sub, reads + read_off[reg_read[rg]], r.qb, r.qe, ref, r.rb, r.re, st[rg].w2, pairs, qbuf,
+                 tbuf);
 }
 
 // One wave per job: the CIGAR is walked wave-uniformly, an M run is compared 64 columns per step
@@ -385,8 +353,6 @@ __global__ void aln_finish_kernel(const AlnParams p, const int32_t *__restrict__
     }
 }
 
-static inline dim3 grid_of(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 hipError_t launch_aln_plan(const AlnParams &p, const int32_t *read_len, const bsw_alnreg_t *regs,
                            const int32_t *reg_read, int32_t n, AlnState *st, int32_t *list0, int32_t *cnt,
                            int32_t *meta, bsw_aln_t *aln, hipStream_t s)
@@ -394,8 +360,8 @@ hipError_t launch_aln_plan(const AlnParams &p, const int32_t *read_len, const bs
     hipError_t e = hipMemsetAsync(meta, 0, kAlnMetaSpread * 16 * sizeof(int32_t), s);
     if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, kAlnCntWords * sizeof(int32_t), s);
     if (e != hipSuccess || n <= 0) return e;
-    hipLaunchKernelGGL(aln_plan_kernel, grid_of(n), dim3(256), 0, s, p, read_len, regs, reg_read, n, st, list0, cnt,
-                       meta, aln);
+    hipLaunchKernelGGL(aln_plan_kernel, grid_for(n, 256), dim3(256), 0, s, p, read_len, regs, reg_read, n, st, list0,
+                       cnt, meta, aln);
     return hipGetLastError();
 }
 
@@ -405,8 +371,8 @@ hipError_t launch_aln_gapfree(const AlnParams &p, const uint8_t *reads, const in
                               hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(aln_gapfree_kernel, grid_of((int64_t)n * 16), dim3(256), 0, s, p, reads, read_off, read_len,
-                       regs, reg_read, n, st, ref, aln, cigar, md);
+    hipLaunchKernelGGL(aln_gapfree_kernel, grid_for((int64_t)n * 16, 256), dim3(256), 0, s, p, reads, read_off,
+                       read_len, regs, reg_read, n, st, ref, aln, cigar, md);
     return hipGetLastError();
 }
 
@@ -416,7 +382,7 @@ hipError_t launch_aln_build(const AlnParams &p, const uint8_t *reads, const int6
                             uint8_t *tbuf, hipStream_t s)
 {
     if (nj <= 0) return hipSuccess;
-    hipLaunchKernelGGL(aln_build_kernel, grid_of((int64_t)nj * 16), dim3(256), 0, s, p, reads, read_off, regs,
+    hipLaunchKernelGGL(aln_build_kernel, grid_for((int64_t)nj * 16, 256), dim3(256), 0, s, p, reads, read_off, regs,
                        reg_read, st, list, nj, ref, pairs, qbuf, tbuf);
     return hipGetLastError();
 }
@@ -428,8 +394,8 @@ hipError_t launch_aln_finish(const AlnParams &p, const int32_t *read_len, const 
                              uint8_t *md, hipStream_t s)
 {
     if (nj <= 0) return hipSuccess;
-    hipLaunchKernelGGL(aln_finish_kernel, grid_of((int64_t)nj * 64), dim3(256), 0, s, p, read_len, regs, reg_read, st, list, nj,
-                       pairs, qbuf, tbuf, jcigar, jncig, next, next_cnt, aln, cigar, md);
+    hipLaunchKernelGGL(aln_finish_kernel, grid_for((int64_t)nj * 64, 256), dim3(256), 0, s, p, read_len, regs, reg_read,
+                       st, list, nj, pairs, qbuf, tbuf, jcigar, jncig, next, next_cnt, aln, cigar, md);
     return hipGetLastError();
 }
 

@@ -7,8 +7,8 @@
 // skipped unless an extended seed of its own chain, >= 95% as long, overlaps it by >= 1/4 of
 // its length on another diagonal.  Work runs in rounds batched across reads: round r extends,
 // for every read, the next seed its containment test keeps.  Here one thread per read runs the
-// per-read order (k_prep), the containment scan and the pick (k_pick, jobs compacted by a
-// wave-aggregated counter), the round's LEFT / RIGHT extensions go through the device
+// per-read order (launch_seed_runs, k_prep), the containment scan and the pick (k_pick, jobs
+// compacted by a wave-aggregated counter), the round's LEFT / RIGHT extensions go through the device
 // extension pipeline (bsw_extend_seeds_device), and k_scatter files the regions; the host only
 // reads back one job count per round.  Job order inside a round is whatever the counter hands
 // out: jobs are independent and results are filed by seed index, so outputs are deterministic.
@@ -20,6 +20,7 @@
 #include "../../include/bsw_ext.h"
 #include "bsw_internal.h"
 #include "bsw_devcache.h"
+#include "bsw_stage_k.h"
 
 namespace {
 
@@ -28,13 +29,9 @@ struct ChainParams {
     int64_t ref_len, l_pac;
 };
 
-__device__ __forceinline__ int d_cal_max_gap(const ChainParams &p, int qlen)
+__device__ __forceinline__ int chain_max_gap(const ChainParams &p, int qlen)
 {
-    const int l_del = (int)((double)(qlen * p.a - p.o_del) / p.e_del + 1.);
-    const int l_ins = (int)((double)(qlen * p.a - p.o_ins) / p.e_ins + 1.);
-    int l = max(l_del, l_ins);
-    l = max(l, 1);
-    return min(l, p.w << 1);
+    return bsw::cal_max_gap(p.a, p.o_del, p.e_del, p.o_ins, p.e_ins, p.w, qlen);
 }
 
 // upstream's "seed contained in an earlier region of the read" test
@@ -47,31 +44,16 @@ __device__ bool d_contained(const ChainParams &p, const bsw_seed_t &s, int l_que
         if (s.len - q.seedlen0 > .1 * l_query) continue;
         int qd = s.qbeg - q.qb;
         int64_t rd = s.rbeg - q.rb;
-        int max_gap = d_cal_max_gap(p, qd < rd ? qd : (int)rd);
+        int max_gap = chain_max_gap(p, qd < rd ? qd : (int)rd);
         int w = min(max_gap, q.w);
         if (qd - rd < w && rd - qd < w) return true;
         qd = q.qe - (s.qbeg + s.len);
         rd = q.re - (s.rbeg + s.len);
-        max_gap = d_cal_max_gap(p, qd < rd ? qd : (int)rd);
+        max_gap = chain_max_gap(p, qd < rd ? qd : (int)rd);
         w = min(max_gap, q.w);
         if (qd - rd < w && rd - qd < w) return true;
     }
     return false;
-}
-
-// seed runs per read: sbeg[r], send[r] (memset 0 first); err |= 1 on a bad or unsorted read id
-__global__ void k_runs(const int32_t *__restrict__ sr, int32_t ns, int32_t n_reads, int32_t *__restrict__ sbeg,
-                       int32_t *__restrict__ send, int32_t *__restrict__ err)
-{
-    const int32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= ns) return;
-    const int32_t r = sr[k];
-    if (r < 0 || r >= n_reads || (k > 0 && sr[k - 1] > r)) {
-        atomicOr(err, 1);
-        return;
-    }
-    if (k == 0 || sr[k - 1] != r) sbeg[r] = k;
-    if (k == ns - 1 || sr[k + 1] != r) send[r] = k + 1;
 }
 
 // per read: regions zeroed, chain order (insertion sort of each chain: score desc, index desc)
@@ -104,8 +86,8 @@ __global__ void k_prep(int32_t n_reads, const int32_t *__restrict__ sbeg, const 
             if (t.len <= 0) continue;
             if (first < 0) first = t.rbeg;
             const int qe = t.qbeg + t.len;
-            lo = min(lo, t.rbeg - (int64_t)(t.qbeg + d_cal_max_gap(p, t.qbeg)));
-            hi = max(hi, t.rbeg + t.len + (int64_t)((l_query - qe) + d_cal_max_gap(p, l_query - qe)));
+            lo = min(lo, t.rbeg - (int64_t)(t.qbeg + chain_max_gap(p, t.qbeg)));
+            hi = max(hi, t.rbeg + t.len + (int64_t)((l_query - qe) + chain_max_gap(p, l_query - qe)));
         }
         lo = max(lo, (int64_t)0);
         hi = min(hi, p.ref_len);
@@ -275,8 +257,7 @@ int chain_rounds_device(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint8_t 
     CH_TRY(hipMemsetAsync(sbeg, 0, nr * sizeof(int32_t), st));
     CH_TRY(hipMemsetAsync(send, 0, nr * sizeof(int32_t), st));
     CH_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_runs, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, d_sr, ns, n_reads, sbeg, send, err);
-    CH_TRY(hipGetLastError());
+    CH_TRY(launch_seed_runs(d_sr, ns, n_reads, sbeg, send, err, st));
     CH_TRY(hipMemcpyAsync(h, err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     CH_TRY(hipStreamSynchronize(st));
     if (h[0]) return BSW_E_INVAL;                       // unsorted / out-of-range seed_read

@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/bsw_ext.h"
+#include "bsw_formulas.h"
 #include "bsw_internal.h"
 #include "bsw_pool.h"
 
@@ -37,11 +38,7 @@ struct Job {                       // one extension of one read
 
 int cal_max_gap(const bsw_params_t &p, int a, int w, int qlen)
 {
-    const int l_del = (int)((double)(qlen * a - p.o_del) / p.e_del + 1.);
-    const int l_ins = (int)((double)(qlen * a - p.o_ins) / p.e_ins + 1.);
-    int l = std::max(l_del, l_ins);
-    l = std::max(l, 1);
-    return std::min(l, w << 1);
+    return bsw::cal_max_gap(a, p.o_del, p.e_del, p.o_ins, p.e_ins, w, qlen);
 }
 
 // mem_chain2aln's target window of a chain (include/bsw_ext.h; oracle_chain_window): min / max

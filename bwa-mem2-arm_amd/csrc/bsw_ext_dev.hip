@@ -14,26 +14,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bsw_ext_k.h"
+#include "bsw_stage_k.h"
 #include "bsw_wave.h"
 
 namespace bsw {
-
-__device__ __forceinline__ int cal_max_gap_d(const ExtDevParams &p, int qlen)
-{
-    const int l_del = (int)((double)(qlen * p.a - p.o_del) / p.e_del + 1.);
-    const int l_ins = (int)((double)(qlen * p.a - p.o_ins) / p.e_ins + 1.);
-    int l = max(l_del, l_ins);
-    l = max(l, 1);
-    return min(l, p.w << 1);
-}
 
 // mem_chain2aln's target window of one seed taken as a chain of one (bsw_ext.cpp chain_window)
 __device__ __forceinline__ void seed_window_d(const ExtDevParams &p, const bsw_seed_t &s, int l, int64_t *r0,
                                               int64_t *r1)
 {
     const int qe = s.qbeg + s.len;
-    int64_t lo = s.rbeg - (s.qbeg + cal_max_gap_d(p, s.qbeg));
-    int64_t hi = s.rbeg + s.len + ((l - qe) + cal_max_gap_d(p, l - qe));
+    int64_t lo = s.rbeg - (s.qbeg + cal_max_gap(p.a, p.o_del, p.e_del, p.o_ins, p.e_ins, p.w, s.qbeg));
+    int64_t hi = s.rbeg + s.len + ((l - qe) + cal_max_gap(p.a, p.o_del, p.e_del, p.o_ins, p.e_ins, p.w, l - qe));
     lo = lo > 0 ? lo : 0;
     hi = hi < p.ref_len ? hi : p.ref_len;
     if (p.l_pac > 0 && lo < p.l_pac && p.l_pac < hi) {
@@ -262,14 +254,12 @@ __global__ void ext_interp_kernel(const ExtDevParams p, const int32_t *__restric
     out[i] = r;
 }
 
-static inline dim3 grid_of(int32_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 hipError_t launch_ext_scan(const ExtDevParams &p, const int32_t *read_len, const bsw_seed_t *seeds, const int64_t *win,
                            int32_t n, int64_t *wout, int32_t *meta, hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(meta, 0, kExtMetaSpread * 16 * sizeof(int32_t), s);
     if (e != hipSuccess || n <= 0) return e;
-    hipLaunchKernelGGL(ext_scan_kernel, grid_of(n), dim3(256), 0, s, p, read_len, seeds, win, n, wout, meta);
+    hipLaunchKernelGGL(ext_scan_kernel, grid_for(n, 256), dim3(256), 0, s, p, read_len, seeds, win, n, wout, meta);
     return hipGetLastError();
 }
 
@@ -280,12 +270,12 @@ hipError_t launch_ext_build(int left, const ExtDevParams &p, const uint8_t *read
 {
     if (n <= 0) return hipSuccess;
     if (left)
-        hipLaunchKernelGGL(ext_left_build_kernel, grid_of(n), dim3(256), 0, s, p, reads, read_off, read_len, seeds,
-                           win, n, ref, st, pairs, qbuf, tbuf, out);
+        hipLaunchKernelGGL(ext_left_build_kernel, grid_for(n, 256), dim3(256), 0, s, p, reads, read_off, read_len,
+                           seeds, win, n, ref, st, pairs, qbuf, tbuf, out);
     else
-        hipLaunchKernelGGL(ext_right_build_kernel, grid_of(n), dim3(256), 0, s, p, reads, read_off, read_len, seeds,
-                           n, ref, st, pairs, qbuf, tbuf);
-    hipLaunchKernelGGL(ext_copy_kernel, dim3((unsigned)(((int64_t)n * 16 + 255) / 256)), dim3(256), 0, s, left, reads,
+        hipLaunchKernelGGL(ext_right_build_kernel, grid_for(n, 256), dim3(256), 0, s, p, reads, read_off, read_len,
+                           seeds, n, ref, st, pairs, qbuf, tbuf);
+    hipLaunchKernelGGL(ext_copy_kernel, grid_for((int64_t)n * 16, 256), dim3(256), 0, s, left, reads,
                        read_off, seeds, n, ref, pairs, qbuf, tbuf);
     return hipGetLastError();
 }
@@ -295,7 +285,7 @@ hipError_t launch_ext_retry_mark(const SeqPair *src, SeqPair *sub, ExtState *st,
 {
     hipError_t e = hipMemsetAsync(cnt, 0, sizeof(int32_t), s);
     if (e != hipSuccess || n <= 0) return e;
-    hipLaunchKernelGGL(ext_retry_mark_kernel, grid_of(n), dim3(256), 0, s, src, sub, st, n, wt, cnt);
+    hipLaunchKernelGGL(ext_retry_mark_kernel, grid_for(n, 256), dim3(256), 0, s, src, sub, st, n, wt, cnt);
     return hipGetLastError();
 }
 
@@ -303,7 +293,7 @@ hipError_t launch_ext_retry_merge(SeqPair *pairs, const SeqPair *sub, ExtState *
                                   int left, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ext_retry_merge_kernel, grid_of(n), dim3(256), 0, s, pairs, sub, st, n, wn, left);
+    hipLaunchKernelGGL(ext_retry_merge_kernel, grid_for(n, 256), dim3(256), 0, s, pairs, sub, st, n, wn, left);
     return hipGetLastError();
 }
 
@@ -311,7 +301,8 @@ hipError_t launch_ext_interp(int left, const ExtDevParams &p, const int32_t *rea
                              int32_t n, const SeqPair *pairs, ExtState *st, bsw_alnreg_t *out, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ext_interp_kernel, grid_of(n), dim3(256), 0, s, p, read_len, seeds, n, pairs, st, out, left);
+    hipLaunchKernelGGL(ext_interp_kernel, grid_for(n, 256), dim3(256), 0, s, p, read_len, seeds, n, pairs, st, out,
+                       left);
     return hipGetLastError();
 }
 

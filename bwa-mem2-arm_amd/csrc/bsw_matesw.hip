@@ -21,17 +21,10 @@
 #include <algorithm>
 #include "bsw_matesw_k.h"
 #include "bsw_sel_dev.h"
+#include "bsw_stage_k.h"
 #include "bsw_wave.h"
 
 namespace bsw {
-
-__device__ __forceinline__ int msw_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t &dist)
-{
-    const bool r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-    const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-    dist = p2 > b1 ? p2 - b1 : b1 - p2;
-    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
 
 // direction r's window of the text around an anchor at arb; true when a job runs for it
 __device__ __forceinline__ bool msw_window(const MswParams &p, const MswDir &d, int r, int64_t arb, int l_ms,
@@ -54,12 +47,6 @@ __device__ __forceinline__ bool msw_window(const MswParams &p, const MswDir &d, 
         else rb = max(rb, l_pac);
     }
     return rb < re && re - rb >= p.s.min_seed_len;
-}
-
-__device__ __forceinline__ int wave_sum(int x)
-{
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
 }
 
 __global__ __launch_bounds__(256) void msw_count_kernel(const MswParams p, const bsw_alnreg_t *__restrict__ regs,
@@ -98,14 +85,6 @@ __global__ __launch_bounds__(256) void msw_count_kernel(const MswParams p, const
     capv[2 * pr + 1] = (f2 - f1) + 4 * c0;
 }
 
-// the frac_rep of a region rides in the (here unused) hash word of its work entry
-__device__ __forceinline__ void msw_load(SelW &x, const bsw_alnreg_t &r, const bsw_selinfo_t &f)
-{
-    x.r = r;
-    x.seedcov = f.seedcov; x.sub = f.sub; x.csub = f.csub; x.sub_n = f.sub_n; x.n_comp = f.n_comp;
-    x.secondary = f.secondary; x.src = f.src; x.mapq = f.mapq; x.hash = (uint64_t)__float_as_uint(f.frac_rep);
-}
-
 __global__ __launch_bounds__(64) void msw_step_kernel(
     const MswParams p, const int32_t *__restrict__ list, int32_t n_items, const bsw_alnreg_t *__restrict__ regs,
     const bsw_selinfo_t *__restrict__ info, const int32_t *__restrict__ first, const int32_t *__restrict__ read_len,
@@ -140,8 +119,10 @@ __global__ __launch_bounds__(64) void msw_step_kernel(
                 const int thr = n ? regs[fb].score - p.pen_unpaired : 0;
                 int c = 0;
                 for (int k = 0; k < n; ++k) {
+                    // the frac_rep of a region rides in the (here unused) hash word of its work entry
+                    const bsw_selinfo_t &f = info[fb + k];
                     SelW x;
-                    msw_load(x, regs[fb + k], info[fb + k]);
+                    selw_load(x, regs[fb + k], f, (uint64_t)__float_as_uint(f.frac_rep));
                     W[k] = x;
                     if (c < nc && x.r.score >= thr) C[c++] = x.r.rb;
                 }
@@ -221,7 +202,7 @@ __global__ __launch_bounds__(64) void msw_step_kernel(
             int skip = failed;
             for (int m = 0; m < n; ++m) {
                 int64_t dist;
-                const int r = msw_infer_dir(p.s.l_pac, arb, W[m].r.rb, dist);
+                const int r = infer_dir(p.s.l_pac, arb, W[m].r.rb, dist);
                 if (dist >= s_pes[r].low && dist <= s_pes[r].high) skip |= 1 << r;
             }
             ++c_calls;
@@ -323,23 +304,20 @@ __global__ void msw_build_kernel(const MswParams p, const MswJob *__restrict__ j
     const MswJob q = jobs[j];
     const int lq = read_len[q.read];
     const uint8_t *rd = reads + read_off[q.read];
-    uint8_t *qd = qbuf + (int64_t)j * p.qstride, *td = tbuf + (int64_t)j * p.tstride;
-    if (sub == 0) {
-        SeqPair sp{};
-        sp.idr = j * p.tstride; sp.idq = j * p.qstride; sp.id = j;
-        sp.len1 = q.len; sp.len2 = lq;
-        sp.h0 = BSW_KSW_XSUBO | BSW_KSW_XSTART | (lq * p.s.a < 250 ? BSW_KSW_XBYTE : 0) | (p.s.min_seed_len * p.s.a);
-        pairs[j] = sp;
-    }
-    if (q.rev) {
+    uint8_t *qd = qbuf + (int64_t)j * p.qstride;
+    if (sub == 0)
+        dp_job_header(pairs, j, p.qstride, p.tstride, q.len, lq,
+                      BSW_KSW_XSUBO | BSW_KSW_XSTART | (lq * p.s.a < 250 ? BSW_KSW_XBYTE : 0) |
+                          (p.s.min_seed_len * p.s.a));
+    if (q.rev) {                                            // the reverse complement, not dp_job_copy_rev
         for (int k = sub; k < lq; k += 16) {
             const uint8_t c = rd[lq - 1 - k];
             qd[k] = c < 4 ? 3 - c : 4;
         }
     } else {
-        for (int k = sub; k < lq; k += 16) qd[k] = rd[k];
+        dp_job_copy(qd, rd, 0, lq, sub);
     }
-    for (int k = sub; k < q.len; k += 16) td[k] = ref[q.rb + k];
+    dp_job_copy(tbuf + (int64_t)j * p.tstride, ref, q.rb, q.len, sub);
 }
 
 __global__ void msw_emit_kernel(const MswParams p, const int32_t *__restrict__ woff, const int32_t *__restrict__ nlist,
@@ -356,20 +334,15 @@ __global__ void msw_emit_kernel(const MswParams p, const int32_t *__restrict__ w
         const SelW x = W[k];
         out_regs[o + k] = x.r;
         out_read[o + k] = r;
-        bsw_selinfo_t f;
-        f.seedcov = x.seedcov; f.sub = x.sub; f.csub = x.csub; f.sub_n = x.sub_n; f.n_comp = x.n_comp;
-        f.secondary = x.secondary; f.mapq = x.mapq; f.src = x.src; f.frac_rep = __uint_as_float((uint32_t)x.hash);
-        out_info[o + k] = f;
+        out_info[o + k] = selw_info(x, __uint_as_float((uint32_t)x.hash));     // (frac_rep: see round 0)
     }
 }
-
-static inline dim3 msw_grid(int64_t n, int b) { return dim3((unsigned)((n + b - 1) / b)); }
 
 hipError_t launch_msw_count(const MswParams &p, const bsw_alnreg_t *regs, const int32_t *first, int32_t *ncand,
                             int32_t *capv, int32_t *meta, hipStream_t s)
 {
     if (p.n_pairs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(msw_count_kernel, msw_grid(p.n_pairs, 256), dim3(256), 0, s, p, regs, first, ncand, capv, meta);
+    hipLaunchKernelGGL(msw_count_kernel, grid_for(p.n_pairs, 256), dim3(256), 0, s, p, regs, first, ncand, capv, meta);
     return hipGetLastError();
 }
 
@@ -380,7 +353,7 @@ hipError_t launch_msw_step(const MswParams &p, const int32_t *list, int32_t n_it
                            int32_t *meta, hipStream_t s)
 {
     if (n_items <= 0) return hipSuccess;
-    hipLaunchKernelGGL(msw_step_kernel, msw_grid(n_items, 64), dim3(64), 0, s, p, list, n_items, regs, info, first,
+    hipLaunchKernelGGL(msw_step_kernel, grid_for(n_items, 64), dim3(64), 0, s, p, list, n_items, regs, info, first,
                        read_len, ncand, coff, woff, cand, work, nlist, st, aln, jobs, next, meta);
     return hipGetLastError();
 }
@@ -390,7 +363,7 @@ hipError_t launch_msw_build(const MswParams &p, const MswJob *jobs, int32_t nj, 
                             uint8_t *qbuf, uint8_t *tbuf, hipStream_t s)
 {
     if (nj <= 0) return hipSuccess;
-    hipLaunchKernelGGL(msw_build_kernel, msw_grid((int64_t)nj * 16, 256), dim3(256), 0, s, p, jobs, nj, reads, read_off,
+    hipLaunchKernelGGL(msw_build_kernel, grid_for((int64_t)nj * 16, 256), dim3(256), 0, s, p, jobs, nj, reads, read_off,
                        read_len, ref, pairs, qbuf, tbuf);
     return hipGetLastError();
 }
@@ -400,8 +373,8 @@ hipError_t launch_msw_emit(const MswParams &p, const int32_t *woff, const int32_
                            hipStream_t s)
 {
     if (p.n_pairs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(msw_emit_kernel, msw_grid(2 * (int64_t)p.n_pairs, 256), dim3(256), 0, s, p, woff, nlist, out_first,
-                       work, out_regs, out_read, out_info);
+    hipLaunchKernelGGL(msw_emit_kernel, grid_for(2 * (int64_t)p.n_pairs, 256), dim3(256), 0, s, p, woff, nlist,
+                       out_first, work, out_regs, out_read, out_info);
     return hipGetLastError();
 }
 

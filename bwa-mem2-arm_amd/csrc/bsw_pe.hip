@@ -18,6 +18,7 @@
 #include <algorithm>
 #include "bsw_pe_k.h"
 #include "bsw_sel_dev.h"
+#include "bsw_stage_k.h"
 
 namespace bsw {
 
@@ -47,14 +48,6 @@ __device__ __forceinline__ bool pe_bounds(const int32_t *__restrict__ first, int
     f0 = first[2 * pr]; f1 = first[2 * pr + 1]; f2 = first[2 * pr + 2];
     return f0 >= 0 && f0 <= f1 && f1 <= f2 && f2 <= n_regs && f1 - f0 <= BSW_SEL_MAX_PER_READ &&
            f2 - f1 <= BSW_SEL_MAX_PER_READ;
-}
-
-__device__ __forceinline__ int pe_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t &dist)
-{
-    const bool r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-    const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-    dist = p2 > b1 ? p2 - b1 : b1 - p2;
-    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
 }
 
 __device__ __forceinline__ int pe_cal_sub(const SelParams &p, const bsw_alnreg_t *__restrict__ a, int n)
@@ -108,7 +101,7 @@ __global__ __launch_bounds__(kPeStatBlock) void pe_stat_kernel(const PeParams p,
         if ((double)pe_cal_sub(p.s, a0, f1 - f0) > 0.8 * a0[0].score) continue;
         if ((double)pe_cal_sub(p.s, a1, f2 - f1) > 0.8 * a1[0].score) continue;
         int64_t is;
-        const int dir = pe_infer_dir(p.s.l_pac, a0[0].rb, a1[0].rb, is);
+        const int dir = infer_dir(p.s.l_pac, a0[0].rb, a1[0].rb, is);
         if (is == 0 || is > p.max_ins) continue;
 #ifdef BSW_PE_STAT_DIRECT                               // experiment build: no table, DESIGN.md §4.18
         atomicAdd(&hist[dir * bins + (int)is], 1);
@@ -146,13 +139,6 @@ __device__ __forceinline__ int pe_q(const PeDir &d, int64_t dist, uint32_t si, u
     return max(q, 0);
 }
 
-__device__ __forceinline__ void pe_load(SelW &x, const bsw_alnreg_t &r, const bsw_selinfo_t &f)
-{
-    x.r = r;
-    x.seedcov = f.seedcov; x.sub = f.sub; x.csub = f.csub; x.sub_n = f.sub_n; x.n_comp = f.n_comp;
-    x.secondary = f.secondary; x.src = f.src; x.mapq = f.mapq; x.hash = 0;
-}
-
 // mem_sam_pe's choice of branch: 0 = no_pairing, 1 = paired with o > score_un, 2 = paired without
 __device__ __forceinline__ int pe_decide(const PeParams &p, bool both, int o, int sub, int n_sub, bool multi, int s0,
                                          int s1, float fr0, float fr1, int &q_pe, bool &was_multi)
@@ -185,7 +171,7 @@ __device__ __forceinline__ int pe_qse(const PeParams &p, const SelW &c, float fr
 __device__ __forceinline__ int pe_unpaired_proper(const PeParams &p, const PeDir *pes, int64_t rb0, int64_t rb1)
 {
     int64_t dist;
-    const PeDir d = pes[pe_infer_dir(p.s.l_pac, rb0, rb1, dist)];
+    const PeDir d = pes[infer_dir(p.s.l_pac, rb0, rb1, dist)];
     return !d.failed && dist >= d.low && dist <= d.high;
 }
 
@@ -215,13 +201,13 @@ __device__ __forceinline__ int pe_fast_pair(const PeParams &p, const PeDir *s_pe
     bool err = false;
     if (n0) {
         const bsw_selinfo_t f = info[f0];
-        pe_load(x0, regs[f0], f);
+        selw_load(x0, regs[f0], f, 0);
         fr0 = f.frac_rep;
         err |= x0.r.rb < 0 || x0.r.rb >= two_l;
     }
     if (n1) {
         const bsw_selinfo_t f = info[f1];
-        pe_load(x1, regs[f1], f);
+        selw_load(x1, regs[f1], f, 0);
         fr1 = f.frac_rep;
         err |= x1.r.rb < 0 || x1.r.rb >= two_l;
     }
@@ -396,7 +382,7 @@ __global__ __launch_bounds__(64) void pe_pair_general_kernel(const PeParams p, b
         bool bad = false;
         for (int k = f0; k < f2; ++k) {
             SelW x;
-            pe_load(x, regs[k], info[k]);
+            selw_load(x, regs[k], info[k], 0);
             bad |= x.r.rb < 0 || x.r.rb >= two_l;
             work[k] = x;
         }
@@ -499,22 +485,17 @@ __global__ __launch_bounds__(64) void pe_pair_general_kernel(const PeParams p, b
         for (int k = f0; k < f2; ++k) {
             const SelW *c = work + k;
             regs[k] = c->r;
-            bsw_selinfo_t f;
-            f.seedcov = c->seedcov; f.sub = c->sub; f.csub = c->csub; f.sub_n = c->sub_n; f.n_comp = c->n_comp;
-            f.secondary = c->secondary; f.mapq = c->mapq; f.src = c->src; f.frac_rep = k < f1 ? fr0 : fr1;
-            info[k] = f;
+            info[k] = selw_info(*c, k < f1 ? fr0 : fr1);
         }
     }
 }
-
-static inline dim3 pe_grid(int64_t n, int b) { return dim3((unsigned)((n + b - 1) / b)); }
 
 hipError_t launch_pe_stat(const PeParams &p, const bsw_alnreg_t *regs, const int32_t *first, int32_t *hist,
                           int32_t *meta, hipStream_t s)
 {
     if (p.n_pairs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pe_stat_kernel, pe_grid(p.n_pairs, kPeStatBlock * kPeStatPer), dim3(kPeStatBlock), 0, s, p, regs,
-                       first, hist, meta);
+    hipLaunchKernelGGL(pe_stat_kernel, grid_for(p.n_pairs, kPeStatBlock * kPeStatPer), dim3(kPeStatBlock), 0, s, p,
+                       regs, first, hist, meta);
     return hipGetLastError();
 }
 
@@ -522,8 +503,8 @@ hipError_t launch_pe_pair_fast(const PeParams &p, const bsw_alnreg_t *regs, bsw_
                                bsw_pair_t *pairs, int32_t *list, int32_t *meta, hipStream_t s)
 {
     if (p.n_pairs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pe_pair_fast_kernel, pe_grid(p.n_pairs, kPeFastBlock * kPeFastPer), dim3(kPeFastBlock), 0, s, p, regs, info, first, pairs, list,
-                       meta);
+    hipLaunchKernelGGL(pe_pair_fast_kernel, grid_for(p.n_pairs, kPeFastBlock * kPeFastPer), dim3(kPeFastBlock), 0, s, p,
+                       regs, info, first, pairs, list, meta);
     return hipGetLastError();
 }
 

@@ -20,9 +20,9 @@
 // The lists are short (bsw_pe.hip's general kernel): XA membership is recounted per record instead
 // of kept in per-read arrays.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include "bsw_rec_k.h"
+#include "bsw_stage_k.h"
 
 namespace bsw {
 
@@ -612,12 +612,10 @@ __global__ __launch_bounds__(kRecTextBlock) void rec_text_write_kernel(RecText t
 
 }  // namespace
 
-static inline unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
 hipError_t launch_rec_count(const RecParams &p, const RecLists &l, int32_t *nrec, int32_t *naln, int32_t *meta,
                             hipStream_t s)
 {
-    rec_plan_kernel<false><<<blocks_of((int64_t)p.n_reads + 1, kBlock), kBlock, 0, s>>>(
+    rec_plan_kernel<false><<<grid_for((int64_t)p.n_reads + 1, kBlock), kBlock, 0, s>>>(
         p, l, nrec, naln, meta, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     return hipGetLastError();
 }
@@ -626,19 +624,9 @@ hipError_t launch_rec_fill(const RecParams &p, const RecLists &l, const int32_t 
                            bsw_rec_t *recs, int32_t *aln_reg, bsw_alnreg_t *creg, int32_t *creg_read, hipStream_t s)
 {
     if (p.n_reads == 0) return hipSuccess;
-    rec_plan_kernel<true><<<blocks_of(p.n_reads, kBlock), kBlock, 0, s>>>(p, l, nullptr, nullptr, nullptr, rec_first,
+    rec_plan_kernel<true><<<grid_for(p.n_reads, kBlock), kBlock, 0, s>>>(p, l, nullptr, nullptr, nullptr, rec_first,
                                                                          aln_first, recs, aln_reg, creg, creg_read);
     return hipGetLastError();
-}
-
-hipError_t launch_rec_scan32(void *tmp, size_t *tmp_bytes, const int32_t *in, int32_t *out, int32_t n, hipStream_t s)
-{
-    return hipcub::DeviceScan::ExclusiveSum(tmp, *tmp_bytes, in, out, n + 1, s);
-}
-
-hipError_t launch_rec_scan64(void *tmp, size_t *tmp_bytes, const int64_t *in, int64_t *out, int32_t n, hipStream_t s)
-{
-    return hipcub::DeviceScan::ExclusiveSum(tmp, *tmp_bytes, in, out, n + 1, s);
 }
 
 hipError_t launch_rec_finish(const RecLists &l, const int32_t *rec_first, bsw_rec_t *recs, int32_t n_rec,
@@ -647,21 +635,21 @@ hipError_t launch_rec_finish(const RecLists &l, const int32_t *rec_first, bsw_re
 {
     const int64_t n = n_rec > n_aln ? n_rec : n_aln;
     if (n == 0) return hipSuccess;
-    rec_finish_kernel<<<blocks_of(n, kBlock), kBlock, 0, s>>>(l, rec_first, recs, n_rec, aln, cigar, cigar_stride, n_aln,
+    rec_finish_kernel<<<grid_for(n, kBlock), kBlock, 0, s>>>(l, rec_first, recs, n_rec, aln, cigar, cigar_stride, n_aln,
                                                               meta);
     return hipGetLastError();
 }
 
 hipError_t launch_rec_text_len(const RecText &t, int64_t *len, int32_t *meta, hipStream_t s)
 {
-    rec_text_len_kernel<<<blocks_of((int64_t)t.n_rec + 1, kBlock), kBlock, 0, s>>>(t, len, meta);
+    rec_text_len_kernel<<<grid_for((int64_t)t.n_rec + 1, kBlock), kBlock, 0, s>>>(t, len, meta);
     return hipGetLastError();
 }
 
 hipError_t launch_rec_text_write(const RecText &t, const int64_t *text_off, uint8_t *text, hipStream_t s)
 {
     if (t.n_rec == 0) return hipSuccess;
-    rec_text_write_kernel<<<blocks_of(t.n_rec, kPerBlock), kRecTextBlock, 0, s>>>(t, text_off, text);
+    rec_text_write_kernel<<<grid_for(t.n_rec, kPerBlock), kRecTextBlock, 0, s>>>(t, text_off, text);
     return hipGetLastError();
 }
 

@@ -52,9 +52,6 @@ hipError_t launch_rec_count(const RecParams &p, const RecLists &l, int32_t *nrec
                             hipStream_t s);
 hipError_t launch_rec_fill(const RecParams &p, const RecLists &l, const int32_t *rec_first, const int32_t *aln_first,
                            bsw_rec_t *recs, int32_t *aln_reg, bsw_alnreg_t *creg, int32_t *creg_read, hipStream_t s);
-// out[0 .. n] = exclusive scan of in[0 .. n]; tmp == nullptr only sizes *tmp_bytes
-hipError_t launch_rec_scan32(void *tmp, size_t *tmp_bytes, const int32_t *in, int32_t *out, int32_t n, hipStream_t s);
-hipError_t launch_rec_scan64(void *tmp, size_t *tmp_bytes, const int64_t *in, int64_t *out, int32_t n, hipStream_t s);
 // One work item per record and per alignment: cross-linking, TLEN, the printed flag; rejected and
 // overflowing alignments and the stage's counters into meta.
 hipError_t launch_rec_finish(const RecLists &l, const int32_t *rec_first, bsw_rec_t *recs, int32_t n_rec,

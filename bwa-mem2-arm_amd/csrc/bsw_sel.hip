@@ -1,7 +1,7 @@
 // bsw_sel.hip -- region selection (include/bsw_sel.h: mem_sort_dedup_patch, mem_mark_primary_se,
 // mem_approx_mapq_se) between bsw_chain2aln_resident and bsw_reg2aln_resident, every per-read
 // step on the GPU:
-//   sel_runs_kernel   : each read's run of seed slots; a read's work list lives in the flat
+//   seed runs         : launch_seed_runs (bsw_stage.hip); a read's work list lives in the flat
 //                       work[] at its run's first slot (a read has at most one region per slot)
 //   sel_gather_kernel : av in upstream's order (chains in order, each by len * a and index
 //                       descending), seedcov, csub, validation
@@ -11,31 +11,20 @@
 //                       it with the job's score; a read whose loop ends goes on through the drops,
 //                       the score sort, the identical-hit rule, the hash sort, primary marking and
 //                       MAPQ (double precision).  Reads with at most one region skip all of it.
-//   sel_build_kernel  : 16 lanes per job, SeqPair + query slice / reference span as aln_build_kernel
+//   sel_build_kernel  : 16 lanes per job, the patch's span through dp_job_write (bsw_stage_k.h)
 //   sel_emit_kernel   : after the scan of the kept counts, the compact output
 // The sorts are klib's ks_introsort (w_introsort of bsw_memchain.hip with a comparator), their
 // explicit stack in LDS; they, the hash, marking, MAPQ and the dedup loop itself (sel_dedup,
 // sel_dedup_drop) are in bsw_sel_dev.h (bsw_pe.hip marks again, bsw_matesw.hip dedups with patch = 0).
 // Plain C++ with vector stores only; no private arrays.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include "bsw_sel_k.h"
 #include "bsw_sel_dev.h"
+#include "bsw_stage_k.h"
 #include "bsw_wave.h"
 
 namespace bsw {
-
-// bsw_gen_cigar_band (include/bsw_global.h), device form
-__device__ __forceinline__ int sel_cigar_band(const SelParams &p, int lq, int rlen, int w_)
-{
-    const int max_ins = (int)((double)(((lq + 1) >> 1) * p.a - p.o_ins) / p.e_ins + 1.);
-    const int max_del = (int)((double)(((lq + 1) >> 1) * p.a - p.o_del) / p.e_del + 1.);
-    const int max_gap = max(max(max_ins, max_del), 1);
-    const int d = abs(rlen - lq);
-    const int w = min((max_gap + d + 1) >> 1, w_);
-    return max(w, d + 3);
-}
 
 // A read whose dedup loop has ended (dedup: it ran, n > 1 at its start): steps 4..7, primary
 // marking and MAPQ; returns the number kept.
@@ -46,20 +35,6 @@ __device__ __forceinline__ int sel_finish(const SelParams &p, int r, SelW *W, in
     if (n == 0) return 0;
     sel_mark_mapq(p, r, W, n, stk, Z, frac_rep);
     return n;
-}
-
-__global__ void sel_runs_kernel(const int32_t *__restrict__ sr, int32_t ns, int32_t n_reads,
-                                int32_t *__restrict__ sbeg, int32_t *__restrict__ send, int32_t *__restrict__ meta)
-{
-    const int32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= ns) return;
-    const int32_t r = sr[k];
-    if (r < 0 || r >= n_reads || (k > 0 && sr[k - 1] > r)) {
-        atomicOr(&meta[kSelErr], 1);
-        return;
-    }
-    if (k == 0 || sr[k - 1] != r) sbeg[r] = k;
-    if (k == ns - 1 || sr[k + 1] != r) send[r] = k + 1;
 }
 
 __global__ __launch_bounds__(64) void sel_gather_kernel(
@@ -117,8 +92,7 @@ __global__ __launch_bounds__(64) void sel_gather_kernel(
         s.n = n; s.i = 0; s.j = 0; s.w = 0;
         st[r] = s;
     }
-    int tot = n;
-    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+    const int tot = wave_sum(n);
     const unsigned long long be = __ballot(err);
     if ((threadIdx.x & 63) == 0) {
         if (tot) atomicAdd(&meta[kSelRegsIn], tot);
@@ -180,26 +154,9 @@ __global__ void sel_build_kernel(const SelParams p, const int32_t *__restrict__ 
     if (j >= nj) return;
     const int rd = list[j];
     const SelRd s = st[rd];
-    const SelW *W = work + sbeg[rd];
-    const int qb = W[s.j].r.qb, qe = W[s.i].r.qe;
-    const int64_t rb = W[s.j].r.rb, re = W[s.i].r.re;
-    const int lq = qe - qb, rl = (int)(re - rb);
-    const uint8_t *q = reads + read_off[rd];
-    uint8_t *qd = qbuf + (int64_t)j * p.qstride, *td = tbuf + (int64_t)j * p.tstride;
-    if (sub == 0) {
-        SeqPair sp{};
-        sp.idr = j * p.tstride; sp.idq = j * p.qstride; sp.id = j;
-        sp.len1 = rl; sp.len2 = lq;
-        sp.h0 = sel_cigar_band(p, lq, rl, s.w);
-        pairs[j] = sp;
-    }
-    if (p.l_pac > 0 && rb >= p.l_pac) {
-        for (int k = sub; k < lq; k += 16) qd[k] = q[qe - 1 - k];
-        for (int k = sub; k < rl; k += 16) td[k] = ref[re - 1 - k];
-    } else {
-        for (int k = sub; k < lq; k += 16) qd[k] = q[qb + k];
-        for (int k = sub; k < rl; k += 16) td[k] = ref[rb + k];
-    }
+    const SelW *W = work + sbeg[rd];                        // patch_reg(a = W[s.j], b = W[s.i]): a's start to b's end
+    dp_job_write(p, j, sub, reads + read_off[rd], W[s.j].r.qb, W[s.i].r.qe, ref, W[s.j].r.rb, W[s.i].r.re, s.w, pairs,
+                 qbuf, tbuf);
 }
 
 __global__ void sel_emit_kernel(const SelParams p, const int32_t *__restrict__ sr, const int32_t *__restrict__ sbeg,
@@ -216,21 +173,7 @@ __global__ void sel_emit_kernel(const SelParams p, const int32_t *__restrict__ s
     const int32_t o = first[r] + idx;
     sel_regs[o] = x.r;
     sel_read[o] = r;
-    bsw_selinfo_t f;
-    f.seedcov = x.seedcov; f.sub = x.sub; f.csub = x.csub; f.sub_n = x.sub_n; f.n_comp = x.n_comp;
-    f.secondary = x.secondary; f.mapq = x.mapq; f.src = x.src; f.frac_rep = frac_rep ? frac_rep[r] : 0.f;
-    sel_info[o] = f;
-}
-
-static inline dim3 grid_of(int64_t n, int b) { return dim3((unsigned)((n + b - 1) / b)); }
-
-hipError_t launch_sel_runs(const int32_t *seed_read, int32_t n_seeds, int32_t n_reads, int32_t *sbeg, int32_t *send,
-                           int32_t *meta, hipStream_t s)
-{
-    if (n_seeds <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sel_runs_kernel, grid_of(n_seeds, 256), dim3(256), 0, s, seed_read, n_seeds, n_reads, sbeg, send,
-                       meta);
-    return hipGetLastError();
+    sel_info[o] = selw_info(x, frac_rep ? frac_rep[r] : 0.f);
 }
 
 hipError_t launch_sel_gather(const SelParams &p, const int32_t *sbeg, const int32_t *send, const int32_t *read_len,
@@ -239,7 +182,7 @@ hipError_t launch_sel_gather(const SelParams &p, const int32_t *sbeg, const int3
                              hipStream_t s)
 {
     if (p.n_reads <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sel_gather_kernel, grid_of(p.n_reads, 64), dim3(64), 0, s, p, sbeg, send, read_len, seeds,
+    hipLaunchKernelGGL(sel_gather_kernel, grid_for(p.n_reads, 64), dim3(64), 0, s, p, sbeg, send, read_len, seeds,
                        seed_chain, regs, extended, csub, work, st, meta);
     return hipGetLastError();
 }
@@ -250,7 +193,7 @@ hipError_t launch_sel_step(const SelParams &p, const int32_t *list, int32_t n, c
                            int32_t *next_cnt, int32_t *kept, int32_t *meta, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sel_step_kernel, grid_of(n, 64), dim3(64), 0, s, p, list, n, pairs, sbeg, reads, read_off,
+    hipLaunchKernelGGL(sel_step_kernel, grid_for(n, 64), dim3(64), 0, s, p, list, n, pairs, sbeg, reads, read_off,
                        frac_rep, ref, work, st, zbuf, next, next_cnt, kept, meta);
     return hipGetLastError();
 }
@@ -260,15 +203,9 @@ hipError_t launch_sel_build(const SelParams &p, const int32_t *list, int32_t nj,
                             const uint8_t *ref, SeqPair *pairs, uint8_t *qbuf, uint8_t *tbuf, hipStream_t s)
 {
     if (nj <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sel_build_kernel, grid_of((int64_t)nj * 16, 256), dim3(256), 0, s, p, list, nj, sbeg, reads,
+    hipLaunchKernelGGL(sel_build_kernel, grid_for((int64_t)nj * 16, 256), dim3(256), 0, s, p, list, nj, sbeg, reads,
                        read_off, work, st, ref, pairs, qbuf, tbuf);
     return hipGetLastError();
-}
-
-hipError_t launch_sel_scan(void *tmp, size_t *tmp_bytes, const int32_t *kept, int32_t *first, int32_t n_reads,
-                           hipStream_t s)
-{
-    return hipcub::DeviceScan::ExclusiveSum(tmp, *tmp_bytes, kept, first, n_reads + 1, s);
 }
 
 hipError_t launch_sel_emit(const SelParams &p, const int32_t *seed_read, const int32_t *sbeg, const int32_t *kept,
@@ -276,8 +213,8 @@ hipError_t launch_sel_emit(const SelParams &p, const int32_t *seed_read, const i
                            int32_t *sel_read, bsw_selinfo_t *sel_info, hipStream_t s)
 {
     if (p.n_seeds <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sel_emit_kernel, grid_of(p.n_seeds, 256), dim3(256), 0, s, p, seed_read, sbeg, kept, first, work,
-                       frac_rep, sel_regs, sel_read, sel_info);
+    hipLaunchKernelGGL(sel_emit_kernel, grid_for(p.n_seeds, 256), dim3(256), 0, s, p, seed_read, sbeg, kept, first,
+                       work, frac_rep, sel_regs, sel_read, sel_info);
     return hipGetLastError();
 }
 

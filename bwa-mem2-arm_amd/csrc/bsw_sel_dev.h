@@ -1,8 +1,8 @@
 // bsw_sel_dev.h -- device code shared by region selection (bsw_sel.hip), the paired-end stage
 // (bsw_pe.hip) and mate rescue (bsw_matesw.hip): a region's moves as 16-byte words, klib's
-// ks_introsort with its explicit stack in LDS, bwa's hash_64, primary marking and MAPQ, the dedup
-// loop and its drops and sorts as include/bsw_sel.h states them.  Plain C++ with vector stores only;
-// no private arrays.
+// ks_introsort with its explicit stack in LDS, a work entry from / to the (region, info) pair the
+// stages exchange, bwa's hash_64, primary marking and MAPQ, the dedup loop and its drops and sorts
+// as include/bsw_sel.h states them.  Plain C++ with vector stores only; no private arrays.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,6 +33,22 @@ __device__ __forceinline__ void sel_swap(SelW *x, SelW *y)
     const SelRaw a = sel_ld(x), b = sel_ld(y);
     sel_st(x, b);
     sel_st(y, a);
+}
+
+// (bsw_alnreg_t, bsw_selinfo_t), as the stages pass a region on, -> its work entry and back.  The
+// info's frac_rep belongs to the read, not to the entry: the caller keeps it and says what hash holds.
+__device__ __forceinline__ void selw_load(SelW &x, const bsw_alnreg_t &r, const bsw_selinfo_t &f, uint64_t hash)
+{
+    x.r = r;
+    x.seedcov = f.seedcov; x.sub = f.sub; x.csub = f.csub; x.sub_n = f.sub_n; x.n_comp = f.n_comp;
+    x.secondary = f.secondary; x.src = f.src; x.mapq = f.mapq; x.hash = hash;
+}
+__device__ __forceinline__ bsw_selinfo_t selw_info(const SelW &x, float frac_rep)
+{
+    bsw_selinfo_t f;
+    f.seedcov = x.seedcov; f.sub = x.sub; f.csub = x.csub; f.sub_n = x.sub_n; f.n_comp = x.n_comp;
+    f.secondary = x.secondary; f.mapq = x.mapq; f.src = x.src; f.frac_rep = frac_rep;
+    return f;
 }
 
 // comparators over small keys (a pivot kept as a whole SelW went to scratch); E = the element

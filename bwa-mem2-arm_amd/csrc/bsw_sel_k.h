@@ -34,9 +34,6 @@ constexpr int kSelErr = 0, kSelRegsIn = 1, kSelRedundant = 2, kSelIdentical = 3,
               kSelRatio = 6, kSelMaxQ = 7, kSelMaxT = 8, kSelCnt = 9 /* , 10: job counts (ping-pong) */,
               kSelMetaWords = 16;
 
-// sbeg[r], send[r] (zeroed first) = read r's run of seed slots; meta[kSelErr] on a bad or unsorted read id
-hipError_t launch_sel_runs(const int32_t *seed_read, int32_t n_seeds, int32_t n_reads, int32_t *sbeg, int32_t *send,
-                           int32_t *meta, hipStream_t s);
 // Per read: av in upstream's order with seedcov / csub into work[sbeg[r] ...], st[r].n; validation.
 hipError_t launch_sel_gather(const SelParams &p, const int32_t *sbeg, const int32_t *send, const int32_t *read_len,
                              const bsw_seed_t *seeds, const int32_t *seed_chain, const bsw_alnreg_t *regs,
@@ -55,11 +52,7 @@ hipError_t launch_sel_step(const SelParams &p, const int32_t *list, int32_t n, c
 hipError_t launch_sel_build(const SelParams &p, const int32_t *list, int32_t nj, const int32_t *sbeg,
                             const uint8_t *reads, const int64_t *read_off, const SelW *work, const SelRd *st,
                             const uint8_t *ref, SeqPair *pairs, uint8_t *qbuf, uint8_t *tbuf, hipStream_t s);
-// first[0 .. n_reads] = exclusive scan of kept[0 .. n_reads] (kept[n_reads] = 0); tmp == nullptr
-// only sizes *tmp_bytes.
-hipError_t launch_sel_scan(void *tmp, size_t *tmp_bytes, const int32_t *kept, int32_t *first, int32_t n_reads,
-                           hipStream_t s);
-// The kept regions of every read, compact, to the caller's arrays.
+// The kept regions of every read, compact, to the caller's arrays (first = launch_scan32 of kept).
 hipError_t launch_sel_emit(const SelParams &p, const int32_t *seed_read, const int32_t *sbeg, const int32_t *kept,
                            const int32_t *first, const SelW *work, const float *frac_rep, bsw_alnreg_t *sel_regs,
                            int32_t *sel_read, bsw_selinfo_t *sel_info, hipStream_t s);

@@ -18,6 +18,7 @@
 #include "bsw_pe_k.h"
 #include "bsw_matesw_k.h"
 #include "bsw_rec_k.h"
+#include "bsw_stage_k.h"
 
 // ---------------------------------------------------------------- shared by the stages
 namespace bsw {
@@ -355,7 +356,7 @@ static int regs_select_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_
     make_glob_params(pr, ctx->glob_band, gp);
     const size_t nr = (size_t)n_reads, ns = (size_t)n_seeds;
     size_t scan_bytes = 0;
-    BSW_TRY(launch_sel_scan(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
+    BSW_TRY(launch_scan32(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
     BSW_TRY(s.d_swork.grow(std::max<size_t>(ns, 1)));
     BSW_TRY(s.d_sz.grow(std::max<size_t>(ns, 1)));
     BSW_TRY(s.d_sst.grow(std::max<size_t>(nr, 1)));
@@ -372,7 +373,7 @@ static int regs_select_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_
     BSW_TRY(hipMemsetAsync(s.d_srun, 0, (2 * nr + 1) * sizeof(int32_t), st));
     BSW_TRY(hipMemsetAsync(s.d_skept, 0, (nr + 1) * sizeof(int32_t), st));
     BSW_TRY(hipMemsetAsync(s.d_smeta, 0, kSelMetaWords * sizeof(int32_t), st));
-    BSW_TRY(launch_sel_runs(io.seed_read, n_seeds, n_reads, sbeg, send, s.d_smeta, st));
+    BSW_TRY(launch_seed_runs(io.seed_read, n_seeds, n_reads, sbeg, send, s.d_smeta + kSelErr, st));
     BSW_TRY(launch_sel_gather(p, sbeg, send, io.read_len, io.seeds, io.seed_chain, io.regs, io.extended, io.csub,
                               s.d_swork, s.d_sst, s.d_smeta, st));
     BSW_TRY(launch_sel_step(p, nullptr, n_reads, nullptr, sbeg, io.reads, io.read_off, io.frac_rep, dc.d_refres,
@@ -421,7 +422,7 @@ static int regs_select_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_
     ss.n_patch_ok = h_meta[kSelOk];
     ss.n_patch_ratio = h_meta[kSelRatio];
     BSW_TRY(tm.begin());
-    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, s.d_skept, io.read_first, n_reads, st));
+    BSW_TRY(launch_scan32(s.d_tmp, &scan_bytes, s.d_skept, io.read_first, n_reads, st));
     BSW_TRY(hipMemcpyAsync(h_meta, io.read_first + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     BSW_TRY(hipStreamSynchronize(st));
     *n_sel = ss.n_sel = h_meta[0];
@@ -904,7 +905,7 @@ static int matesw_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st,
     if ((int64_t)n_regs * 5 > INT32_MAX) return BSW_E_RANGE;        // the work lists' offsets are int32
     const size_t nr = (size_t)n_reads, np = nr / 2, n1 = nr + 1;
     size_t scan_bytes = 0;
-    BSW_TRY(launch_sel_scan(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
+    BSW_TRY(launch_scan32(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
     BSW_TRY(s.d_tmp.grow(std::max<size_t>(scan_bytes, 16)));
     BSW_TRY(s.d_wint.grow(5 * n1 + 2 * np + 1));
     BSW_TRY(s.d_wmeta.grow(kMswSlots * kMswMetaWords));
@@ -922,8 +923,8 @@ static int matesw_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st,
     BSW_TRY(hipMemsetAsync(s.d_wmeta, 0, kMetaBytes, st));
     BSW_TRY(tm.begin());
     BSW_TRY(launch_msw_count(p, io.regs, io.first, ncand, capv, s.d_wmeta, st));
-    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, ncand, coff, n_reads, st));
-    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, capv, woff, n_reads, st));
+    BSW_TRY(launch_scan32(s.d_tmp, &scan_bytes, ncand, coff, n_reads, st));
+    BSW_TRY(launch_scan32(s.d_tmp, &scan_bytes, capv, woff, n_reads, st));
     BSW_TRY(tm.end());
     BSW_TRY(hipMemcpyAsync(h_meta, s.d_wmeta, kMswMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     BSW_TRY(hipMemcpyAsync(h_meta + kMswMetaWords, coff + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -981,7 +982,7 @@ static int matesw_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st,
         ws.n_lists_changed += m[kMswChanged];
     }
     BSW_TRY(tm.begin());
-    BSW_TRY(launch_sel_scan(s.d_tmp, &scan_bytes, nlist, io.out_first, n_reads, st));
+    BSW_TRY(launch_scan32(s.d_tmp, &scan_bytes, nlist, io.out_first, n_reads, st));
     BSW_TRY(hipMemcpyAsync(h_meta, io.out_first + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     BSW_TRY(hipStreamSynchronize(st));
     *n_out = ws.n_out = h_meta[0];
@@ -1142,7 +1143,7 @@ static int records_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st
     p.mask_level = opt.mask_level; p.xa_ratio = (double)opt.XA_drop_ratio;
     const size_t nr = (size_t)n_reads, n1 = nr + 1;
     size_t scan_bytes = 0;
-    BSW_TRY(launch_rec_scan32(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
+    BSW_TRY(launch_scan32(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
     BSW_TRY(s.d_tmp.grow(std::max<size_t>(scan_bytes, 16)));
     BSW_TRY(s.d_rcnt.grow(3 * n1));
     BSW_TRY(s.d_rmeta.grow(kRecMetaWords + kRecNameWords));
@@ -1154,8 +1155,8 @@ static int records_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st
     BSW_TRY(hipMemsetAsync(s.d_rmeta, 0, kRecMetaWords * sizeof(int32_t), st));
     BSW_TRY(tm.begin());
     BSW_TRY(launch_rec_count(p, io.lists, nrec, naln, s.d_rmeta, st));
-    BSW_TRY(launch_rec_scan32(s.d_tmp, &scan_bytes, nrec, io.rec_first, n_reads, st));
-    BSW_TRY(launch_rec_scan32(s.d_tmp, &scan_bytes, naln, aln_first, n_reads, st));
+    BSW_TRY(launch_scan32(s.d_tmp, &scan_bytes, nrec, io.rec_first, n_reads, st));
+    BSW_TRY(launch_scan32(s.d_tmp, &scan_bytes, naln, aln_first, n_reads, st));
     BSW_TRY(tm.end());
     BSW_TRY(hipMemcpyAsync(h_meta, s.d_rmeta, kRecMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     BSW_TRY(hipMemcpyAsync(h_meta + kRecMetaWords, io.rec_first + nr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1228,7 +1229,7 @@ static int sam_text_device(Slot &s, hipStream_t st, const bsw_rec_opt_t &opt, Re
 {
     *n_bytes = 0;
     size_t scan_bytes = 0;
-    BSW_TRY(launch_rec_scan64(nullptr, &scan_bytes, nullptr, nullptr, t.n_rec, st));
+    BSW_TRY(launch_scan64(nullptr, &scan_bytes, nullptr, nullptr, t.n_rec, st));
     BSW_TRY(s.d_tmp.grow(std::max<size_t>(scan_bytes, 16)));
     BSW_TRY(s.d_rlen.grow((size_t)t.n_rec + 1));
     BSW_TRY(s.d_rmeta.grow(kRecMetaWords + kRecNameWords));
@@ -1243,7 +1244,7 @@ static int sam_text_device(Slot &s, hipStream_t st, const bsw_rec_opt_t &opt, Re
     t.rname = (const uint8_t *)(s.d_rmeta + kRecMetaWords);
     BSW_TRY(tm.begin());
     BSW_TRY(launch_rec_text_len(t, s.d_rlen, s.d_rmeta, st));
-    BSW_TRY(launch_rec_scan64(s.d_tmp, &scan_bytes, s.d_rlen, io.text_off, t.n_rec, st));
+    BSW_TRY(launch_scan64(s.d_tmp, &scan_bytes, s.d_rlen, io.text_off, t.n_rec, st));
     BSW_TRY(tm.end());
     BSW_TRY(hipMemcpyAsync(s.h_meta, s.d_rmeta, kRecMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     BSW_TRY(hipMemcpyAsync(h_tot, io.text_off + t.n_rec, sizeof(int64_t), hipMemcpyDeviceToHost, st));

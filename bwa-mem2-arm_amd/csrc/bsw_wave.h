@@ -28,7 +28,14 @@ __device__ __forceinline__ int wave_min(int x)
     return min(min(a, b), min(c, d));
 }
 
-// Same reductions with the row combination done by DPP row_bcast:15 / row_bcast:31 (gfx9 DPP)
+// Wave-uniform sum over all 64 lanes (exec must be full): a butterfly of cross-lane reads.
+__device__ __forceinline__ int wave_sum(int x)
+{
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+
+// wave_max / wave_min with the row combination done by DPP row_bcast:15 / row_bcast:31 (gfx9 DPP)
 // instead of four v_readlane: 6 DPP ops + one v_readlane of lane 63.
 __device__ __forceinline__ int wave_max_bc(int x)
 {
