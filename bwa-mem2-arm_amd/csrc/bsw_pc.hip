@@ -28,7 +28,8 @@
 // beyond end keep their stale values, A.7: a later row whose end grows by 2 reads them), put
 // E = 0 at slot end, drop slots > end (and < beg) from the key, and pass H(i, end-1) along the
 // chain (h1 at row end = H(i, end-1), for gscore and the lazy last-positive scan).  Groups that
-// contain some lane's beg also reset F and H to 0 entering column beg.  Slots left of beg may
+// contain some lane's beg (L) also reset F and H to 0 entering column beg, on a per-cell chain;
+// the others (R: right edge only) run the FAST packed chain (PC_REDGE).  Slots left of beg may
 // take garbage: they are never read again (beg never decreases).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -177,7 +178,9 @@ __device__ __forceinline__ uint32_t pack2(int v) { return ((uint32_t)v & 0xffffu
 // A1 reads the entering h1 (H(4G-1) in its high half) and pa = {H(4G), H(4G+1)}; A2 the leaving
 // h1 = {H(4G+2), H(4G+3)}: the int16 form builds HH[2G], HH[2G+1]; the byte form (BY) builds
 // HB[G] = bytes {H(4G-1), H(4G), H(4G+1), H(4G+2)} by two v_perm (the same instruction count)
-#define PC_FAST_CHAIN_(A1, A2)                                                           \
+#define PC_FAST_CHAIN_(A1, A2) PC_FAST_CHAIN__(A1, A2, "%[h1]")
+// H1O: the register the leaving h1 is written to (the right-edge body keeps the entering one)
+#define PC_FAST_CHAIN__(A1, A2, H1O)                                                     \
     "v_pk_sub_u16 %[fp], %[f], %[e0e] op_sel_hi:[0,1] clamp\n\t"                            \
     "v_pk_max_i16 %[fp], %[fp], %[ta] op_sel_hi:[1,0]\n\t"                                  \
     "v_pk_max_i16 %[pa], %[fp], %[sa]\n\t"                                                  \
@@ -186,16 +189,109 @@ __device__ __forceinline__ uint32_t pack2(int v) { return ((uint32_t)v & 0xffffu
     "v_pk_max_i16 %[fp], %[fp], %[y]\n\t"                                                   \
     A1                                                                                       \
     "v_pk_max_i16 %[fp], %[fp], %[tb] op_sel_hi:[1,0]\n\t"                                  \
-    "v_pk_max_i16 %[h1], %[fp], %[sb]\n\t"                                                  \
+    "v_pk_max_i16 " H1O ", %[fp], %[sb]\n\t"                                                \
     "v_sub_u32_sdwa %[f], %[fp], %[ed] clamp dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD\n\t" \
     A2                                                                                       \
     PC_SDWA("v_max_i32", "%[f]", "%[f]", "sext(%[tb])", "WORD_1")
+
+// Right-edge (masked-R) group on the packed chain (BSW_PC_RIGHT_EDGE 0: the
+// per-cell PC_MASKED form).  An R group holds no lane's beg, so the entering f / h1 are valid for
+// every lane it matters to and the FAST chain gives H(4G..4G+3) for all of them at once; columns
+// at or past a lane's end run on stale inputs, bounded like any cell's, and are never written.
+// The chain leaves its h1 in c1, the new-row candidates are the FAST byte-aligns (c0 = slots
+// {4G, 4G+1}, pb = slots {4G+2, 4G+3}), and per-lane masks from end do the rest:
+//   sa = slots {4G, 4G+1} <= end, sb = slots {4G+2, 4G+3} <= end, ta / tb = the same slots < end
+//   (ta = {sa.hi, sb.lo}: slot s <= end is slot s - 1 < end)
+//   HH <- candidate under sa / sb; EE <- E' & (slot < end) under sa / sb (0 at slot end, stale
+//   beyond); key halves & sa / sb
+//   h1 carry: v(s) = the value of slot s (v(4G) = the entering h1) sits in the HIGH half of
+//   h1, c0, pa, pb, c1 for s = 4G .. 4G+4, and slot s <= end in the high half of sa, ta, sb, tb
+//   for s = 4G+1 .. 4G+4: four v_bfi leave h1 = v(clamp(end, 4G, 4G+4)) = H(i, end-1) for a lane
+//   whose end lies in or below the group, H(4G+3) for a lane wholly in band.  (f is dead for a
+//   lane past its end: every later group is masked out for it.)
+// KA / KB build the key halves from c0 / pb into fp / c2.  51 VALU with the scores (60 before).
+#ifndef BSW_PC_RIGHT_EDGE
+#define BSW_PC_RIGHT_EDGE 1
+#endif
+#define PC_REDGE(PH, KA, KB)                                                             \
+    PH("a", "%[xa]") PH("b", "%[xb]")                                                        \
+    PC_FAST_CHAIN__("v_alignbyte_b32 %[c0], %[pa], %[h1], 2\n\t",                            \
+                    "v_alignbyte_b32 %[pb], %[c1], %[pa], 2\n\t", "%[c1]")                   \
+    KA KB                                                                                    \
+    "v_pk_sub_i16 %[sa], %[jja], %[endw]\n\t"                                                \
+    "v_pk_sub_i16 %[sb], %[jjb], %[endw]\n\t"                                                \
+    "v_pk_sub_i16 %[tb], %[jjb], %[endm1w]\n\t"                                              \
+    "v_pk_ashrrev_i16 %[sa], 15, %[sa] op_sel_hi:[0,1]\n\t"                                  \
+    "v_pk_ashrrev_i16 %[sb], 15, %[sb] op_sel_hi:[0,1]\n\t"                                  \
+    "v_pk_ashrrev_i16 %[tb], 15, %[tb] op_sel_hi:[0,1]\n\t"                                  \
+    "v_alignbyte_b32 %[ta], %[sb], %[sa], 2\n\t"                                             \
+    "v_bfi_b32 %[h1], %[sa], %[c0], %[h1]\n\t"                                               \
+    "v_bfi_b32 %[ha], %[sa], %[c0], %[ha]\n\t"                                               \
+    "v_and_b32_e32 %[xa], %[xa], %[ta]\n\t"                                                  \
+    "v_bfi_b32 %[h1], %[ta], %[pa], %[h1]\n\t"                                               \
+    "v_bfi_b32 %[ea], %[sa], %[xa], %[ea]\n\t"                                               \
+    "v_and_b32_e32 %[fp], %[fp], %[sa]\n\t"                                                  \
+    "v_bfi_b32 %[h1], %[sb], %[pb], %[h1]\n\t"                                               \
+    "v_bfi_b32 %[hb], %[sb], %[pb], %[hb]\n\t"                                               \
+    "v_and_b32_e32 %[xb], %[xb], %[tb]\n\t"                                                  \
+    "v_bfi_b32 %[h1], %[tb], %[c1], %[h1]\n\t"                                               \
+    "v_bfi_b32 %[eb], %[sb], %[xb], %[eb]\n\t"                                               \
+    "v_and_b32_e32 %[c2], %[c2], %[sb]\n\t"                                                  \
+    "v_pk_max_u16 %[key], %[key], %[fp]\n\t"                                                 \
+    "v_pk_max_u16 %[key], %[key], %[c2]\n\t"
+// the R body of a group: the packed form above, or the per-cell one (h1 as a clean int inside)
+#if BSW_PC_RIGHT_EDGE
+#define PC_RBODY(PH, KA_M, KB_M, KA_R, KB_R) PC_REDGE(PH, KA_R, KB_R)
+#else
+#define PC_RBODY(PH, KA_M, KB_M, KA_R, KB_R)                                             \
+    "v_lshrrev_b32_e32 %[h1], 16, %[h1]\n\t"                                                 \
+    PC_MASKED_(PH, PC_MCELL("%[c0]", "%[h1]", "a", "WORD_0", "%[j0]"),                       \
+                   PC_MCELL("%[c1]", "%[c0]", "a", "WORD_1", "%[j1]"),                       \
+                   PC_MCELL("%[c2]", "%[c1]", "b", "WORD_0", "%[j2]"),                       \
+                   PC_MCELL("%[h1]", "%[c2]", "b", "WORD_1", "%[j3]"), KA_M, KB_M, "", "")   \
+    "v_lshlrev_b32_e32 %[h1], 16, %[h1]\n\t"
+#endif
+#define PC_LBODY(PH, KA_M, KB_M)                                                         \
+    "v_lshrrev_b32_e32 %[h1], 16, %[h1]\n\t"         /* per-cell chain: h1 as a clean int */ \
+    PC_MASKED_(PH, PC_RESET("%[h1]", "%[r0]") PC_MCELL("%[c0]", "%[h1]", "a", "WORD_0", "%[j0]"), \
+                   PC_RESET("%[c0]", "%[j1]") PC_MCELL("%[c1]", "%[c0]", "a", "WORD_1", "%[j1]"), \
+                   PC_RESET("%[c1]", "%[j2]") PC_MCELL("%[c2]", "%[c1]", "b", "WORD_0", "%[j2]"), \
+                   PC_RESET("%[c2]", "%[j3]") PC_MCELL("%[h1]", "%[c2]", "b", "WORD_1", "%[j3]"), \
+                   KA_M, KB_M, PC_LEFTMASK("a"), PC_LEFTMASK("b"))                           \
+    "v_lshlrev_b32_e32 %[h1], 16, %[h1]\n\t"
+
+// the out-of-line part of a group (subsection 1): skip test, then the L or the R body.  PRE: what
+// the masked bodies need first (their key constants, the byte planes' unpack); POST: the byte
+// planes' pack
+#define PC_OUTOFLINE(PRE, PH, KA_M, KB_M, KA_R, KB_R, POST)                              \
+    ".subsection 1\n"                                                                        \
+    "5:\n\t"                                                                                 \
+    "s_bitcmp1_b64 %[men], %[g]\n\t"                 /* outside [min beg, max end]: skip */ \
+    "s_cbranch_scc0 3b\n\t"                                                                  \
+    "s_setprio 2\n\t"                                /* masked bodies: short per-cell chains */\
+    PC_CNT(0)                                                                                \
+    PRE                                                                                      \
+    PC_SCORES                                                                                \
+    "s_bitcmp1_b64 %[mle], %[g]\n\t"                 /* some lane's beg in this group: L */ \
+    "s_cbranch_scc1 4f\n\t"                                                                  \
+    PC_CNT(2)                                                                                \
+    PC_RBODY(PH, KA_M, KB_M, KA_R, KB_R)                                                     \
+    POST                                                                                     \
+    "s_setprio 0\n\t"                                                                        \
+    "s_branch 3b\n"                                                                          \
+    "4:\n\t"                                                                                 \
+    PC_CNT(3)                                                                                \
+    PC_LBODY(PH, KA_M, KB_M)                                                                 \
+    POST                                                                                     \
+    "s_setprio 0\n\t"                                                                        \
+    "s_branch 3b\n"                                                                          \
+    ".subsection 0\n"
 
 // Layout: the FAST body is the fall-through path (one bit test, a not-taken branch, no taken
 // branch); skipped and masked groups branch to code in subsection 1 of the kernel's section
 // (out of line, after the kernel's main body) and back.  Branch targets stay inside the
 // kernel's own section (built with -ffunction-sections), well within s_cbranch's +-128 KB.
-#define PC_GROUP_ASM(KEYA_FAST, KEYA_MASK)                                                \
+#define PC_GROUP_ASM(KEYA_FAST, KEYA_MASK, KEYA_R)                                        \
     asm volatile(                                                                            \
         "s_bitcmp1_b64 %[mfa], %[g]\n\t"             /* every live lane in band: FAST */    \
         "s_cbranch_scc0 5f\n\t"                                                              \
@@ -208,37 +304,8 @@ __device__ __forceinline__ uint32_t pack2(int v) { return ((uint32_t)v & 0xffffu
         "v_lshl_or_b32 %[pb], %[hb], 8, %[jjb]\n\t"                                          \
         "v_pk_max_u16 %[key], %[key], %[pb]\n"                                               \
         "3:\n"                                                                               \
-        ".subsection 1\n"                                                                    \
-        "5:\n\t"                                                                             \
-        "s_bitcmp1_b64 %[men], %[g]\n\t"             /* outside [min beg, max end]: skip */ \
-        "s_cbranch_scc0 3b\n\t"                                                              \
-        "s_setprio 2\n\t"                            /* masked bodies: short per-cell chains */\
-        PC_CNT(0)                                                                            \
-        "v_lshrrev_b32_e32 %[h1], 16, %[h1]\n\t"     /* masked bodies: h1 as a clean int */ \
-        PC_SCORES                                                                            \
-        "s_bitcmp1_b64 %[mle], %[g]\n\t"             /* some lane's beg in this group: L */ \
-        "s_cbranch_scc1 4f\n\t"                                                              \
-        PC_CNT(2)                                                                            \
-        PC_MASKED(PC_MCELL("%[c0]", "%[h1]", "a", "WORD_0", "%[j0]"),                        \
-                  PC_MCELL("%[c1]", "%[c0]", "a", "WORD_1", "%[j1]"),                        \
-                  PC_MCELL("%[c2]", "%[c1]", "b", "WORD_0", "%[j2]"),                        \
-                  PC_MCELL("%[h1]", "%[c2]", "b", "WORD_1", "%[j3]"),                        \
-                  KEYA_MASK, "v_lshl_or_b32 %[pb], %[pb], 8, %[jjb]\n\t", "", "")           \
-        "v_lshlrev_b32_e32 %[h1], 16, %[h1]\n\t"                                              \
-        "s_setprio 0\n\t"                                                                    \
-        "s_branch 3b\n"                                                                      \
-        "4:\n\t"                                                                             \
-        PC_CNT(3)                                                                            \
-        PC_MASKED(PC_RESET("%[h1]", "%[r0]") PC_MCELL("%[c0]", "%[h1]", "a", "WORD_0", "%[j0]"), \
-                  PC_RESET("%[c0]", "%[j1]") PC_MCELL("%[c1]", "%[c0]", "a", "WORD_1", "%[j1]"), \
-                  PC_RESET("%[c1]", "%[j2]") PC_MCELL("%[c2]", "%[c1]", "b", "WORD_0", "%[j2]"), \
-                  PC_RESET("%[c2]", "%[j3]") PC_MCELL("%[h1]", "%[c2]", "b", "WORD_1", "%[j3]"), \
-                  KEYA_MASK, "v_lshl_or_b32 %[pb], %[pb], 8, %[jjb]\n\t",                    \
-                  PC_LEFTMASK("a"), PC_LEFTMASK("b"))                                        \
-        "v_lshlrev_b32_e32 %[h1], 16, %[h1]\n\t"                                              \
-        "s_setprio 0\n\t"                                                                    \
-        "s_branch 3b\n"                                                                      \
-        ".subsection 0\n"                                                                    \
+        PC_OUTOFLINE("", PC_PH1, KEYA_MASK, "v_lshl_or_b32 %[pb], %[pb], 8, %[jjb]\n\t",     \
+                     KEYA_R, "v_lshl_or_b32 %[c2], %[pb], 8, %[jjb]\n\t", "")                \
         : [ha] "+v"(ha), [hb] "+v"(hb), [ea] "+v"(ea), [eb] "+v"(eb), [f] "+v"(f),           \
           [h1] "+v"(h1), [key] "+v"(key), [y] "=&v"(y), [sa] "=&v"(sa), [sb] "=&v"(sb),     \
           [ta] "=&v"(ta), [tb] "=&v"(tb), [xa] "=&v"(xa), [xb] "=&v"(xb), [c0] "=&v"(c0),    \
@@ -274,41 +341,12 @@ __device__ __forceinline__ uint32_t pack2(int v) { return ((uint32_t)v & 0xffffu
         "v_perm_b32 %[pb], %[hb], %[j4], %[skb]\n\t"                                         \
         "v_pk_max_u16 %[key], %[key], %[pb]\n"                                               \
         "3:\n"                                                                               \
-        ".subsection 1\n"                                                                    \
-        "5:\n\t"                                                                             \
-        "s_bitcmp1_b64 %[men], %[g]\n\t"                                                     \
-        "s_cbranch_scc0 3b\n\t"                                                              \
-        "s_setprio 2\n\t"                                                                    \
-        PC_CNT(0)                                                                            \
-        "s_mov_b32 %[jja], %[ija]\n\t"               /* packed {4G-1, 4G}, {4G+1, 4G+2} */ \
-        "s_mov_b32 %[jjb], %[ijb]\n\t"                                                       \
-        "v_lshrrev_b32_e32 %[h1], 16, %[h1]\n\t"                                             \
-        PC_SCORES                                                                            \
-        "s_bitcmp1_b64 %[mle], %[g]\n\t"                                                     \
-        "s_cbranch_scc1 4f\n\t"                                                              \
-        PC_CNT(2)                                                                            \
-        PC_MASKED(PC_MCELL("%[c0]", "%[h1]", "a", "WORD_0", "%[j0]"),                        \
-                  PC_MCELL("%[c1]", "%[c0]", "a", "WORD_1", "%[j1]"),                        \
-                  PC_MCELL("%[c2]", "%[c1]", "b", "WORD_0", "%[j2]"),                        \
-                  PC_MCELL("%[h1]", "%[c2]", "b", "WORD_1", "%[j3]"),                        \
-                  "v_perm_b32 %[pa], %[pa], %[j4], %[ska]\n\t",                              \
-                  "v_perm_b32 %[pb], %[pb], %[j4], %[skb]\n\t", "", "")                      \
-        "v_lshlrev_b32_e32 %[h1], 16, %[h1]\n\t"                                              \
-        "s_setprio 0\n\t"                                                                    \
-        "s_branch 3b\n"                                                                      \
-        "4:\n\t"                                                                             \
-        PC_CNT(3)                                                                            \
-        PC_MASKED(PC_RESET("%[h1]", "%[r0]") PC_MCELL("%[c0]", "%[h1]", "a", "WORD_0", "%[j0]"), \
-                  PC_RESET("%[c0]", "%[j1]") PC_MCELL("%[c1]", "%[c0]", "a", "WORD_1", "%[j1]"), \
-                  PC_RESET("%[c1]", "%[j2]") PC_MCELL("%[c2]", "%[c1]", "b", "WORD_0", "%[j2]"), \
-                  PC_RESET("%[c2]", "%[j3]") PC_MCELL("%[h1]", "%[c2]", "b", "WORD_1", "%[j3]"), \
-                  "v_perm_b32 %[pa], %[pa], %[j4], %[ska]\n\t",                              \
-                  "v_perm_b32 %[pb], %[pb], %[j4], %[skb]\n\t",                              \
-                  PC_LEFTMASK("a"), PC_LEFTMASK("b"))                                        \
-        "v_lshlrev_b32_e32 %[h1], 16, %[h1]\n\t"                                              \
-        "s_setprio 0\n\t"                                                                    \
-        "s_branch 3b\n"                                                                      \
-        ".subsection 0\n"                                                                    \
+        PC_OUTOFLINE("s_mov_b32 %[jja], %[ija]\n\t"   /* packed {4G-1, 4G}, {4G+1, 4G+2} */  \
+                     "s_mov_b32 %[jjb], %[ijb]\n\t", PC_PH1,                                 \
+                     "v_perm_b32 %[pa], %[pa], %[j4], %[ska]\n\t",                           \
+                     "v_perm_b32 %[pb], %[pb], %[j4], %[skb]\n\t",                           \
+                     "v_perm_b32 %[fp], %[c0], %[j4], %[ska]\n\t",                           \
+                     "v_perm_b32 %[c2], %[pb], %[j4], %[skb]\n\t", "")                       \
         : [ha] "+v"(ha), [hb] "+v"(hb), [ea] "+v"(ea), [eb] "+v"(eb), [f] "+v"(f),           \
           [h1] "+v"(h1), [key] "+v"(key), [y] "=&v"(y), [sa] "=&v"(sa), [sb] "=&v"(sb),     \
           [ta] "=&v"(ta), [tb] "=&v"(tb), [xa] "=&v"(xa), [xb] "=&v"(xb), [c0] "=&v"(c0),    \
@@ -345,18 +383,22 @@ __device__ __forceinline__ void pc_group(uint32_t &ha, uint32_t &hb, uint32_t &e
     uint32_t y, sa, sb, ta, tb, xa, xb, c0, c1, c2, pa, pb, fp;
     const uint32_t e0e = (uint32_t)ed << 16;                          // {0, e}
     const uint32_t ee2 = (uint32_t)ed | ((uint32_t)(2 * ed) << 16);   // {e, 2e}
+#define PC_K0_FAST "v_lshlrev_b32_e32 %[pa], 24, %[pa]\n\t"           /* pa = {H(0), H(1)} here */
+#define PC_K0_MASK "v_lshl_or_b32 %[pa], %[c0], 24, 0\n\t"
+#define PC_K0_R "v_lshlrev_b32_e32 %[fp], 24, %[pa]\n\t"
+#define PC_KA_FAST "v_lshl_or_b32 %[pa], %[ha], 8, %[jja]\n\t"
+#define PC_KA_MASK "v_lshl_or_b32 %[pa], %[pa], 8, %[jja]\n\t"
+#define PC_KA_R "v_lshl_or_b32 %[fp], %[c0], 8, %[jja]\n\t"
     if constexpr (G == 0) {
         // slot 0 holds the column-0 boundary, not a cell: its key half is 0 (c0 << 24 | 0)
-        PC_GROUP_ASM("v_lshlrev_b32_e32 %[pa], 24, %[pa]\n\t",        /* pa = {H(0), H(1)} here */
-                     "v_lshl_or_b32 %[pa], %[c0], 24, 0\n\t");
+        PC_GROUP_ASM(PC_K0_FAST, PC_K0_MASK, PC_K0_R);
     } else if constexpr (JK) {
         constexpr uint32_t J4 = (uint32_t)(4 * G - 1) | ((uint32_t)(4 * G) << 8) | ((uint32_t)(4 * G + 1) << 16) |
                                 ((uint32_t)(4 * G + 2) << 24);
         uint32_t tja, tjb;
         PC_GROUP_ASM_J;
     } else {
-        PC_GROUP_ASM("v_lshl_or_b32 %[pa], %[ha], 8, %[jja]\n\t",
-                     "v_lshl_or_b32 %[pa], %[pa], 8, %[jja]\n\t");
+        PC_GROUP_ASM(PC_KA_FAST, PC_KA_MASK, PC_KA_R);
     }
 }
 
@@ -387,7 +429,7 @@ constexpr uint32_t kSelK0 = 0x050C0C0Cu;       // group 0: {0, 0, 0, HB.b1} (slo
     "v_perm_b32 %[hw], %[hb], %[ha], %[spk]\n\t"                                             \
     "v_perm_b32 %[ew], %[eb], %[ea], %[spk]\n\t"
 
-#define PCB_GROUP_ASM(KEYA_FAST, KEYA_MASK)                                               \
+#define PCB_GROUP_ASM(KEYA_FAST, KEYA_MASK, KEYA_R)                                       \
     asm volatile(                                                                            \
         "s_bitcmp1_b64 %[mfa], %[g]\n\t"             /* every live lane in band: FAST */    \
         "s_cbranch_scc0 5f\n\t"                                                              \
@@ -403,42 +445,8 @@ constexpr uint32_t kSelK0 = 0x050C0C0Cu;       // group 0: {0, 0, 0, HB.b1} (slo
         "v_perm_b32 %[pb], %[hw], %[jjb], %[vkb]\n\t"                                        \
         "v_pk_max_u16 %[key], %[key], %[pb]\n"                                               \
         "3:\n"                                                                               \
-        ".subsection 1\n"                                                                    \
-        "5:\n\t"                                                                             \
-        "s_bitcmp1_b64 %[men], %[g]\n\t"             /* outside [min beg, max end]: skip */ \
-        "s_cbranch_scc0 3b\n\t"                                                              \
-        "s_setprio 2\n\t"                                                                    \
-        PC_CNT(0)                                                                            \
-        PCB_UNPACK                                                                           \
-        "v_lshrrev_b32_e32 %[h1], 16, %[h1]\n\t"                                             \
-        PC_SCORES                                                                            \
-        "s_bitcmp1_b64 %[mle], %[g]\n\t"             /* some lane's beg in this group: L */ \
-        "s_cbranch_scc1 4f\n\t"                                                              \
-        PC_CNT(2)                                                                            \
-        PC_MASKED_(PC_PH1B,                                                                  \
-                  PC_MCELL("%[c0]", "%[h1]", "a", "WORD_0", "%[j0]"),                        \
-                  PC_MCELL("%[c1]", "%[c0]", "a", "WORD_1", "%[j1]"),                        \
-                  PC_MCELL("%[c2]", "%[c1]", "b", "WORD_0", "%[j2]"),                        \
-                  PC_MCELL("%[h1]", "%[c2]", "b", "WORD_1", "%[j3]"),                        \
-                  KEYA_MASK, "v_lshl_or_b32 %[pb], %[pb], 8, %[jjb]\n\t", "", "")           \
-        PCB_PACK                                                                             \
-        "v_lshlrev_b32_e32 %[h1], 16, %[h1]\n\t"                                             \
-        "s_setprio 0\n\t"                                                                    \
-        "s_branch 3b\n"                                                                      \
-        "4:\n\t"                                                                             \
-        PC_CNT(3)                                                                            \
-        PC_MASKED_(PC_PH1B,                                                                  \
-                  PC_RESET("%[h1]", "%[r0]") PC_MCELL("%[c0]", "%[h1]", "a", "WORD_0", "%[j0]"), \
-                  PC_RESET("%[c0]", "%[j1]") PC_MCELL("%[c1]", "%[c0]", "a", "WORD_1", "%[j1]"), \
-                  PC_RESET("%[c1]", "%[j2]") PC_MCELL("%[c2]", "%[c1]", "b", "WORD_0", "%[j2]"), \
-                  PC_RESET("%[c2]", "%[j3]") PC_MCELL("%[h1]", "%[c2]", "b", "WORD_1", "%[j3]"), \
-                  KEYA_MASK, "v_lshl_or_b32 %[pb], %[pb], 8, %[jjb]\n\t",                    \
-                  PC_LEFTMASK("a"), PC_LEFTMASK("b"))                                        \
-        PCB_PACK                                                                             \
-        "v_lshlrev_b32_e32 %[h1], 16, %[h1]\n\t"                                             \
-        "s_setprio 0\n\t"                                                                    \
-        "s_branch 3b\n"                                                                      \
-        ".subsection 0\n"                                                                    \
+        PC_OUTOFLINE(PCB_UNPACK, PC_PH1B, KEYA_MASK, "v_lshl_or_b32 %[pb], %[pb], 8, %[jjb]\n\t", \
+                     KEYA_R, "v_lshl_or_b32 %[c2], %[pb], 8, %[jjb]\n\t", PCB_PACK)          \
         : [hw] "+v"(hw), [ew] "+v"(ew), [ha] "=&v"(ha), [hb] "=&v"(hb), [ea] "=&v"(ea),      \
           [eb] "=&v"(eb), [f] "+v"(f),                                                       \
           [h1] "+v"(h1), [key] "+v"(key), [y] "=&v"(y), [sa] "=&v"(sa), [sb] "=&v"(sb),     \
@@ -455,7 +463,6 @@ constexpr uint32_t kSelK0 = 0x050C0C0Cu;       // group 0: {0, 0, 0, HB.b1} (slo
           [sa2] "s"(kSelA2), [sk0] "s"(kSelK0), [vka] "v"(bs.ka), [vkb] "v"(bs.kb)            \
         : "vcc", "scc")
 
-
 template <int G>
 __device__ __forceinline__ void pcb_group(uint32_t &hw, uint32_t &ew, uint32_t q, uint32_t plo, uint32_t phi,
                                           int &f, int &h1, uint32_t &key, uint32_t oe2, uint32_t ed2, int ed,
@@ -469,12 +476,12 @@ __device__ __forceinline__ void pcb_group(uint32_t &hw, uint32_t &ew, uint32_t q
     uint32_t ha, hb, ea, eb, y, sa, sb, ta, tb, xa, xb, c0, c1, c2, pa, pb, fp;
     const uint32_t e0e = (uint32_t)ed << 16;
     const uint32_t ee2 = (uint32_t)ed | ((uint32_t)(2 * ed) << 16);
+#define PCB_K0_FAST "v_perm_b32 %[pa], %[hw], %[hw], %[sk0]\n\t"
+#define PCB_KA_FAST "v_perm_b32 %[pa], %[hw], %[jja], %[vka]\n\t"
     if constexpr (G == 0) {
-        PCB_GROUP_ASM("v_perm_b32 %[pa], %[hw], %[hw], %[sk0]\n\t",
-                      "v_lshl_or_b32 %[pa], %[c0], 24, 0\n\t");
+        PCB_GROUP_ASM(PCB_K0_FAST, PC_K0_MASK, PC_K0_R);
     } else {
-        PCB_GROUP_ASM("v_perm_b32 %[pa], %[hw], %[jja], %[vka]\n\t",
-                      "v_lshl_or_b32 %[pa], %[pa], 8, %[jja]\n\t");
+        PCB_GROUP_ASM(PCB_KA_FAST, PC_KA_MASK, PC_KA_R);
     }
 }
 

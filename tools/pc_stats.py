@@ -27,6 +27,7 @@ L.bsw_pc_stats(st, 0)
 rows, ent, fast, mr, ml, lp, waves, ue, scans, ret_s, ret_c = (int(st[k]) for k in range(NST))
 print(f"waves {waves} rows {rows} ({rows / waves:.1f}/wave)  groups entered {ent} ({ent / rows:.2f}/row)")
 print(f"FAST {fast / ent:.3f}  masked-R {mr / ent:.3f}  masked-L {ml / ent:.3f}  lastpos rows {lp / rows:.3f}")
+print(f"per row: entered {ent / rows:.2f}  FAST {fast / rows:.2f}  R {mr / rows:.3f}  L {ml / rows:.3f}")
 print(f"uniform-end rows {ue / rows:.3f} (every live lane of the wave at the same band end)")
 print(f"early stop: scan rows {scans} ({scans / waves:.2f}/wave)  lanes retired by the scalar bound {ret_s} "
       f"({ret_s / len(pairs):.3f}/pair)  by the per-cell bound {ret_c} ({ret_c / len(pairs):.3f}/pair)")
