@@ -126,7 +126,10 @@ __global__ void aln_plan_kernel(const AlnParams p, const int32_t *__restrict__ r
         AlnState x;
         x.w2 = 0; x.last_sc = -(1 << 30); x.n_pass = 0; x.kind = kAlnRejected;
         const int64_t lq64 = (int64_t)r.qe - r.qb, rl64 = r.re - r.rb;
-        if (r.rb < 0 || r.re < 0 || lq64 <= 0 || r.rb >= r.re || (p.l_pac > 0 && r.rb < p.l_pac && r.re > p.l_pac)) {
+        // bns_intv2rid < 0: the region bridges a join of the text -- the contig table's, or with no table
+        // the strand boundary alone (its n = 1 case)
+        if (r.rb < 0 || r.re < 0 || lq64 <= 0 || r.rb >= r.re ||
+            (p.ctg.off ? contig_crosses(p.ctg, r.rb, r.re) : (p.l_pac > 0 && r.rb < p.l_pac && r.re > p.l_pac))) {
             rej = 1;
             bsw_aln_t o;
             o.pos = -1; o.is_rev = 0; o.n_cigar = 0; o.NM = -1; o.score = 0; o.w = 0; o.n_pass = 1; o.md_len = 0;

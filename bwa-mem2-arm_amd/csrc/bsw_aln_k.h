@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/bsw_seqpair.h"
 #include "../../include/bsw_aln.h"
+#include "bsw_contig_seg.h"
 
 namespace bsw {
 
@@ -14,6 +15,7 @@ struct AlnParams {
     int32_t cigar_stride, md_stride;    // the caller's (md_stride 0: no MD)
     int32_t qstride, tstride;           // per-job code-buffer strides (set after the plan)
     int64_t ref_len, l_pac;
+    ContigView ctg;                     // off == nullptr: no table, the reject test is the l_pac one
     int8_t mat[25];
 };
 

@@ -27,6 +27,7 @@ namespace {
 struct ChainParams {
     int32_t o_del, e_del, o_ins, e_ins, a, w;
     int64_t ref_len, l_pac;
+    bsw::ContigView ctg;                // off != nullptr: windows are clipped to the first seed's segment
 };
 
 __device__ __forceinline__ int chain_max_gap(const ChainParams &p, int qlen)
@@ -91,7 +92,9 @@ __global__ void k_prep(int32_t n_reads, const int32_t *__restrict__ sbeg, const 
         }
         lo = max(lo, (int64_t)0);
         hi = min(hi, p.ref_len);
-        if (p.l_pac > 0 && lo < p.l_pac && p.l_pac < hi) {
+        if (p.ctg.off) {                                    // bns_fetch_seq with mid = seeds[0].rbeg
+            if (first >= 0) bsw::contig_clip(p.ctg, first, lo, hi);
+        } else if (p.l_pac > 0 && lo < p.l_pac && p.l_pac < hi) {
             if (first < p.l_pac) hi = p.l_pac;
             else lo = p.l_pac;
         }
@@ -228,7 +231,8 @@ int chain_rounds_device(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint8_t 
     const int64_t ref_len = ctx_refres_len(ctx);
     if (ref_len < 0) return BSW_E_INVAL;                // no resident reference
     if (const int rc = ext_opt_check(opt, ref_len)) return rc;
-    ChainParams p{prm.o_del, prm.e_del, prm.o_ins, prm.e_ins, prm.mat[0], opt->w, ref_len, opt->l_pac};
+    ChainParams p{prm.o_del, prm.e_del, prm.o_ins, prm.e_ins, prm.mat[0], opt->w, ref_len, opt->l_pac, {}};
+    if (const int rc = ctx_contigs(ctx, opt->l_pac, ref_len, &p.ctg, nullptr)) return rc;
     const auto tp = std::chrono::steady_clock::now();
     // a cached stream + pinned readback words and cached scratch (bsw_devcache.h): no driver
     // allocations per call.  B is destroyed first: it synchronises the stream, then returns its

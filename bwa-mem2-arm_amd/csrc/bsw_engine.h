@@ -28,6 +28,8 @@
 #include "../../include/bsw_pe.h"
 #include "../../include/bsw_matesw.h"
 #include "../../include/bsw_rec.h"
+#include "../../include/bsw_contigs.h"
+#include "bsw_contig_seg.h"
 #include "bsw_kernels.h"
 #include "bsw_internal.h"
 
@@ -268,6 +270,21 @@ struct DeviceCtx {
     DevBuf<uint8_t> d_refres;           // resident reference (bsw_set_reference)
     int64_t refres_len = -1;
     std::shared_mutex refmu;            // extension calls hold it shared while they use d_refres
+    // the contig table (bsw_set_contigs), under refmu like the reference; n_ctg == 0: none
+    DevBuf<int64_t> d_ctg_off;          // [n_ctg + 1] prefix sums
+    DevBuf<uint8_t> d_ctg_names;
+    DevBuf<int32_t> d_ctg_name_off;     // [n_ctg + 1]
+    int32_t n_ctg = 0;
+    int64_t ctg_sum = 0;
+    std::vector<int64_t> h_ctg_off;     // the prefix sums on the host (the host window builder, bsw_ext.cpp)
+
+    // the table fits a call that names l_pac (0: a one-strand reference of refres_len bases)
+    bool ctg_ok(int64_t l_pac) const { return n_ctg == 0 || ctg_sum == (l_pac > 0 ? l_pac : refres_len); }
+    ContigView ctg_view(int64_t l_pac) const
+    {
+        if (n_ctg == 0) return ContigView{nullptr, nullptr, nullptr, 0, l_pac};
+        return ContigView{d_ctg_off.p, d_ctg_names.p, d_ctg_name_off.p, n_ctg, l_pac};
+    }
 
     ~DeviceCtx() { (void)hipSetDevice(device); }        // (for d_refres; slots set it themselves)
     // A failed acquire destroys the half-made slot: what it had created is released and its

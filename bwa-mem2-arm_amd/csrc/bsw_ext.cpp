@@ -45,8 +45,8 @@ int cal_max_gap(const bsw_params_t &p, int a, int w, int qlen)
 // of the seeds' reach, clipped to [0, ref_len), and with l_pac > 0 the side of the first seed
 // when it crosses the forward-reverse boundary.  seed(i) returns the chain's i-th seed.
 template <class Seed>
-void chain_window(const bsw_params_t &p, int a, const bsw_ext_opt_t &opt, int64_t ref_len, int l_query, int n,
-                  Seed seed, int64_t *rmax0, int64_t *rmax1)
+void chain_window(const bsw_params_t &p, int a, const bsw_ext_opt_t &opt, const bsw::ContigView &cv, int64_t ref_len,
+                  int l_query, int n, Seed seed, int64_t *rmax0, int64_t *rmax1)
 {
     int64_t lo = ref_len, hi = 0, first = -1;
     for (int i = 0; i < n; ++i) {
@@ -59,7 +59,9 @@ void chain_window(const bsw_params_t &p, int a, const bsw_ext_opt_t &opt, int64_
     }
     lo = std::max<int64_t>(lo, 0);
     hi = std::min<int64_t>(hi, ref_len);
-    if (opt.l_pac > 0 && lo < opt.l_pac && opt.l_pac < hi) {
+    if (cv.off) {                                           // a contig table: the first seed's segment (bns_fetch_seq)
+        if (first >= 0) bsw::contig_clip(cv, first, lo, hi);
+    } else if (opt.l_pac > 0 && lo < opt.l_pac && opt.l_pac < hi) {
         if (first < opt.l_pac) hi = opt.l_pac;
         else lo = opt.l_pac;
     }
@@ -149,13 +151,27 @@ int ext_opt_check(const bsw_ext_opt_t *opt, int64_t ref_len)
 
 // a seed must lie inside [0, ref_len) and, on a two-strand text, on one strand (upstream's
 // bns_intv2rid drops bridging seeds before chaining)
-bool ext_seed_ok(const bsw_ext_opt_t *opt, const bsw_seed_t &s, int32_t l, int64_t ref_len)
+bool ext_seed_ok(const bsw_ext_opt_t *opt, const ContigView &cv, const bsw_seed_t &s, int32_t l, int64_t ref_len)
 {
     if (s.qbeg < 0 || s.qbeg + s.len > l || s.rbeg < 0 || s.rbeg + s.len > ref_len || l > BSW_MAX_LEN) return false;
+    if (cv.off) return s.len <= 0 || !contig_crosses(cv, s.rbeg, s.rbeg + s.len);
     return !(opt->l_pac > 0 && s.rbeg < opt->l_pac && s.rbeg + s.len > opt->l_pac);
 }
 
 }  // namespace bsw
+
+// the context's contig table on the host, for the host builders; BSW_E_INVAL when it does not fit the call
+struct HostContigs {
+    std::vector<int64_t> off;
+    bsw::ContigView view{nullptr, nullptr, nullptr, 0, 0};
+    int load(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, int64_t ref_len)
+    {
+        if (const int rc = bsw::ctx_contigs(ctx, opt->l_pac, ref_len, nullptr, &off)) return rc;
+        view = bsw::ContigView{off.empty() ? nullptr : off.data(), nullptr, nullptr, (int32_t)off.size() - 1, opt->l_pac};
+        if (off.empty()) view.n = 0;
+        return BSW_OK;
+    }
+};
 
 extern "C" int bsw_ext_last_stats(bsw_ctx_t *ctx, bsw_ext_stats_t *out)
 {
@@ -171,6 +187,8 @@ static int extend_seeds_win(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint
     if (!ctx || !opt || n < 0 || (n > 0 && (!ref || !reads || !read_off || !read_len || !seeds || !out)))
         return BSW_E_INVAL;
     if (const int rc = bsw::ext_opt_check(opt, ref_len)) return rc;
+    HostContigs hc;
+    if (const int rc = hc.load(ctx, opt, ref_len)) return rc;
     // SeqPair idr / idq are int32 offsets into one phase's code buffers: split calls whose
     // buffers could pass 2^31 bytes (window <= read + 2 cal_max_gap <= read + 4w per read)
     {
@@ -209,12 +227,12 @@ static int extend_seeds_win(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint
         const bsw_seed_t &s = seeds[i];
         if (s.len <= 0) continue;
         const int32_t l = read_len[i];
-        if (!bsw::ext_seed_ok(opt, s, l, ref_len)) return BSW_E_RANGE;
+        if (!bsw::ext_seed_ok(opt, hc.view, s, l, ref_len)) return BSW_E_RANGE;
         if (win) {
             rmax0[i] = win[2 * i];
             rmax1[i] = win[2 * i + 1];
         } else {
-            chain_window(p, a, *opt, ref_len, l, 1, [&](int) -> const bsw_seed_t & { return s; }, &rmax0[i],
+            chain_window(p, a, *opt, hc.view, ref_len, l, 1, [&](int) -> const bsw_seed_t & { return s; }, &rmax0[i],
                          &rmax1[i]);
         }
         if (rmax0[i] > s.rbeg || rmax1[i] < s.rbeg + s.len || s.rbeg - rmax0[i] > BSW_MAX_LEN ||
@@ -390,6 +408,8 @@ int chain_rounds(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, int64_t ref_len, cons
     bsw::ctx_params(ctx, &p);
     const int a = p.mat[0];
     *cs = bsw_chain_stats_t{};
+    HostContigs hc;
+    if (const int rc = hc.load(ctx, opt, ref_len)) return rc;
     auto tp = Clock::now();
     // read runs (seeds grouped by read)
     std::vector<int32_t> rstart;
@@ -412,7 +432,7 @@ int chain_rounds(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, int64_t ref_len, cons
                 int32_t c1 = c0;
                 while (c1 < rstart[r + 1] && seed_chain[c1] == seed_chain[c0]) ++c1;
                 for (int32_t i = c0; i < c1; ++i) { order[i] = i; chain_of[i] = c0; }
-                chain_window(p, a, *opt, ref_len, read_len[seed_read[c0]], c1 - c0,
+                chain_window(p, a, *opt, hc.view, ref_len, read_len[seed_read[c0]], c1 - c0,
                              [&](int i) -> const bsw_seed_t & { return seeds[c0 + i]; }, &cwin[2 * (size_t)c0],
                              &cwin[2 * (size_t)c0 + 1]);
                 std::sort(order.begin() + c0, order.begin() + c1, [&](int32_t x, int32_t y) {

@@ -28,7 +28,9 @@ __device__ __forceinline__ void seed_window_d(const ExtDevParams &p, const bsw_s
     int64_t hi = s.rbeg + s.len + ((l - qe) + cal_max_gap(p.a, p.o_del, p.e_del, p.o_ins, p.e_ins, p.w, l - qe));
     lo = lo > 0 ? lo : 0;
     hi = hi < p.ref_len ? hi : p.ref_len;
-    if (p.l_pac > 0 && lo < p.l_pac && p.l_pac < hi) {
+    if (p.ctg.off) {
+        contig_clip(p.ctg, s.rbeg, lo, hi);
+    } else if (p.l_pac > 0 && lo < p.l_pac && p.l_pac < hi) {
         if (s.rbeg < p.l_pac) hi = p.l_pac;
         else lo = p.l_pac;
     }
@@ -57,7 +59,9 @@ __global__ void ext_scan_kernel(const ExtDevParams p, const int32_t *__restrict_
         if (s.len > 0) {            // only seeded reads are validated and sized (as bsw_extend_seeds)
             l = read_len[i];
             if (l < 0 || l > BSW_MAX_LEN || s.qbeg < 0 || s.qbeg + s.len > l || s.rbeg < 0 ||
-                s.rbeg + s.len > p.ref_len || (p.l_pac > 0 && s.rbeg < p.l_pac && s.rbeg + s.len > p.l_pac)) {
+                s.rbeg + s.len > p.ref_len ||
+                (p.ctg.off ? contig_crosses(p.ctg, s.rbeg, s.rbeg + s.len)
+                           : (p.l_pac > 0 && s.rbeg < p.l_pac && s.rbeg + s.len > p.l_pac))) {
                 err = 1;
             } else {
                 if (win) {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/bsw_seqpair.h"
 #include "../../include/bsw_ext.h"
+#include "bsw_contig_seg.h"
 
 namespace bsw {
 
@@ -13,6 +14,7 @@ struct ExtDevParams {
     int32_t qstride, tstride;           // per-read code-buffer strides
     int64_t ref_len;
     int64_t l_pac;                      // bsw_ext_opt_t::l_pac (0: one-strand reference)
+    ContigView ctg;                     // off != nullptr: a seed's window is clipped to its segment
 };
 
 struct ExtState {                       // per read, between the phases

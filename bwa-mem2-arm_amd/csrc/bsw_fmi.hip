@@ -970,13 +970,45 @@ struct bsw_fmi {
     int32_t *d_err = nullptr;
     void *h_stage = nullptr;                  // host-buffer calls: device copies
     std::mutex mu;                            // one seeding call at a time per index
+    int64_t *d_ctg_off = nullptr;             // bsw_fmi_set_contigs: [n_ctg + 1] prefix sums; under mu
+    int32_t n_ctg = 0;
+    int64_t ctg_sum = 0;
 };
 
 int bsw::fmi_view(bsw_fmi_t *f, FmiView *out)
 {
     if (!f) return BSW_E_INVAL;
     if (f->device < 0) return BSW_E_NODEV;
-    *out = FmiView{f->device, f->d_sa, f->wide, f->n, f->n / 2, f->stream, &f->mu};
+    *out = FmiView{f->device, f->d_sa, f->wide, f->n, f->n / 2, f->stream, &f->mu, &f->d_ctg_off, &f->n_ctg, &f->ctg_sum};
+    return BSW_OK;
+}
+
+// the table for bsw_mem_chain_device, which has no context (include/bsw_contigs.h)
+extern "C" int bsw_fmi_set_contigs(bsw_fmi_t *f, int32_t n, const int64_t *len)
+{
+    if (!f || n < 0 || n > BSW_CONTIG_MAX_N || (n > 0 && !len)) return BSW_E_INVAL;
+    if (f->device < 0) return BSW_E_NODEV;
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    for (int32_t i = 0; i < n; ++i) {
+        if (len[i] <= 0 || len[i] > BSW_CONTIG_MAX_SUM - off[i]) return BSW_E_INVAL;
+        off[i + 1] = off[i] + len[i];
+    }
+    if (hipSetDevice(f->device) != hipSuccess) return BSW_E_HIP;
+    int64_t *d_new = nullptr;                               // the copy first: a failure leaves the table that is set
+    if (n > 0) {
+        hipError_t e = hipMalloc((void **)&d_new, off.size() * sizeof(int64_t));
+        if (e != hipSuccess) return e == hipErrorOutOfMemory ? BSW_E_NOMEM : BSW_E_HIP;
+        e = hipMemcpy(d_new, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d_new);
+            return BSW_E_HIP;
+        }
+    }
+    std::lock_guard<std::mutex> lk(f->mu);                  // waits for a running call
+    if (f->d_ctg_off) (void)hipFree(f->d_ctg_off);
+    f->d_ctg_off = d_new;
+    f->n_ctg = n;
+    f->ctg_sum = off[(size_t)n];
     return BSW_OK;
 }
 
@@ -1322,6 +1354,7 @@ void bsw_fmi_destroy(bsw_fmi_t *f)
     if (f->d_stab) (void)hipFree(f->d_stab);
     if (f->d_err) (void)hipFree(f->d_err);
     if (f->d_scratch) (void)hipFree(f->d_scratch);
+    if (f->d_ctg_off) (void)hipFree(f->d_ctg_off);
     if (f->ev0) (void)hipEventDestroy(f->ev0);
     if (f->ev1) (void)hipEventDestroy(f->ev1);
     if (f->stream) (void)hipStreamDestroy(f->stream);

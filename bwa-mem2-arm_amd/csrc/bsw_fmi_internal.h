@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <mutex>
 #include "../../include/bsw_fmi.h"
+#include "../../include/bsw_contigs.h"
+#include "bsw_contig_seg.h"
 
 namespace bsw {
 // One 64-byte occurrence block per 64 BWT rows, two widths: narrow (|T| + 1 < 2^32: 32-bit
@@ -46,6 +48,9 @@ struct FmiView {
     int64_t l_pac;                   // forward-strand length
     hipStream_t stream;              // the index's own stream
     std::mutex *mu;                  // one call at a time per index
+    int64_t *const *ctg_off;         // bsw_fmi_set_contigs: read under mu (*ctg_off null / *n_ctg 0: no table)
+    const int32_t *n_ctg;
+    const int64_t *ctg_sum;
 };
 // BSW_E_NODEV for a host-only index
 int fmi_view(bsw_fmi_t *f, FmiView *out);

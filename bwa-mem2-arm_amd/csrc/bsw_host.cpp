@@ -515,6 +515,16 @@ int64_t ctx_refres_len(bsw_ctx_t *ctx)
     return dc.d_refres ? dc.refres_len : -1;
 }
 
+int ctx_contigs(bsw_ctx_t *ctx, int64_t l_pac, int64_t ref_len, ContigView *dev, std::vector<int64_t> *host_off)
+{
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> g(dc.refmu);
+    if (dc.n_ctg > 0 && dc.ctg_sum != (l_pac > 0 ? l_pac : ref_len)) return BSW_E_INVAL;
+    if (dev) *dev = dc.ctg_view(l_pac);
+    if (host_off) *host_off = dc.n_ctg > 0 ? dc.h_ctg_off : std::vector<int64_t>();
+    return BSW_OK;
+}
+
 void *pinned_acquire(bsw_ctx_t *ctx, int which, size_t bytes)
 {
     auto &b = ctx->pin[which & 1];
@@ -853,6 +863,60 @@ int bsw_set_reference(bsw_ctx_t *ctx, const uint8_t *ref, int64_t ref_len)
     return BSW_OK;
 }
 
+int bsw_set_contigs(bsw_ctx_t *ctx, int32_t n, const int64_t *len, const char *const *names)
+{
+    if (!ctx || n < 0 || (n > 0 && (!len || !names))) return BSW_E_INVAL;
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    std::vector<int32_t> name_off((size_t)n + 1, 0);
+    std::vector<uint8_t> bytes;
+    for (int32_t i = 0; i < n; ++i) {
+        if (len[i] <= 0 || len[i] > INT64_MAX / 2 - off[i] || !names[i]) return BSW_E_INVAL;
+        const size_t l = strnlen(names[i], BSW_CONTIG_MAX_NAME + 1);
+        if (l < 1 || l > BSW_CONTIG_MAX_NAME) return BSW_E_INVAL;
+        off[i + 1] = off[i] + len[i];
+        bytes.insert(bytes.end(), names[i], names[i] + l);
+        name_off[i + 1] = (int32_t)bytes.size();
+    }
+    // the limits the pair kernels' sort coordinate relies on (kPeRidShift, bsw_pe_k.h): stated in bsw_contigs.h
+    if (n > BSW_CONTIG_MAX_N || off[(size_t)n] > BSW_CONTIG_MAX_SUM) return BSW_E_INVAL;
+    // every device's copy first, then the switch: a failure leaves the table that is set on all of them
+    struct Staged {
+        bsw::DevBuf<int64_t> off;
+        bsw::DevBuf<uint8_t> names;
+        bsw::DevBuf<int32_t> name_off;
+    };
+    std::vector<Staged> staged(ctx->devs.size());
+    for (size_t d = 0; n > 0 && d < ctx->devs.size(); ++d) {
+        Staged &t = staged[d];
+        BSW_TRY(hipSetDevice(ctx->devs[d]->device));
+        BSW_TRY(t.off.reserve_exact(off.size()));
+        BSW_TRY(t.name_off.reserve_exact(name_off.size()));
+        BSW_TRY(t.names.reserve_exact(bytes.size()));
+        hipStream_t cs = nullptr;                           // (a stream of its own, as bsw_set_reference)
+        BSW_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+        hipError_t e = hipMemcpyAsync(t.off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, cs);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(t.name_off, name_off.data(), name_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, cs);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.names, bytes.data(), bytes.size(), hipMemcpyHostToDevice, cs);
+        if (e == hipSuccess) e = hipStreamSynchronize(cs);
+        (void)hipStreamDestroy(cs);
+        BSW_TRY(e);
+    }
+    for (size_t d = 0; d < ctx->devs.size(); ++d) {
+        bsw::DeviceCtx &dc = *ctx->devs[d];
+        std::unique_lock<std::shared_mutex> g(dc.refmu);   // waits for running stage calls
+        (void)hipSetDevice(dc.device);                      // (the old buffers are freed below, on their device)
+        std::swap(dc.d_ctg_off, staged[d].off);
+        std::swap(dc.d_ctg_names, staged[d].names);
+        std::swap(dc.d_ctg_name_off, staged[d].name_off);
+        dc.n_ctg = n;
+        dc.ctg_sum = off[(size_t)n];
+        dc.h_ctg_off = off;
+        staged[d] = Staged();
+    }
+    return BSW_OK;
+}
+
 int bsw_extend_seeds_device(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint8_t *d_reads,
                             const int64_t *d_read_off, const int32_t *d_read_len, const bsw_seed_t *d_seeds,
                             int32_t n, bsw_alnreg_t *d_out, void *stream)
@@ -872,6 +936,7 @@ int bsw::extend_seeds_device_win(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const
     std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the resident reference stays put
     if (!dc.d_refres) return BSW_E_INVAL;
     if (const int rc = bsw::ext_opt_check(opt, dc.refres_len)) return rc;
+    if (!dc.ctg_ok(opt->l_pac)) return BSW_E_INVAL;
     if (n == 0) return BSW_OK;
     const auto t0 = std::chrono::steady_clock::now();
     bsw_ext_stats_t es{};
@@ -883,6 +948,7 @@ int bsw::extend_seeds_device_win(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const
         xp.o_del = p.o_del; xp.e_del = p.e_del; xp.o_ins = p.o_ins; xp.e_ins = p.e_ins;
         xp.ref_len = dc.refres_len;
         xp.l_pac = opt->l_pac;
+        xp.ctg = dc.ctg_view(opt->l_pac);
         // scan: per-read validation and windows, longest read / window, job counts
         BSW_TRY(s.d_xwin.grow(2 * (size_t)n));
         BSW_TRY(bsw::launch_ext_scan(xp, d_read_len, d_seeds, d_win, n, s.d_xwin, s.d_meta, st));

@@ -4,6 +4,7 @@
 #include "../../include/bsw_ext.h"
 #include <cstdint>
 #include <vector>
+#include "bsw_contig_seg.h"
 
 namespace bsw {
 // bsw_get_scores with a per-call end_bonus (LEFT uses pen_clip5, RIGHT pen_clip3) and the
@@ -25,7 +26,12 @@ void set_chain_stats(bsw_ctx_t *ctx, const bsw_chain_stats_t &s);
 int get_chain_stats(bsw_ctx_t *ctx, bsw_chain_stats_t *out);
 // bsw_ext_opt_t / seed checks shared by the host and device extension forms (bsw_ext.cpp)
 int ext_opt_check(const bsw_ext_opt_t *opt, int64_t ref_len);
-bool ext_seed_ok(const bsw_ext_opt_t *opt, const bsw_seed_t &s, int32_t l, int64_t ref_len);
+bool ext_seed_ok(const bsw_ext_opt_t *opt, const ContigView &cv, const bsw_seed_t &s, int32_t l, int64_t ref_len);
+// The context's contig table (bsw_set_contigs) for an extension call that names l_pac over a reference of
+// ref_len bases: BSW_E_INVAL when one is set and does not sum to l_pac (l_pac == 0: to ref_len).  *dev = the
+// view with device pointers (off null: no table); *host_off = a copy of the prefix sums (empty: no table).
+// Either may be null.
+int ctx_contigs(bsw_ctx_t *ctx, int64_t l_pac, int64_t ref_len, ContigView *dev, std::vector<int64_t> *host_off);
 // bsw_extend_seeds_device with each job's target window given (d_win[2j], d_win[2j + 1]: the
 // chain's window, mem_chain2aln) or computed per seed (d_win == nullptr)
 int extend_seeds_device_win(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint8_t *d_reads,

@@ -43,8 +43,15 @@ __device__ __forceinline__ bool msw_window(const MswParams &p, const MswDir &d, 
     re = min(re, l_pac << 1);
     if (rb < re) {
         const int64_t mid = (rb + re) >> 1;
-        if (mid < l_pac) re = min(re, l_pac);
-        else rb = max(rb, l_pac);
+        if (p.ctg.off) {
+            // bns_fetch_seq(.., mid, ..): the window is clipped to the segment of its midpoint, and the job
+            // exists only when that segment's contig is the anchor's (mem_matesw: a->rid == rid)
+            if (contig_clip(p.ctg, mid, rb, re) != contig_rid(p.ctg, arb)) return false;
+        } else if (mid < l_pac) {
+            re = min(re, l_pac);
+        } else {
+            rb = max(rb, l_pac);
+        }
     }
     return rb < re && re - rb >= p.s.min_seed_len;
 }

@@ -6,6 +6,7 @@
 #include "../../include/bsw_seqpair.h"
 #include "../../include/bsw_matesw.h"
 #include "bsw_sel_k.h"
+#include "bsw_contig_seg.h"
 
 namespace bsw {
 
@@ -19,6 +20,7 @@ struct MswParams {
     int32_t max_matesw, pen_unpaired;
     int32_t qstride, tstride;           // per-job code-buffer strides (set after a round's plan)
     MswDir pes[4];
+    ContigView ctg;                     // off != nullptr: windows are clipped to the midpoint's segment (bsw_contig_seg.h)
 };
 
 struct MswSt {                          // per pair: the call its cursor stands at

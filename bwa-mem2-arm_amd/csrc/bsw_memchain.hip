@@ -152,10 +152,12 @@ __device__ void w_introsort(size_t n, WI *a)
 }
 
 // test_and_merge: 1 = absorbed (appended to c, or contained)
-__device__ bool test_and_merge(const COpt &o, int64_t l_pac, ChainRec &c, PoolSeed *pool, int32_t *next,
-                               int32_t &np, const PoolSeed &p)
+__device__ bool test_and_merge(const COpt &o, const bsw::ContigView &ctg, int64_t l_pac, ChainRec &c, PoolSeed *pool,
+                               int32_t *next, int32_t &np, const PoolSeed &p)
 {
     const PoolSeed f = pool[c.head], last = pool[c.tail];
+    // upstream's first test: another contig than the chain's (that of its first seed) asks for a new chain
+    if (ctg.off && bsw::contig_rid(ctg, p.rbeg) != bsw::contig_rid(ctg, f.rbeg)) return false;
     const int64_t qend = last.qbeg + last.len, rend = last.rbeg + last.len;
     if (p.qbeg >= f.qbeg && p.qbeg + p.len <= qend && p.rbeg >= f.rbeg && p.rbeg + p.len <= rend) return true;
     if ((last.rbeg < l_pac || f.rbeg < l_pac) && p.rbeg >= l_pac) return false;
@@ -194,7 +196,7 @@ __device__ int chain_weight(const ChainRec &c, const PoolSeed *pool, const int32
 
 // per read: region [off, off + cnt) of pool / next / chains / order / wi / list
 template <class S>
-__global__ void k_chain(COpt o, const S *__restrict__ sa, int64_t l_pac, const int32_t *__restrict__ read_len,
+__global__ void k_chain(COpt o, bsw::ContigView ctg, const S *__restrict__ sa, int64_t l_pac, const int32_t *__restrict__ read_len,
                         int32_t n_reads, const bsw_bwtintv_t *__restrict__ mems, int32_t cap,
                         const int32_t *__restrict__ n_mems, const int64_t *__restrict__ off,
                         PoolSeed *__restrict__ pool_all, int32_t *__restrict__ next_all,
@@ -221,7 +223,9 @@ __global__ void k_chain(COpt o, const S *__restrict__ sa, int64_t l_pac, const i
                 s.rbeg = (int64_t)sa[p.x[0] + k];
                 s.qbeg = (int32_t)(p.info >> 32);
                 s.len = slen;
-                if (s.rbeg < l_pac && l_pac < s.rbeg + s.len) continue;      // bridging: rid < 0
+                // bridging a join of the text (bns_intv2rid < 0): the contig table's, or the strand boundary alone
+                if (ctg.off ? bsw::contig_crosses(ctg, s.rbeg, s.rbeg + s.len) : (s.rbeg < l_pac && l_pac < s.rbeg + s.len))
+                    continue;
                 int lo = 0, hi = nc;
                 while (lo < hi) {
                     const int mid = (lo + hi) >> 1;
@@ -229,7 +233,7 @@ __global__ void k_chain(COpt o, const S *__restrict__ sa, int64_t l_pac, const i
                 }
                 const bool eq = lo < nc && ch[ord[lo]].pos == s.rbeg;
                 const int lower = eq ? lo : lo - 1;
-                if (lower >= 0 && test_and_merge(o, l_pac, ch[ord[lower]], pool, next, np, s)) continue;
+                if (lower >= 0 && test_and_merge(o, ctg, l_pac, ch[ord[lower]], pool, next, np, s)) continue;
                 const int at = eq ? lo + 1 : lo;
                 for (int u = nc; u > at; --u) ord[u] = ord[u - 1];
                 ChainRec c;
@@ -385,11 +389,12 @@ int run_chain(const bsw::FmiView &f, const COpt &o, const int32_t *d_len, int32_
     MC_TRY(B.get(ord, R));
     MC_TRY(B.get(wi, R));
     MC_TRY(B.get(list, R));
+    const bsw::ContigView ctg{*f.n_ctg > 0 ? *f.ctg_off : nullptr, nullptr, nullptr, *f.n_ctg, f.l_pac};
     if (f.sa64)
-        hipLaunchKernelGGL(k_chain<uint64_t>, g, b, 0, s, o, (const uint64_t *)f.d_sa, f.l_pac, d_len, n, d_mems, cap,
+        hipLaunchKernelGGL(k_chain<uint64_t>, g, b, 0, s, o, ctg, (const uint64_t *)f.d_sa, f.l_pac, d_len, n, d_mems, cap,
                            d_nm, off, pool, next, chains, ord, wi, list, n_kept, kcnt);
     else
-        hipLaunchKernelGGL(k_chain<uint32_t>, g, b, 0, s, o, (const uint32_t *)f.d_sa, f.l_pac, d_len, n, d_mems, cap,
+        hipLaunchKernelGGL(k_chain<uint32_t>, g, b, 0, s, o, ctg, (const uint32_t *)f.d_sa, f.l_pac, d_len, n, d_mems, cap,
                            d_nm, off, pool, next, chains, ord, wi, list, n_kept, kcnt);
     MC_TRY(hipGetLastError());
     MC_TRY(hipMemsetAsync(kcnt + n, 0, sizeof(int64_t), s));
@@ -437,6 +442,7 @@ extern "C" int bsw_mem_chain_device(bsw_fmi_t *fmi, const bsw_chain_opt_t *opt, 
     if (const int rc = bsw::fmi_view(fmi, &f)) return rc;
     std::lock_guard<std::mutex> lk(*f.mu);
     if (hipSetDevice(f.device) != hipSuccess) return BSW_E_HIP;
+    if (*f.n_ctg > 0 && *f.ctg_sum != f.l_pac) return BSW_E_INVAL;     // (bsw_fmi_set_contigs: the sum is l_pac)
     COpt o{opt->max_occ, opt->w, opt->max_chain_gap, opt->min_chain_weight, opt->min_seed_len, opt->max_chain_extend,
            opt->drop_ratio, opt->mask_level};
     return run_chain(f, o, d_read_len, n_reads, d_mems, cap, d_n_mems, d_seeds, d_seed_read, d_seed_chain, seed_cap,

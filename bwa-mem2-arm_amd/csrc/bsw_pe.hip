@@ -64,6 +64,12 @@ __device__ __forceinline__ int pe_cal_sub(const SelParams &p, const bsw_alnreg_t
     return p.min_seed_len * p.a;
 }
 
+// the hits at rb0 and rb1 lie on one contig (with no table: always)
+__device__ __forceinline__ bool pe_same_rid(const PeParams &p, int64_t rb0, int64_t rb1)
+{
+    return !p.ctg.off || contig_rid(p.ctg, rb0) == contig_rid(p.ctg, rb1);
+}
+
 __global__ __launch_bounds__(kPeStatBlock) void pe_stat_kernel(const PeParams p, const bsw_alnreg_t *__restrict__ regs,
                                                                const int32_t *__restrict__ first,
                                                                int32_t *__restrict__ hist, int32_t *__restrict__ meta)
@@ -100,6 +106,7 @@ __global__ __launch_bounds__(kPeStatBlock) void pe_stat_kernel(const PeParams p,
         const bsw_alnreg_t *a0 = regs + f0, *a1 = regs + f1;
         if ((double)pe_cal_sub(p.s, a0, f1 - f0) > 0.8 * a0[0].score) continue;
         if ((double)pe_cal_sub(p.s, a1, f2 - f1) > 0.8 * a1[0].score) continue;
+        if (!pe_same_rid(p, a0[0].rb, a1[0].rb)) continue;   // (mem_pestat: r[0]->a[0].rid != r[1]->a[0].rid)
         int64_t is;
         const int dir = infer_dir(p.s.l_pac, a0[0].rb, a1[0].rb, is);
         if (is == 0 || is > p.max_ins) continue;
@@ -172,7 +179,7 @@ __device__ __forceinline__ int pe_unpaired_proper(const PeParams &p, const PeDir
 {
     int64_t dist;
     const PeDir d = pes[infer_dir(p.s.l_pac, rb0, rb1, dist)];
-    return !d.failed && dist >= d.low && dist <= d.high;
+    return !d.failed && dist >= d.low && dist <= d.high && pe_same_rid(p, rb0, rb1);
 }
 
 __device__ __forceinline__ void pe_load_pes(const PeParams &p, PeDir *s_pes)
@@ -228,7 +235,7 @@ __device__ __forceinline__ int pe_fast_pair(const PeParams &p, const PeDir *s_pe
         const int sa = end0_first ? st0 : st1, sb = end0_first ? st1 : st0;  // strands in v's order
         const PeDir d = s_pes[sa << 1 | sb];
         const int64_t dist = end0_first ? v1 - v0 : v0 - v1;
-        if (!d.failed && dist <= d.high && dist >= d.low) {
+        if (!d.failed && dist <= d.high && dist >= d.low && pe_same_rid(p, x0.r.rb, x1.r.rb)) {
             flags |= kPeFHasU;
             o = pe_q(d, dist, (uint32_t)x0.r.score, (uint32_t)x1.r.score, p.s.a);
         }
@@ -412,6 +419,7 @@ __global__ __launch_bounds__(64) void pe_pair_general_kernel(const PeParams p, b
                 const int st = rb >= p.s.l_pac;
                 PeV x;
                 x.x = st ? two_l - 1 - rb : rb;
+                if (p.ctg.off) x.x += (int64_t)contig_of(p.ctg, x.x) << kPeRidShift;   // (bsw_pe_k.h)
                 x.y = (uint64_t)(uint32_t)c->r.score << 32 | (uint64_t)(uint32_t)(i << 2 | st << 1 | e);
                 V[k] = x;
             }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/bsw_pe.h"
 #include "bsw_sel_k.h"
+#include "bsw_contig_seg.h"
 
 namespace bsw {
 
@@ -17,7 +18,15 @@ struct PeParams {
     int32_t n_pairs, n_regs;
     int32_t max_ins, T, pen_unpaired, pad;
     PeDir pes[4];
+    ContigView ctg;                     // off != nullptr: hits on different contigs are no pair (bsw_contig_seg.h)
 };
+
+// mem_pair's sort key with a contig table: upstream's rid << 32 | (position - offset) orders the hits as
+// the global forward position does, and a rid change ends the distance scan.  The same order and the same
+// end come from the global position moved apart by rid << kPeRidShift: bsw_set_contigs admits at most
+// BSW_CONTIG_MAX_N = 2^22 contigs that sum to at most BSW_CONTIG_MAX_SUM = 2^39, so two hits on different
+// contigs are more than 2^39 apart -- beyond any int32 `high` -- and the largest coordinate is below 2^63
+constexpr int kPeRidShift = 40;
 
 struct alignas(16) PeV {                // mem_pair's v entry
     int64_t x;

@@ -197,9 +197,10 @@ __device__ __forceinline__ int64_t cigar_rlen(const uint32_t *cg, int n)
     return l;
 }
 
-__global__ __launch_bounds__(kBlock) void rec_finish_kernel(RecLists L, const int32_t *rec_first, bsw_rec_t *recs,
-                                                            int32_t n_rec, const bsw_aln_t *aln, const uint32_t *cigar,
-                                                            int32_t cigar_stride, int32_t n_aln, int32_t *meta)
+__global__ __launch_bounds__(kBlock) void rec_finish_kernel(RecLists L, ContigView ctg, const int32_t *rec_first,
+                                                            bsw_rec_t *recs, int32_t n_rec, const bsw_aln_t *aln,
+                                                            const uint32_t *cigar, int32_t cigar_stride, int32_t n_aln,
+                                                            int32_t *meta)
 {
     __shared__ int32_t cnt[kRecMetaWords];
     if (threadIdx.x < kRecMetaWords) cnt[threadIdx.x] = 0;
@@ -246,7 +247,8 @@ __global__ __launch_bounds__(kBlock) void rec_finish_kernel(RecLists L, const in
             }
             if (!p_map && ma >= 0) { pos = mpos; is_rev = m_rev; }
             if (ma < 0 && p_map) { mpos = pos; m_rev = is_rev; }
-            if (p_ok && m_ok) {
+            // (mem_aln2sam: p->rid == m->rid; both positions are forward coordinates)
+            if (p_ok && m_ok && (!ctg.off || contig_of(ctg, pos) == contig_of(ctg, mpos))) {
                 const int64_t p0 = pos + (is_rev ? cigar_rlen(cigar + (size_t)o.aln * cigar_stride, aln[o.aln].n_cigar) - 1 : 0);
                 const int64_t p1 = mpos + (m_rev ? cigar_rlen(cigar + (size_t)ma * cigar_stride, aln[ma].n_cigar) - 1 : 0);
                 tlen = -(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0));
@@ -444,6 +446,29 @@ __device__ __forceinline__ bool text_record_ok(const RecText &t, int i)
     return true;
 }
 
+// where a forward position prints: its contig's name, the contig's offset and its rid -- with no
+// table opt->rname, 0 and 0
+struct Place {
+    const uint8_t *name;
+    int len, rid;
+    int64_t base, end;                  // the contig is [base, end)
+};
+
+__device__ __forceinline__ Place place_of(const RecText &t, int64_t pos)
+{
+    if (!t.ctg.off) return {t.rname, t.rname_len, 0, 0, INT64_MAX};
+    const int k = contig_of(t.ctg, pos);
+    const int o = t.ctg.name_off[k];
+    return {t.ctg.names + o, t.ctg.name_off[k + 1] - o, k, t.ctg.off[k], t.ctg.off[k + 1]};
+}
+
+// the same for a position that usually lies in the contig already found (the mate, SA and XA entries): no
+// second search then
+__device__ __forceinline__ Place place_near(const RecText &t, int64_t pos, const Place &near)
+{
+    return pos >= near.base && pos < near.end ? near : place_of(t, pos);
+}
+
 template <class S>
 __device__ __forceinline__ void emit_line(S &s, const RecText &t, int i)
 {
@@ -459,10 +484,12 @@ __device__ __forceinline__ void emit_line(S &s, const RecText &t, int i)
     s.ch('\t');
     const int ncig = p.aln >= 0 ? t.aln[p.aln].n_cigar : 0;
     const uint32_t *cg = t.cigar + (size_t)max(p.aln, 0) * t.cigar_stride;
+    Place at = {nullptr, 0, t.ctg.off ? -1 : 0, 0, 0};   // (an empty range: nothing is near it)
     if (p.pos >= 0) {
-        s.copy(t.rname, t.rname_len);
+        at = place_of(t, p.pos);
+        s.copy(at.name, at.len);
         s.ch('\t');
-        s.num(p.pos + 1);
+        s.num(p.pos - at.base + 1);
         s.ch('\t');
         s.num(p.mapq);
         s.ch('\t');
@@ -473,8 +500,11 @@ __device__ __forceinline__ void emit_line(S &s, const RecText &t, int i)
     }
     s.ch('\t');
     if (p.mpos >= 0) {
-        s.lit("=\t", 2);
-        s.num(p.mpos + 1);
+        const Place mt = place_near(t, p.mpos, at);
+        if (mt.rid == at.rid) s.ch('=');    // (pos >= 0 whenever mpos is: cross-linking)
+        else s.copy(mt.name, mt.len);
+        s.ch('\t');
+        s.num(p.mpos - mt.base + 1);
         s.ch('\t');
         s.num(p.tlen);
     } else {
@@ -518,9 +548,10 @@ __device__ __forceinline__ void emit_line(S &s, const RecText &t, int i)
                 if (j == which || (t.recs[f0 + j].flag & 0x100)) continue;
                 const int qa = t.recs[f0 + j].aln;
                 const bsw_aln_t a = t.aln[qa];
-                s.copy(t.rname, t.rname_len);
+                const Place sa = place_near(t, a.pos, at);
+                s.copy(sa.name, sa.len);
                 s.ch(',');
-                s.num(a.pos + 1);
+                s.num(a.pos - sa.base + 1);
                 s.ch(',');
                 s.ch(a.is_rev ? '-' : '+');
                 s.ch(',');
@@ -537,10 +568,11 @@ __device__ __forceinline__ void emit_line(S &s, const RecText &t, int i)
         s.lit("\tXA:Z:", 6);
         for (int j = p.xa_first; j < p.xa_first + p.xa_n; ++j) {
             const bsw_aln_t a = t.aln[j];
-            s.copy(t.rname, t.rname_len);
+            const Place xa = place_near(t, a.pos, at);
+            s.copy(xa.name, xa.len);
             s.ch(',');
             s.ch(a.is_rev ? '-' : '+');
-            s.num(a.pos + 1);
+            s.num(a.pos - xa.base + 1);
             s.ch(',');
             put_cigar(s, t.cigar + (size_t)j * t.cigar_stride, a.n_cigar, 0);
             s.ch(',');
@@ -629,14 +661,14 @@ hipError_t launch_rec_fill(const RecParams &p, const RecLists &l, const int32_t 
     return hipGetLastError();
 }
 
-hipError_t launch_rec_finish(const RecLists &l, const int32_t *rec_first, bsw_rec_t *recs, int32_t n_rec,
-                             const bsw_aln_t *aln, const uint32_t *cigar, int32_t cigar_stride, int32_t n_aln,
-                             int32_t *meta, hipStream_t s)
+hipError_t launch_rec_finish(const RecLists &l, const ContigView &ctg, const int32_t *rec_first, bsw_rec_t *recs,
+                             int32_t n_rec, const bsw_aln_t *aln, const uint32_t *cigar, int32_t cigar_stride,
+                             int32_t n_aln, int32_t *meta, hipStream_t s)
 {
     const int64_t n = n_rec > n_aln ? n_rec : n_aln;
     if (n == 0) return hipSuccess;
-    rec_finish_kernel<<<grid_for(n, kBlock), kBlock, 0, s>>>(l, rec_first, recs, n_rec, aln, cigar, cigar_stride, n_aln,
-                                                              meta);
+    rec_finish_kernel<<<grid_for(n, kBlock), kBlock, 0, s>>>(l, ctg, rec_first, recs, n_rec, aln, cigar, cigar_stride,
+                                                              n_aln, meta);
     return hipGetLastError();
 }
 

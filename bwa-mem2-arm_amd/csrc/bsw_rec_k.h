@@ -3,6 +3,7 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 #include "../../include/bsw_rec.h"
+#include "bsw_contig_seg.h"
 
 namespace bsw {
 
@@ -31,6 +32,7 @@ struct RecText {                        // call 2's arrays and options
     const int64_t *read_off, *name_off;
     const int32_t *read_len;
     int32_t n_rec, n_aln, n_reads, n_names, cigar_stride, md_stride, paired, flags, rname_len;
+    ContigView ctg;                     // off != nullptr: names and relative positions from the table, rname unread
 };
 
 // meta words (one int32 array, zeroed per call); the counters are added once per block
@@ -53,10 +55,11 @@ hipError_t launch_rec_count(const RecParams &p, const RecLists &l, int32_t *nrec
 hipError_t launch_rec_fill(const RecParams &p, const RecLists &l, const int32_t *rec_first, const int32_t *aln_first,
                            bsw_rec_t *recs, int32_t *aln_reg, bsw_alnreg_t *creg, int32_t *creg_read, hipStream_t s);
 // One work item per record and per alignment: cross-linking, TLEN, the printed flag; rejected and
-// overflowing alignments and the stage's counters into meta.
-hipError_t launch_rec_finish(const RecLists &l, const int32_t *rec_first, bsw_rec_t *recs, int32_t n_rec,
-                             const bsw_aln_t *aln, const uint32_t *cigar, int32_t cigar_stride, int32_t n_aln,
-                             int32_t *meta, hipStream_t s);
+// overflowing alignments and the stage's counters into meta.  With a contig table TLEN stays 0
+// unless pos and mpos lie in one contig.
+hipError_t launch_rec_finish(const RecLists &l, const ContigView &ctg, const int32_t *rec_first, bsw_rec_t *recs,
+                             int32_t n_rec, const bsw_aln_t *aln, const uint32_t *cigar, int32_t cigar_stride,
+                             int32_t n_aln, int32_t *meta, hipStream_t s);
 // len[i] = the bytes of record i's line (len[n_rec] = 0); validation into meta[kRecErr]
 hipError_t launch_rec_text_len(const RecText &t, int64_t *len, int32_t *meta, hipStream_t s);
 // the lines at text + text_off[i]; text is 4-byte aligned

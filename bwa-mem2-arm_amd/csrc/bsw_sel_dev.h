@@ -247,6 +247,12 @@ __device__ __forceinline__ void sel_mark_mapq(const SelParams &p, int r, SelW *W
 // The i / j loop of read r from (i, j); have: score answers the patch_reg it was suspended at (a
 // global score may be negative, so the score itself cannot say so).  Returns true when it
 // suspends again (st[r] holds where; lq / rl its job's spans).
+// mem_sort_dedup_patch's rid tests: two regions are compared (and patched) only on one contig
+__device__ __forceinline__ bool sel_same_rid(const SelParams &p, const SelW &x, const SelW &y)
+{
+    return !p.ctg.off || contig_rid(p.ctg, x.r.rb) == contig_rid(p.ctg, y.r.rb);
+}
+
 __device__ __forceinline__ bool sel_dedup(const SelParams &p, int r, SelW *W, int n, int i, int j, int w, bool have,
                                           int score,
                           const uint8_t *__restrict__ q_codes, const uint8_t *__restrict__ ref, const int8_t *s_mat,
@@ -254,10 +260,10 @@ __device__ __forceinline__ bool sel_dedup(const SelParams &p, int r, SelW *W, in
 {
     for (; i < n; ++i, j = -2) {
         if (j == -2) {
-            if (W[i].r.rb >= W[i - 1].r.re + p.max_chain_gap) continue;
+            if (!sel_same_rid(p, W[i], W[i - 1]) || W[i].r.rb >= W[i - 1].r.re + p.max_chain_gap) continue;
             j = i - 1;
         }
-        for (; j >= 0 && W[i].r.rb < W[j].r.re + p.max_chain_gap; --j) {
+        for (; j >= 0 && sel_same_rid(p, W[i], W[j]) && W[i].r.rb < W[j].r.re + p.max_chain_gap; --j) {
             const bsw_alnreg_t P = W[i].r, Q = W[j].r;
             if (!have) {
                 if (Q.qe == Q.qb) continue;
@@ -295,7 +301,8 @@ __device__ __forceinline__ bool sel_dedup(const SelParams &p, int r, SelW *W, in
                     atomicOr(&meta[kSelErr], 1);
                     continue;
                 }
-                if (lq <= 0 || rl <= 0 || (p.l_pac > 0 && Q.rb < p.l_pac && P.re > p.l_pac)) {
+                if (lq <= 0 || rl <= 0 ||
+                    (p.ctg.off ? contig_crosses(p.ctg, Q.rb, P.re) : (p.l_pac > 0 && Q.rb < p.l_pac && P.re > p.l_pac))) {
                     score = 0;                              // gen_cigar2 rejects the span
                 } else if (lq == rl && w == 0) {
                     score = 0;                              // gen_cigar2's gap-free shortcut

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/bsw_seqpair.h"
 #include "../../include/bsw_sel.h"
+#include "bsw_contig_seg.h"
 
 namespace bsw {
 
@@ -15,6 +16,7 @@ struct SelParams {
     float mask_level_redun, mask_level;
     int32_t qstride, tstride;           // per-job code-buffer strides (set after a round's step)
     int64_t ref_len, l_pac, id0;
+    ContigView ctg;                     // off != nullptr: dedup and patch compare regions of one contig only
     int8_t mat[25];
 };
 

@@ -141,8 +141,11 @@ static int dp_batch(bsw_ctx_t *ctx, const GlobParams &gp, Slot &s, int32_t n, ui
 }
 
 // the resident reference is the forward + reverse strands of an l_pac-base genome; the caller
-// holds dc.refmu shared
-static bool ref_ok(const DeviceCtx &dc, int64_t l_pac) { return dc.d_refres && dc.refres_len == 2 * l_pac; }
+// holds dc.refmu shared.  A contig table (bsw_contigs.h) has to sum to that l_pac
+static bool ref_ok(const DeviceCtx &dc, int64_t l_pac)
+{
+    return dc.d_refres && dc.refres_len == 2 * l_pac && dc.ctg_ok(l_pac);
+}
 
 }  // namespace bsw
 
@@ -166,6 +169,7 @@ static int reg2aln_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st
     p.n_reads = n_reads;
     p.cigar_stride = cigar_stride; p.md_stride = md_stride;
     p.ref_len = dc.refres_len; p.l_pac = opt.l_pac;
+    p.ctg = dc.ctg_view(opt.l_pac);
     memcpy(p.mat, pr.mat, 25);
     GlobParams gp;
     make_glob_params(pr, ctx->glob_band, gp);
@@ -232,7 +236,8 @@ static int reg2aln_check(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, DeviceCtx &dc
     if (n_reads < 0 || n_regs < 0 || cigar_stride < 1 || md_stride < 0 || (md == nullptr) != (md_stride == 0))
         return BSW_E_INVAL;
     if (!dc.d_refres) return BSW_E_INVAL;
-    if (opt->w < 0 || opt->w > (1 << 28) || opt->l_pac < 0 || (opt->l_pac > 0 && !ref_ok(dc, opt->l_pac)))
+    if (opt->w < 0 || opt->w > (1 << 28) || opt->l_pac < 0 || (opt->l_pac > 0 && !ref_ok(dc, opt->l_pac)) ||
+        !dc.ctg_ok(opt->l_pac))
         return BSW_E_INVAL;
     return BSW_OK;
 }
@@ -351,6 +356,7 @@ static int regs_select_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_
     p.mapQ_coef_len = opt.mapQ_coef_len; p.mapQ_coef_fac = opt.mapQ_coef_fac; p.patch = opt.patch;
     p.mask_level_redun = opt.mask_level_redun; p.mask_level = opt.mask_level;
     p.ref_len = dc.refres_len; p.l_pac = opt.l_pac; p.id0 = opt.id0;
+    p.ctg = dc.ctg_view(opt.l_pac);
     memcpy(p.mat, pr.mat, 25);
     GlobParams gp;
     make_glob_params(pr, ctx->glob_band, gp);
@@ -441,7 +447,8 @@ static int regs_select_check(const bsw_sel_opt_t *opt, DeviceCtx &dc, int32_t n_
 {
     if (n_reads < 0 || n_seeds < 0 || sel_cap < 0) return BSW_E_INVAL;
     if (!dc.d_refres) return BSW_E_INVAL;
-    if (opt->w < 0 || opt->w > (1 << 28) || opt->l_pac < 0 || (opt->l_pac > 0 && !ref_ok(dc, opt->l_pac)))
+    if (opt->w < 0 || opt->w > (1 << 28) || opt->l_pac < 0 || (opt->l_pac > 0 && !ref_ok(dc, opt->l_pac)) ||
+        !dc.ctg_ok(opt->l_pac))
         return BSW_E_INVAL;
     if (opt->max_chain_gap < 0 || opt->mapQ_coef_len < 0 || opt->b < 0 || opt->min_seed_len < 0) return BSW_E_INVAL;
     return BSW_OK;
@@ -577,7 +584,7 @@ static int pe_check_pes(const bsw_pestat_t *pes)
 // the stage reads no reference; one that is resident has to be the l_pac the call names
 static int pe_check_ref(const bsw_pe_opt_t &opt, DeviceCtx &dc)
 {
-    return !dc.d_refres || ref_ok(dc, opt.l_pac) ? BSW_OK : BSW_E_INVAL;
+    return dc.ctg_ok(opt.l_pac) && (!dc.d_refres || ref_ok(dc, opt.l_pac)) ? BSW_OK : BSW_E_INVAL;
 }
 
 static void make_pe_params(const bsw_ctx_t *ctx, const bsw_pe_opt_t &opt, int32_t n_reads, int32_t n_regs, PeParams &p)
@@ -592,6 +599,7 @@ static void make_pe_params(const bsw_ctx_t *ctx, const bsw_pe_opt_t &opt, int32_
     p.s.l_pac = opt.l_pac; p.s.id0 = opt.id0;
     p.n_pairs = n_reads / 2; p.n_regs = n_regs;
     p.max_ins = opt.max_ins; p.T = opt.T; p.pen_unpaired = opt.pen_unpaired;
+    p.ctg = ctx->devs[0]->ctg_view(opt.l_pac);              // (the stage's device; the caller holds its refmu shared)
 }
 
 // mem_pestat's per-direction arithmetic over the counts c[v] of insert size v (bsw_pe.h)
@@ -897,6 +905,7 @@ static int matesw_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st,
     p.s.l_pac = opt.l_pac; p.s.n_reads = n_reads;
     p.n_pairs = n_reads / 2; p.n_regs = n_regs;
     p.max_matesw = opt.max_matesw; p.pen_unpaired = opt.pen_unpaired;
+    p.ctg = p.s.ctg = dc.ctg_view(opt.l_pac);               // (the windows, and the dedup behind every call)
     for (int d = 0; d < 4; ++d) {
         p.pes[d].low = pes[d].low; p.pes[d].high = pes[d].high; p.pes[d].failed = pes[d].failed != 0;
     }
@@ -1188,7 +1197,8 @@ static int records_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st
     }
     BSW_TRY(tm.add(rs.helper_ms));
     BSW_TRY(tm.begin());
-    BSW_TRY(launch_rec_finish(io.lists, io.rec_first, io.recs, nrc, io.aln, io.cigar, cigar_stride, na, s.d_rmeta, st));
+    BSW_TRY(launch_rec_finish(io.lists, dc.ctg_view(opt.l_pac), io.rec_first, io.recs, nrc, io.aln, io.cigar, cigar_stride,
+                              na, s.d_rmeta, st));
     BSW_TRY(tm.end());
     BSW_TRY(hipMemcpyAsync(h_meta, s.d_rmeta, kRecMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     BSW_TRY(hipStreamSynchronize(st));
@@ -1213,9 +1223,14 @@ static int sam_text_check_args(const bsw_rec_opt_t *opt, int32_t n_rec, int32_t 
     return paired && (n_reads & 1) ? BSW_E_INVAL : BSW_OK;
 }
 
-static void make_rec_text(const bsw_rec_opt_t &opt, int32_t n_rec, int32_t n_aln, int32_t n_reads, int32_t paired,
-                          int32_t cigar_stride, int32_t md_stride, RecText &t)
+// the text calls read no reference; a contig table has to sum to the l_pac they name (the caller
+// holds dc.refmu shared, and keeps it while the kernels read the table)
+static bool text_ctg_ok(const DeviceCtx &dc, const bsw_rec_opt_t &opt) { return dc.ctg_ok(opt.l_pac); }
+
+static void make_rec_text(const DeviceCtx &dc, const bsw_rec_opt_t &opt, int32_t n_rec, int32_t n_aln, int32_t n_reads,
+                          int32_t paired, int32_t cigar_stride, int32_t md_stride, RecText &t)
 {
+    t.ctg = dc.ctg_view(opt.l_pac);
     t.n_rec = n_rec; t.n_aln = n_aln; t.n_reads = n_reads;
     t.n_names = paired ? n_reads / 2 : n_reads;
     t.cigar_stride = cigar_stride; t.md_stride = md_stride;
@@ -1395,11 +1410,13 @@ int bsw_sam_text_resident(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_re
         (text_cap > 0 && !d_text) || ((uintptr_t)d_text & 3))
         return BSW_E_INVAL;
     bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the contig table stays put
+    if (!bsw::text_ctg_ok(dc, *opt)) return BSW_E_INVAL;
     bsw::RecText t{};
     t.recs = d_recs; t.rec_first = d_rec_first; t.aln = d_aln; t.cigar = d_cigar; t.md = d_md;
     t.reads = d_reads; t.names = d_names; t.quals = d_quals;
     t.read_off = d_read_off; t.name_off = d_name_off; t.read_len = d_read_len;
-    bsw::make_rec_text(*opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, t);
+    bsw::make_rec_text(dc, *opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, t);
     float text_ms = 0.f;
     const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
         hipStream_t st = stream ? (hipStream_t)stream : s.stream;
@@ -1429,6 +1446,8 @@ int bsw_sam_text(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *recs
     for (size_t i = 0; i < nn; ++i)
         if (name_off[i] < 0 || name_off[i + 1] < name_off[i]) return BSW_E_RANGE;
     bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (!bsw::text_ctg_ok(dc, *opt)) return BSW_E_INVAL;
     const size_t nr = (size_t)n_reads, nc = (size_t)n_rec, na = (size_t)n_aln;
     bsw::StagedIo io;
     const auto d_recs = io.in(recs, nc);
@@ -1445,7 +1464,7 @@ int bsw_sam_text(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *recs
     const auto d_text = io.out(text, (size_t)text_cap);
     const auto d_text_off = io.out(text_off, nc + 1);
     bsw::RecText t{};
-    bsw::make_rec_text(*opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, t);
+    bsw::make_rec_text(dc, *opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, t);
     float text_ms = 0.f;
     const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
         BSW_TRY(io.stage(s));

@@ -51,6 +51,9 @@ MATESW_SYMBOLS = ("bsw_matesw_opt_default", "bsw_matesw", "bsw_matesw_resident",
 # include/bsw_rec.h (additive to ABI 8: BSW_REC_API)
 REC_SYMBOLS = ("bsw_rec_opt_default", "bsw_records", "bsw_records_resident", "bsw_sam_text", "bsw_sam_text_resident",
                "bsw_rec_last_stats")
+# include/bsw_contigs.h (additive to ABI 8: BSW_CONTIGS_API)
+CONTIGS_SYMBOLS = ("bsw_set_contigs", "bsw_fmi_set_contigs")
+CONTIG_MAX_NAME = 63
 
 # include/bsw.h engine options (bsw_set_option)
 OPT_KERNEL8, OPT_FORK, OPT_SORTKEY, OPT_GLOB_BAND, OPT_EXT_CHUNK, OPT_HOST_CHUNK, OPT_LONG, OPT_HOST_PACK = 1, 2, 3, 4, 5, 6, 7, 8
@@ -247,6 +250,10 @@ def hip_lib():
         L.bsw_rec_last_stats.argtypes = [P, P]
         for f in REC_SYMBOLS[1:]:
             getattr(L, f).restype = ctypes.c_int
+        L.bsw_set_contigs.argtypes = [P, i32, P, ctypes.POINTER(ctypes.c_char_p)]
+        L.bsw_set_contigs.restype = ctypes.c_int
+        L.bsw_fmi_set_contigs.argtypes = [P, i32, P]
+        L.bsw_fmi_set_contigs.restype = ctypes.c_int
         L.bsw_get_scores_packed_device.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int, P, P]
         for f in ("bsw_create", "bsw_create_on", "bsw_get_scores", "bsw_get_scores_device", "bsw_last_stats",
                   "bsw_pack_batch", "bsw_get_scores_packed_device",
@@ -451,6 +458,17 @@ def set_reference(engine, ref: np.ndarray):
     """bsw_set_reference: keep ref resident in HBM (for extend_seeds_device)."""
     ref = np.ascontiguousarray(ref, dtype=np.uint8)
     _check(hip_lib().bsw_set_reference(engine._ctx, _ptr(ref), len(ref)))
+
+
+def set_contigs(engine, lens=(), names=()):
+    """bsw_set_contigs (include/bsw_contigs.h): the contig table of the resident reference -- lengths and names
+    (str or bytes), one each per contig; no contigs removes the table."""
+    lens = np.ascontiguousarray(lens, dtype=np.int64)
+    if len(lens) != len(names):
+        raise ValueError("one name per contig")
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in names]
+    arr = (ctypes.c_char_p * max(len(raw), 1))(*raw)
+    _check(hip_lib().bsw_set_contigs(engine._ctx, len(lens), _ptr(lens) if len(lens) else None, arr))
 
 
 def extend_seeds_device(engine, d_reads: int, d_off: int, d_len: int, d_seeds: int, n: int, d_out: int,
@@ -1285,6 +1303,11 @@ class Fmi:
             self.close()
         except Exception:
             pass
+
+    def set_contigs(self, lens=()):
+        """bsw_fmi_set_contigs (include/bsw_contigs.h): the contig lengths for mem_chain_device; none removes them."""
+        lens = np.ascontiguousarray(lens, dtype=np.int64)
+        _check(hip_lib().bsw_fmi_set_contigs(self._f, len(lens), _ptr(lens) if len(lens) else None))
 
     def check(self) -> int:
         """bsw_fmi_check: number of violated index invariants (0 = consistent)"""

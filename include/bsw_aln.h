@@ -40,8 +40,12 @@
  *   if qb != 0 or qe != l_query: clip5 = is_rev ? l_query - qe : qb, clip3 = is_rev ? qb :
  *   l_query - qe; a nonzero clip5 is prepended, a nonzero clip3 appended as S
  *
- * CIGAR words are len << 4 | op, M = 0, I = 1, D = 2, S = 3.  Scope as bsw_fmi.h: ONE reference
- * sequence (no rid, no contig offset); pos is the 0-based forward coordinate.  opt->l_pac == 0
+ * CIGAR words are len << 4 | op, M = 0, I = 1, D = 2, S = 3.  Scope: pos is the 0-based forward
+ * coordinate on the concatenated text, with or without a contig table (no rid, no contig offset is
+ * stored).  With a table (bsw_set_contigs, bsw_contigs.h) the reject test reads it: a region with
+ * seg(rb) != seg(re - 1) is BSW_ALN_REJECTED (bns_intv2rid < 0), of which the l_pac test is the
+ * one-contig case; the table has to sum to opt->l_pac (l_pac == 0: to the resident length), or the
+ * call returns BSW_E_INVAL.  No ALT contigs.  opt->l_pac == 0
  * is a one-strand reference: every region is forward.
  *
  * A REJECTED region -- gen_cigar2's rejects above, rb < 0 or re < 0 (upstream's unmapped

@@ -16,7 +16,12 @@
  *     (mem_chain2aln's rmax[] computation).  bsw_extend_seeds treats every seed as a chain of one.
  *     Windows are clipped only at the strand boundary: the reference is ONE sequence (upstream
  *     also clips to the seed's contig, bns_fetch_seq; a multi-contig genome passed concatenated
- *     is extended across its contig joins -- see include/bsw_fmi.h "Scope").
+ *     is extended across its contig joins -- see include/bsw_fmi.h "Scope").  With a contig table
+ *     (bsw_set_contigs, include/bsw_contigs.h) the window is clipped, after the computation above, to
+ *     the segment of the chain's first seed instead (bns_fetch_seq with mid = seeds[0].rbeg; the strand
+ *     boundary is one more join), in the host-built and the device forms alike; a seed over a join is
+ *     BSW_E_RANGE; a table that does not sum to opt->l_pac (l_pac == 0: to ref_len) is BSW_E_INVAL.
+ *     No ALT contigs.
  *   LEFT  (qbeg > 0): query = reverse(read[0, qbeg)), target = reverse(ref[rmax0, rbeg)),
  *         h0 = sc, end_bonus = pen_clip5, band w << k for k < max_band_try (retry while the
  *         score changed and max_off >= 3/4 of the band)

@@ -24,7 +24,10 @@
  *     chain rid) and clips extension windows to the contig (bns_fetch_seq); here the only
  *     boundary is the forward / reverse strand one (l_pac).  A multi-sequence genome (GRCh38)
  *     must be given as one concatenated sequence, and seeds / chains / windows that cross its
- *     contig joins are NOT filtered as upstream filters them.
+ *     contig joins are NOT filtered as upstream filters them -- unless the contig table is set
+ *     (bsw_fmi_set_contigs for bsw_mem_chain_device, bsw_set_contigs for the context's calls;
+ *     bsw_contigs.h): then bridging seeds are dropped, a chain holds seeds of one contig, and
+ *     windows are clipped to the first seed's contig.  No ALT contigs.
  *   - reads shorter than ~720 bp.  Upstream's mem_align1_core runs mem_flt_chained_seeds
  *     between chaining and extension; it returns at once while MEM_MINSC_COEF * ln(l) >
  *     MEM_SEEDSW_COEF * l (5.5 ln l > 0.05 l: l <= 720 with min_chain_weight 0) and is not

@@ -4,7 +4,10 @@
  * of them.  This text is the specification; tests/matesw_py.py pins it.  All arithmetic is C's.
  * The stage runs between bsw_pe_stat* (whose pes[4] it consumes) and bsw_pe_pair* (whose step 1 is
  * the primary marking upstream runs after rescue): regs_select -> pe_stat -> matesw -> pe_pair ->
- * reg2aln.  Scope as bsw_pe.h: ONE reference sequence (rid = 0, no ALT), the resident text T =
+ * reg2aln.  Scope as bsw_pe.h: no ALT; with no contig table ONE reference sequence (rid = 0), with
+ * one (bsw_set_contigs, bsw_contigs.h; it has to sum to opt->l_pac) a window, after its clamp to [0, 2 l_pac),
+ * is clipped to the segment of its midpoint (rb + re) >> 1 instead of to that midpoint's strand, and its job
+ * exists only when that segment's contig is the anchor's and re - rb >= min_seed_len.  The resident text T =
  * forward + reverse complement, 2 * l_pac bases; reads 2p and 2p + 1 are pair p; a read's list is
  * a[e] as bsw_regs_select* left it (before bsw_pe_pair*'s step 1).  a = mat[0] and the gap penalties
  * come from the context.

@@ -6,7 +6,13 @@
  * tests/pe_py.py pins it.  All arithmetic is C's: `int` truncation, `double` where written, a
  * float option times an integer in single precision.  Reads 2p and 2p + 1 are the two ends of
  * pair p; "list" = a read's regions as bsw_regs_select* left them (bsw_sel.h), a[0] its first.
- * One reference sequence (rid = 0, no ALT: n_pri = n).  a = mat[0] and the gap penalties come from
+ * With no contig table one reference sequence (rid = 0); no ALT (n_pri = n).  With a table
+ * (bsw_set_contigs, bsw_contigs.h; it has to sum to opt->l_pac, BSW_E_INVAL otherwise) the rid of a
+ * region is that of its rb, and hits on different contigs are never a pair: bsw_pe_stat* takes no
+ * insert size from a pair whose two top regions differ in rid; mem_pair's v is sorted by upstream's
+ * rid << 32 | forward position - offset, which is the order of the global forward position, and its
+ * distance scan ends at a rid change; no_pairing's proper flag also needs equal rids.  Coordinates
+ * stay global.  a = mat[0] and the gap penalties come from
  * the context, as in bsw_sel.h.  Mate rescue (mem_matesw) is bsw_matesw.h's: it consumes pes[] and
  * slots between the two calls below without changing them.
  *

@@ -7,9 +7,17 @@
  * it.  "list" = a read's regions as bsw_regs_select* (single-end) or bsw_pe_pair* (paired-end) left
  * them, info = their bsw_selinfo_t; reads 2p and 2p + 1 are the two ends of pair p.
  *
- * SCOPE.  One reference sequence (rid 0, its name opt->rname); no ALT contigs (is_alt = 0, n_pri =
- * n, secondary_all == secondary); MEM_F_ALL (-a) off; no RG tag, no comment.  File I/O, the header
- * and the command line are the caller's.
+ * SCOPE.  With no contig table one reference sequence (rid 0, its name opt->rname).  With a table
+ * (bsw_set_contigs, bsw_contigs.h) the rids are derived from the global positions: a record's from
+ * pos, its mate's from mpos, both after cross-linking (an unmapped end takes its mate's); TLEN is 0
+ * unless the two are equal (mem_aln2sam: p->rid == m->rid); the text prints the contig's name for
+ * `rname` and pos - offset + 1 for `pos + 1` wherever they stand below, each SA:Z / XA:Z entry its
+ * own contig's, and RNEXT is `=` only when the rids are equal, else the mate's contig name.
+ * opt->rname is then not printed (the argument check on it stays, so that it needs no context), and
+ * opt->l_pac has to be the sum of the contig lengths in the text calls too (BSW_E_INVAL).  pos, mpos
+ * and every bsw_aln_t.pos stay global.  No ALT contigs (is_alt = 0, n_pri = n, secondary_all ==
+ * secondary); MEM_F_ALL (-a) off; no RG tag, no comment.  File I/O, the header and the command line
+ * are the caller's.
  *
  * ALIGNMENTS (mem_reg2aln).  The unmapped alignment (mem_reg2aln(.., 0)): pos -1, flag 0x4,
  *   n_cigar 0, everything else 0 -- `AS:i:0 XS:i:0` are printed.  The alignment of region r takes

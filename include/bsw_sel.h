@@ -77,8 +77,12 @@
  * mapQ_coef_fac is an int upstream: log(50) truncates to 3, the default here.  The device
  * computes MAPQ in double precision.
  *
- * Scope as bsw_aln.h: ONE reference sequence.  a, b aside, scoring comes from the context's
- * parameters (a = mat[0], the gap penalties); b is an option because the matrix does not name it.
+ * Scope: no ALT contigs; with no contig table ONE reference sequence, with one (bsw_set_contigs,
+ * bsw_contigs.h; it has to sum to opt->l_pac) dedup and patch keep to one contig: the outer skip also
+ * moves on when p and a[i - 1] lie on different contigs, the inner loop runs only while p and a[j]
+ * lie on one, so no region is dropped for, or patched with, one of another contig.  a, b aside,
+ * scoring comes from the context's parameters (a = mat[0], the gap penalties); b is an option because
+ * the matrix does not name it.
  *
  * Purely additive to ABI version 8 (bsw_abi_version() is unchanged); this header carries its own
  * BSW_SEL_API.
