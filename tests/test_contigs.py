@@ -25,15 +25,15 @@ import pytest
 
 import bsw
 import contigs_py as cp
-import hiprt
 import rec_py as rq
 import reg2aln_py as rp
 import regsel_py as sp
 from conftest import ROOT
+from resident import ResidentBatch
+from stagekit import (DEFAULT, RECORDS, declared, exported, fetch, got_aln, got_pair, got_text, mat_gaps, revcomp,
+                      same_aln, same_msw, same_records, same_sel, same_text)
 from test_matesw import MsBatch, reg, rnd
-from test_rec import RNAME, _gpu_case, _resident_records_and_text, _same_records, _same_text, pairs_of, rec_set
-from test_reg2aln import DEFAULT, _same as _same_aln, revcomp
-from test_regsel import _mat_gaps
+from test_rec import RNAME, _gpu_case, pairs_of, rec_set
 
 LENS = (5000, 100, 1200, 7777)
 NAMES = ("1", "chrB_" + "x" * 58, "chrC", "chrD")
@@ -46,7 +46,7 @@ REF[OC + 300:OC + 400] = REF[1000:1100]                      # the unit of conti
 REF[9000:9100] = REF[1000:1100]                              # .. and in chrD, one substitution
 REF[9040] = (REF[9040] + 1) % 4
 T2 = np.concatenate([REF, 3 - REF[::-1]]).astype(np.uint8)
-MAT, GAPS = _mat_gaps(DEFAULT)
+MAT, GAPS = mat_gaps(DEFAULT)
 
 
 def rv(s, e):
@@ -325,14 +325,12 @@ def test_one_contig_named_like_rname_is_no_table():
 def test_library_exports_the_contigs_header():
     src = open(os.path.join(ROOT, "include", "bsw_contigs.h")).read()
     assert re.search(r"#define BSW_CONTIGS_API 1\b", src) and re.search(r"#define BSW_CONTIG_MAX_NAME 63\b", src)
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(bsw_[a-z_0-9]+)\s*\(", src))
-    assert declared == set(bsw.CONTIGS_SYMBOLS)
-    out = subprocess.run(["nm", "-D", "--defined-only", bsw.HIP_LIB], capture_output=True, text=True).stdout
-    assert declared <= set(re.findall(r" T (bsw_\w+)", out))
+    decl = declared("bsw_contigs.h")
+    assert decl == set(bsw.CONTIGS_SYMBOLS)
+    assert decl <= exported()
     others = (set(bsw.ABI_SYMBOLS) | set(bsw.ALN_SYMBOLS) | set(bsw.SEL_SYMBOLS) | set(bsw.PE_SYMBOLS) |
               set(bsw.MATESW_SYMBOLS) | set(bsw.REC_SYMBOLS))
-    assert not declared & others and len(bsw.ABI_SYMBOLS) == 45 and bsw.hip_lib().bsw_abi_version() == 8
+    assert not decl & others and len(bsw.ABI_SYMBOLS) == 45 and bsw.hip_lib().bsw_abi_version() == 8
     for cc, ext in (("gcc", "c"), ("g++", "cpp")):
         r = subprocess.run([cc, "-fsyntax-only", "-x", "c" if ext == "c" else "c++", "-I", os.path.join(ROOT, "include"),
                             os.path.join(ROOT, "include", "bsw_contigs.h")], capture_output=True, text=True)
@@ -378,27 +376,23 @@ def test_gpu_reg2aln_rejects_over_every_join():
     eng = _engine()
     o = bsw.ext_opt(l_pac=L)
     plain = bsw.reg2aln(eng, reads, off, lens, regs, rr, o)
-    _same_aln(rp.reg2aln(T2, L, reads, off, lens, regs, rr, MAT, GAPS, 100)[:3], plain, "no table")
+    same_aln(rp.reg2aln(T2, L, reads, off, lens, regs, rr, MAT, GAPS, 100)[:3], plain, "no table")
     bsw.set_contigs(eng, LENS, NAMES)
     got = bsw.reg2aln(eng, reads, off, lens, regs, rr, o)
-    _same_aln(cp.reg2aln(TAB, T2, reads, off, lens, regs, rr, MAT, GAPS, 100)[:3], got, "table")
+    same_aln(cp.reg2aln(TAB, T2, reads, off, lens, regs, rr, MAT, GAPS, 100)[:3], got, "table")
     assert list(np.flatnonzero((got[0]["flags"] ^ plain[0]["flags"]) & bsw.ALN_REJECTED)) == [2, 3, 4, 7, 11] and ok.sum() == 11
     assert bsw.aln_last_stats(eng).n_rejected == 7
     # the resident form
-    d = [hiprt.DeviceBuffer.from_array(np.ascontiguousarray(x)) for x in (reads, off, lens, regs, rr)]
-    n = len(regs)
-    d_aln, d_cig, d_md = hiprt.DeviceBuffer(n * 40), hiprt.DeviceBuffer(n * 16 * 4), hiprt.DeviceBuffer(n * 64)
-    for buf, nb in ((d_cig, n * 64), (d_md, n * 64)):
-        hiprt.check(hiprt.rt().hipMemset(ctypes.c_void_p(buf.ptr), 0, nb))
-    bsw.reg2aln_resident(eng, d[0].ptr, d[1].ptr, d[2].ptr, n, d[3].ptr, d[4].ptr, n, d_aln.ptr, d_cig.ptr, 16, d_md.ptr, 64, o)
-    res = (d_aln.download(np.zeros(n, dtype=bsw.ALN_DTYPE)), d_cig.download(np.zeros((n, 16), np.uint32)),
-           d_md.download(np.zeros((n, 64), np.uint8)))
-    _same_aln(got, res, "resident")
+    b = ResidentBatch(eng, reads, off, lens)
+    b.put(regs=regs, sr=rr)
+    b.reg2aln(o)
+    res = got_aln(b)
+    same_aln(got, res, "resident")
     # one contig == no table; no contigs removes the table
     bsw.set_contigs(eng, [L], [RNAME])
-    _same_aln(plain, bsw.reg2aln(eng, reads, off, lens, regs, rr, o), "one contig")
+    same_aln(plain, bsw.reg2aln(eng, reads, off, lens, regs, rr, o), "one contig")
     bsw.set_contigs(eng)
-    _same_aln(plain, bsw.reg2aln(eng, reads, off, lens, regs, rr, o), "table removed")
+    same_aln(plain, bsw.reg2aln(eng, reads, off, lens, regs, rr, o), "table removed")
     eng.close()
 
 
@@ -427,15 +421,14 @@ def test_gpu_hand_set_device_to_device(name):
     reads, off, lens, regs, info, first = w.arrays
     eng = _engine()
     bsw.set_contigs(eng, LENS, NAMES)
-    d = {k: hiprt.DeviceBuffer.from_array(np.ascontiguousarray(v)) for k, v in (("reads", reads), ("off", off), ("lens", lens))}
-    d_regs = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(regs, dtype=bsw.ALNREG_DTYPE))
-    d_info = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(info, dtype=bsw.SELINFO_DTYPE))
-    d_first = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(first, dtype=np.int32))
-    d_pairs = None if h.pairs is None else hiprt.DeviceBuffer.from_array(np.ascontiguousarray(h.pairs, dtype=bsw.PAIR_DTYPE))
-    rec, txt = _resident_records_and_text(eng, w, d, d_regs.ptr, d_info.ptr, d_first.ptr, d_pairs.ptr if d_pairs else 0,
-                                          len(lens), len(regs), bsw.rec_opt(**w.opt), h.names, h.quals, h.pairs is not None)
-    _same_records(w, rec, f"{name} resident", bsw.rec_last_stats(eng))
-    _same_text(w.text, w.text_off, txt, f"{name} resident")
+    b = ResidentBatch(eng, reads, off, lens, h.quals)
+    b.put(sreg=regs, sinfo=info, sfirst=first, **({} if h.pairs is None else {"pairs": h.pairs}))
+    b.records(bsw.rec_opt(**w.opt), paired=h.pairs is not None)
+    rec = fetch(b, *RECORDS)
+    b.sam_text(bsw.rec_opt(**w.opt), h.names, h.pairs is not None, cap=len(w.text) + 5)
+    txt = got_text(b)
+    same_records(w, rec, f"{name} resident", bsw.rec_last_stats(eng))
+    same_text(w.text, w.text_off, txt, f"{name} resident")
     eng.close()
 
 
@@ -454,20 +447,18 @@ def test_gpu_one_contig_is_no_table_on_the_pipeline_set():
         recs, rfirst, aln, aln_reg, cig, md = got
         return got, bsw.sam_text(eng, recs, rfirst, aln, cig, md, a["reads"], a["off"], a["lens"], s.names, s.quals, opt, True)
 
-    d = {k: hiprt.DeviceBuffer.from_array(np.ascontiguousarray(a[k])) for k in ("reads", "off", "lens")}
-    nr, m = len(a["lens"]), len(s.regs)
-    d_regs = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(s.regs, dtype=bsw.ALNREG_DTYPE))
-    d_info = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(s.info, dtype=bsw.SELINFO_DTYPE))
-    d_first = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(p.mfirst, dtype=np.int32))
-    d_pairs = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(s.pairs, dtype=bsw.PAIR_DTYPE))
+    b = ResidentBatch(eng, a["reads"], a["off"], a["lens"], s.quals)
+    b.put(mreg=s.regs, minfo=s.info, mfirst=p.mfirst, pairs=s.pairs)
 
     def resident(opt):
-        return _resident_records_and_text(eng, s, d, d_regs.ptr, d_info.ptr, d_first.ptr, d_pairs.ptr, nr, m, opt, s.names,
-                                          s.quals, True)
+        b.records(opt)
+        rec = fetch(b, *RECORDS)
+        b.sam_text(opt, s.names, True, cap=len(s.text) + 5)
+        return rec, got_text(b)
 
     base = host(o), resident(o)
-    _same_records(s.res, base[0][0], "no table")
-    _same_text(s.text, s.text_off, base[0][1], "no table")
+    same_records(s.res, base[0][0], "no table")
+    same_text(s.text, s.text_off, base[0][1], "no table")
     bsw.set_contigs(eng, [p.l_pac], [RNAME])
     for opt, tag in ((o, "one contig"), (bsw.rec_opt(**dict(s.opt, rname="unread")), "rname unread")):
         for (rec0, txt0), (rec1, txt1), form in zip(base, (host(opt), resident(opt)), ("host", "resident")):
@@ -641,15 +632,12 @@ def test_gpu_paired_end_stage_by_contig():
     same(got, s["stat"][0], s["pair"], "table")
     assert not np.array_equal(got[1][2]["paired"], plain[1][2]["paired"]) and got[0][1]["n"] == 31 and plain[0][1]["n"] == 35
     # the resident form, in place
-    nr, m = len(first) - 1, len(regs)
-    d_regs = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(regs, dtype=bsw.ALNREG_DTYPE))
-    d_info = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(info, dtype=bsw.SELINFO_DTYPE))
-    d_first = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(first, dtype=np.int32))
-    d_pairs = hiprt.DeviceBuffer((nr // 2) * bsw.PAIR_DTYPE.itemsize)
-    pes = bsw.pe_stat_resident(eng, d_regs.ptr, d_info.ptr, d_first.ptr, nr, m, o)
-    bsw.pe_pair_resident(eng, pes, d_regs.ptr, d_info.ptr, d_first.ptr, nr, m, d_pairs.ptr, o)
-    res = (d_regs.download(np.zeros(m, dtype=bsw.ALNREG_DTYPE)), d_info.download(np.zeros(m, dtype=bsw.SELINFO_DTYPE)),
-           d_pairs.download(np.zeros(nr // 2, dtype=bsw.PAIR_DTYPE)))
+    nr = len(first) - 1
+    b = ResidentBatch(eng, np.zeros(1, np.uint8), np.zeros(nr, np.int64), np.zeros(nr, np.int32))   # (neither call reads the reads)
+    b.put(sreg=regs, sinfo=info, sfirst=first)
+    pes = b.pe_stat(o)
+    b.pe_pair(pes, o)
+    res = got_pair(b)
     same((pes, res), s["stat"][0], s["pair"], "resident")
     # no_pairing's proper flag
     given, (r1, i1, f1), want_plain, want, _ = nopair_case()
@@ -712,17 +700,16 @@ def test_rescue_windows_by_contig():
 
 @pytest.mark.gpu
 def test_gpu_rescue_windows_by_contig():
-    from test_matesw import _same as _same_msw
     s = msw_set()
     o = bsw.matesw_opt(l_pac=L)
     eng = _engine()
-    _same_msw(s["plain"], bsw.matesw(eng, s["pes"], *s["arr"], o), "no table", bsw.matesw_last_stats(eng))
+    same_msw(s["plain"], bsw.matesw(eng, s["pes"], *s["arr"], o), "no table", bsw.matesw_last_stats(eng))
     bsw.set_contigs(eng, LENS, NAMES)
     got = bsw.matesw(eng, s["pes"], *s["arr"], o)
-    _same_msw(s["table"], got, "table", bsw.matesw_last_stats(eng))
+    same_msw(s["table"], got, "table", bsw.matesw_last_stats(eng))
     assert _mate_lists((0, 0, 0, got[3])) == [1, 1, 0, 0, 1]
     bsw.set_contigs(eng, [L], [RNAME])
-    _same_msw(s["plain"], bsw.matesw(eng, s["pes"], *s["arr"], o), "one contig", bsw.matesw_last_stats(eng))
+    same_msw(s["plain"], bsw.matesw(eng, s["pes"], *s["arr"], o), "one contig", bsw.matesw_last_stats(eng))
     eng.close()
 
 
@@ -854,24 +841,20 @@ def test_pipeline_under_the_table_reaches_every_rid_branch():
 def test_gpu_pipeline_under_the_table():
     """seeding -> chaining -> extension (host-built and resident) -> selection -> statistics -> rescue -> pairing ->
     records -> text, device to device under the table, each stage against the restatement"""
-    from test_matesw import _same as _same_msw
-    from test_regsel import _same as _same_sel
     p = pipe()
     reads, off, lens = p.reads, p.off, p.lens
     nr = len(lens)
     fmi = bsw.Fmi(REF)
     eng = _engine()
-    d_reads = hiprt.DeviceBuffer.from_array(reads)
-    plain, _, _ = bsw.seed_and_chain(fmi, d_reads, off, lens)
+    b = ResidentBatch(eng, reads, off, lens, p.quals)
+    plain = b.seed_and_chain(fmi)
     for x, y in zip(plain, p.plain_seeds):
         assert np.array_equal(x, y), "no table: seeds"
     # one contig == no table at the front stages too: seeds, regions (resident and host-built), selection
     def front():
-        (s_, r_, c_), (ds, dr, dc_), (do, dl) = bsw.seed_and_chain(fmi, d_reads, off, lens)
-        n_ = len(s_)
-        dg, de = hiprt.DeviceBuffer(n_ * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(n_ * 4)
-        bsw.chain2aln_resident(eng, d_reads.ptr, do.ptr, dl.ptr, nr, ds.ptr, dr.ptr, dc_.ptr, n_, dg.ptr, de.ptr, p.eopt)
-        g_, e_ = dg.download(np.zeros(n_, dtype=bsw.ALNREG_DTYPE)), de.download(np.zeros(n_, np.int32))
+        s_, r_, c_ = b.seed_and_chain(fmi)
+        b.chain2aln(p.eopt)
+        g_, e_ = b.get("regs"), b.get("ext")
         h_ = bsw.chain2aln(eng, T2, reads, off, lens, s_, r_, c_, p.eopt)
         sel_ = bsw.regs_select(eng, reads, off, lens, s_, r_, c_, g_, e_, bsw.sel_opt(l_pac=L))
         return [s_, r_, c_, g_, e_, h_[0], h_[1]] + list(sel_)
@@ -884,7 +867,7 @@ def test_gpu_pipeline_under_the_table():
     bsw.set_contigs(eng, LENS, NAMES)
     fmi.set_contigs(LENS[:3])
     with pytest.raises(bsw.BswError, match="-22"):
-        bsw.seed_and_chain(fmi, d_reads, off, lens)
+        b.seed_and_chain(fmi)
     with pytest.raises(bsw.BswError, match="-22"):             # the extension calls check the context's table
         bsw.set_contigs(eng, LENS[:3], NAMES[:3])
         bsw.chain2aln(eng, T2, reads, off, lens, plain[0], plain[1], plain[2], p.eopt)
@@ -893,47 +876,33 @@ def test_gpu_pipeline_under_the_table():
         with pytest.raises(bsw.BswError, match="-22"):
             fmi.set_contigs(bad)
     fmi.set_contigs(LENS)
-    (seeds, sr, sc), (d_seeds, d_sr, d_sc), (d_off, d_len) = bsw.seed_and_chain(fmi, d_reads, off, lens)
+    seeds, sr, sc = b.seed_and_chain(fmi)
     assert np.array_equal(seeds, p.seeds) and np.array_equal(sr, p.sr) and np.array_equal(sc, p.sc), "seeds"
-    n = len(seeds)
-    d_regs, d_ext = hiprt.DeviceBuffer(n * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(n * 4)
-    bsw.chain2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, nr, d_seeds.ptr, d_sr.ptr, d_sc.ptr, n, d_regs.ptr,
-                           d_ext.ptr, p.eopt)
-    regs, ext = d_regs.download(np.zeros(n, dtype=bsw.ALNREG_DTYPE)), d_ext.download(np.zeros(n, np.int32))
+    b.chain2aln(p.eopt)
+    regs, ext = b.get("regs"), b.get("ext")
     assert np.array_equal(ext, p.ext), np.flatnonzero(ext != p.ext)[:5]
     assert regs.tobytes() == np.ascontiguousarray(p.regs, dtype=bsw.ALNREG_DTYPE).tobytes(), "regions"
     hregs, hext = bsw.chain2aln(eng, T2, reads, off, lens, seeds, sr, sc, p.eopt)     # the host-built form
     assert hregs.tobytes() == regs.tobytes() and np.array_equal(hext, ext), "host-built == resident"
-    d_sreg, d_srd = hiprt.DeviceBuffer(n * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(n * 4)
-    d_info, d_first = hiprt.DeviceBuffer(n * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((nr + 1) * 4)
-    k = bsw.regs_select_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, nr, d_seeds.ptr, d_sr.ptr, d_sc.ptr, d_regs.ptr,
-                                 d_ext.ptr, n, d_sreg.ptr, d_srd.ptr, d_info.ptr, d_first.ptr, n, bsw.sel_opt(l_pac=L))
+    k = b.select(bsw.sel_opt(l_pac=L))
     assert k == len(p.sel[0])
-    gsel = (d_sreg.download(np.zeros(n, dtype=bsw.ALNREG_DTYPE))[:k], d_srd.download(np.zeros(n, np.int32))[:k],
-            d_info.download(np.zeros(n, dtype=bsw.SELINFO_DTYPE))[:k], d_first.download(np.zeros(nr + 1, np.int32)))
-    _same_sel(p.sel, gsel, "selection")
+    same_sel(p.sel, fetch(b, *b.lists[0]), "selection")
     o = bsw.pe_opt(l_pac=L)
-    pes = bsw.pe_stat_resident(eng, d_sreg.ptr, d_info.ptr, d_first.ptr, nr, k, o)
+    pes = b.pe_stat(o)
     for fl in ("low", "high", "failed", "n"):
         assert np.array_equal(pes[fl], p.pes[fl]), fl
     cap = len(p.msw[0])
-    d_oreg, d_ord = hiprt.DeviceBuffer(cap * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(cap * 4)
-    d_oinfo, d_ofirst = hiprt.DeviceBuffer(cap * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((nr + 1) * 4)
-    m = bsw.matesw_resident(eng, pes, d_reads.ptr, d_off.ptr, d_len.ptr, nr, d_sreg.ptr, d_info.ptr, d_first.ptr, k,
-                            d_oreg.ptr, d_ord.ptr, d_oinfo.ptr, d_ofirst.ptr, cap, bsw.matesw_opt(l_pac=L))
+    m = b.matesw(pes, bsw.matesw_opt(l_pac=L), cap=cap)
     assert m == cap
-    gm = (d_oreg.download(np.zeros(cap, dtype=bsw.ALNREG_DTYPE)), d_ord.download(np.zeros(cap, np.int32)),
-          d_oinfo.download(np.zeros(cap, dtype=bsw.SELINFO_DTYPE)), d_ofirst.download(np.zeros(nr + 1, np.int32)))
-    _same_msw(p.msw, gm, "rescue", bsw.matesw_last_stats(eng))
-    d_pairs = hiprt.DeviceBuffer((nr // 2) * bsw.PAIR_DTYPE.itemsize)
-    bsw.pe_pair_resident(eng, pes, d_oreg.ptr, d_oinfo.ptr, d_ofirst.ptr, nr, m, d_pairs.ptr, o)
-    gp = d_pairs.download(np.zeros(nr // 2, dtype=bsw.PAIR_DTYPE))
+    same_msw(p.msw, fetch(b, *b.lists[0]), "rescue", bsw.matesw_last_stats(eng))
+    b.pe_pair(pes, o)
+    gp = b.get("pairs")
     for fl in bsw.PAIR_DTYPE.names:
         assert np.array_equal(gp[fl], p.paired[2][fl]), fl
-    d = dict(reads=d_reads, off=d_off, lens=d_len)
-    rec, txt = _resident_records_and_text(eng, p, d, d_oreg.ptr, d_oinfo.ptr, d_ofirst.ptr, d_pairs.ptr, nr, m,
-                                          bsw.rec_opt(**p.ropt), p.names, p.quals, True)
-    _same_records(p.res, rec, "pipeline", bsw.rec_last_stats(eng))
-    _same_text(p.text, p.text_off, txt, "pipeline")
+    b.records(bsw.rec_opt(**p.ropt))
+    rec = fetch(b, *RECORDS)
+    b.sam_text(bsw.rec_opt(**p.ropt), p.names, True, cap=len(p.text) + 5)
+    same_records(p.res, rec, "pipeline", bsw.rec_last_stats(eng))
+    same_text(p.text, p.text_off, got_text(b), "pipeline")
     eng.close()
     fmi.close()

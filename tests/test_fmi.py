@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "bwa-mem2-arm_amd", "py"))
 import oracle  # noqa: E402
 import bsw  # noqa: E402
+from resident import ResidentBatch  # noqa: E402
 
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 
@@ -568,18 +569,14 @@ def test_wide_index_at_genome_scale_text_and_oracle():
     sa_rows = np.zeros(max(base, 1), dtype=np.int64)
     sa_rows[np.concatenate(dst)] = pos_of(np.concatenate(src))
     seeds, sr, sc = oracle.mem_chain(sa_rows, len(ref), lens, mems_c, cnt, copt)
-    d_reads = hiprt.DeviceBuffer.from_array(reads)
-    (gs, gsr, gsc), (d_s, d_sr, d_sc), (d_off, d_len) = bsw.seed_and_chain(f, d_reads, off, lens, cap=cap)
-    assert np.array_equal(gsr, sr) and np.array_equal(gsc, sc) and np.array_equal(gs, seeds)
     eng = bsw.Engine()
     bsw.set_reference(eng, T)
+    b = ResidentBatch(eng, reads, off, lens)
+    gs, gsr, gsc = b.seed_and_chain(f, cap=cap)
+    assert np.array_equal(gsr, sr) and np.array_equal(gsc, sc) and np.array_equal(gs, seeds)
     opt = bsw.ext_opt(l_pac=len(ref))
-    ns = len(seeds)
-    d_out, d_ext = hiprt.DeviceBuffer(max(1, ns) * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(max(1, ns) * 4)
-    bsw.chain2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, len(lens), d_s.ptr, d_sr.ptr, d_sc.ptr, ns,
-                           d_out.ptr, d_ext.ptr, opt)
-    out = d_out.download(np.zeros(ns, dtype=bsw.ALNREG_DTYPE))
-    ext = d_ext.download(np.zeros(ns, dtype=np.int32))
+    b.chain2aln(opt)
+    out, ext = b.get("regs"), b.get("ext")
     want, wext = oracle.chain2aln(oracle.make_params(), opt, T, reads, off, lens, seeds, sr, sc, nthreads=8)
     assert np.array_equal(ext, wext)
     for fld in bsw.ALNREG_DTYPE.names:

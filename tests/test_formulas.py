@@ -16,7 +16,7 @@ import pytest
 import pe_py as pp
 import reg2aln_py as rp
 from conftest import ROOT
-from test_reg2aln import SCORINGS
+from stagekit import SCORINGS
 
 LENS = (0, 1, 2, 19, 150, 151, 10000)
 BANDS = (1, 100, 400)

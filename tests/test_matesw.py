@@ -28,9 +28,11 @@ import pe_py as pp
 import reg2aln_py as rp
 import regsel_py as sp
 from conftest import ROOT
-from test_pe import _pes, _same_pair, _same_pes
-from test_reg2aln import DEFAULT, SCORINGS, revcomp
-from test_regsel import _mat_gaps, _select
+from resident import ResidentBatch
+from stagekit import (DEFAULT, SCORINGS, declared, engine_of, exported, fetch, got_aln, got_pair, mat_gaps, revcomp,
+                      same_aln, same_msw, same_pair, same_pes)
+from test_pe import _pes
+from test_regsel import _select
 
 L = 30_000                                                   # l_pac of the hand text
 RL = 100
@@ -109,7 +111,7 @@ class MsBatch:
 
 
 def _run(batch, pes, scoring=DEFAULT, ksw=kp.ksw_align2, jobs=None, text=T, **optkw):
-    mat, gaps = _mat_gaps(scoring)
+    mat, gaps = mat_gaps(scoring)
     reads, off, lens, regs, info, first = batch.arrays(scoring[0])
     return mp.mate_rescue(pes, text, reads, off, lens, regs, info, first, mp.matesw_opt(l_pac=L, **optkw), mat, gaps,
                           ksw, jobs=jobs)
@@ -146,7 +148,7 @@ def test_basic_fr_rescue():
     assert list(first) == [0, 1, 2] and _fields(regs[1]) == (rb, rb + 100, 0, 100, 70) and rb == 2 * L - 1501
     # csub = score2, the best row maximum >= 19 outside te -+ 70 rows: chance similarity in a 500-base window
     # (the C oracle on the same job says which)
-    mat, gaps = _mat_gaps(DEFAULT)
+    mat, gaps = mat_gaps(DEFAULT)
     q = [int(c) for c in REF[1401:1501]]
     for k in (11, 27, 43, 59, 75, 91):
         q[k] = 3 - ((3 - q[k] + 1) % 4)
@@ -417,7 +419,7 @@ def test_both_ksw_formulations_agree_on_every_hand_job():
     for g in GROUPS:
         for sc, mir in ((DEFAULT, False), (SCORINGS[2], True)):
             b, pes, kw, want, jobs, text = hand_want(g, sc, mir)
-            mat, gaps = _mat_gaps(sc)
+            mat, gaps = mat_gaps(sc)
             for q, t, xtra in jobs:
                 assert kp.ksw_align2(q, t, mat, *gaps, xtra) == oracle.ksw_align2(q, t, mat, *gaps, xtra)
                 n += 1
@@ -469,7 +471,7 @@ class MsSet:
         self.regs, _, self.info, self.first, _ = self.sel
         self.opt = pp.pe_opt(l_pac=self.l_pac)
         self.mopt = mp.matesw_opt(l_pac=self.l_pac)
-        self.mat, self.gaps = _mat_gaps(DEFAULT)
+        self.mat, self.gaps = mat_gaps(DEFAULT)
         self.pes, self.tr_stat, _ = pp.pe_stat(self.regs, self.info, self.first, self.opt, 1)
         self.want = mp.mate_rescue(self.pes, Tt, reads, off, lens, self.regs, self.info, self.first, self.mopt,
                                    self.mat, self.gaps, oracle.ksw_align2)
@@ -517,17 +519,9 @@ def test_combined_sets_reach_every_branch():
 
 
 # ---------------------------------------------------------------- CPU: the header
-def _declared():
-    src = open(os.path.join(ROOT, "include", "bsw_matesw.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return set(re.findall(r"\b(bsw_[a-z_0-9]+)\s*\(", src))
-
-
 def test_library_exports_the_matesw_header():
-    assert _declared() == set(bsw.MATESW_SYMBOLS)
-    out = subprocess.run(["nm", "-D", "--defined-only", bsw.HIP_LIB], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (bsw_\w+)", out))
-    assert _declared() <= exported, _declared() - exported
+    assert declared("bsw_matesw.h") == set(bsw.MATESW_SYMBOLS)
+    assert declared("bsw_matesw.h") <= exported(), declared("bsw_matesw.h") - exported()
     others = set(bsw.ABI_SYMBOLS) | set(bsw.ALN_SYMBOLS) | set(bsw.SEL_SYMBOLS) | set(bsw.PE_SYMBOLS)
     assert not set(bsw.MATESW_SYMBOLS) & others
     assert len(bsw.ABI_SYMBOLS) == 45 and bsw.hip_lib().bsw_abi_version() == 8
@@ -583,30 +577,6 @@ def test_defaults_and_invalid_arguments_need_no_device():
 
 
 # ---------------------------------------------------------------- GPU
-def _engine(scoring=DEFAULT):
-    a, b, od, ed, oi, ei = scoring
-    eng = bsw.Engine(bsw.default_params(a=a, b=b, o_del=od, e_del=ed, o_ins=oi, e_ins=ei))
-    return eng
-
-
-def _same(want, got, tag, st=None):
-    wr, wd, wi, wf, tr = want
-    gr, gd, gi, gf = got
-    assert np.array_equal(wf, gf), f"{tag}: first differs at {np.flatnonzero(wf != gf)[:5]}: want {wf[:12]} got {gf[:12]}"
-    assert len(wr) == len(gr), tag
-    assert np.array_equal(wd, gd), f"{tag}: reg_read"
-    for f in sp.ALNREG_FIELDS:
-        bad = np.flatnonzero(wr[f] != gr[f])
-        assert len(bad) == 0, f"{tag}: {f} differs at {len(bad)} regions, first {bad[:5]}: want {wr[f][bad[:5]]} got {gr[f][bad[:5]]}"
-    for f in bsw.SELINFO_DTYPE.names:
-        bad = np.flatnonzero(wi[f] != gi[f])
-        assert len(bad) == 0, f"{tag}: info.{f} differs at {len(bad)} regions, first {bad[:5]}: want {wi[f][bad[:5]]} got {gi[f][bad[:5]]}"
-    if st is not None:
-        for k, v in mp.stats_of(tr, (len(wf) - 1) // 2, len(wr)).items():
-            assert getattr(st, k) == v, f"{tag}: stats {k} = {getattr(st, k)}, want {v}"
-        assert (st.sw_ms > 0) == (tr.cnt["jobs"] > 0), tag
-
-
 def _gpu(eng, batch, pes, scoring=DEFAULT, **kw):
     reads, off, lens, regs, info, first = batch.arrays(scoring[0])
     return bsw.matesw(eng, pes, reads, off, lens, regs, info, first, bsw.matesw_opt(l_pac=L, **kw))
@@ -615,13 +585,13 @@ def _gpu(eng, batch, pes, scoring=DEFAULT, **kw):
 @pytest.mark.gpu
 @pytest.mark.parametrize("scoring", SCORINGS)
 def test_gpu_hand_set(scoring):
-    eng = _engine(scoring)
+    eng = engine_of(scoring)
     bsw.set_reference(eng, T)
     for mirror in (False, True):
         bsw.set_reference(eng, T_MIRROR if mirror else T)
         for g in GROUPS:
             b, pes, kw, want, jobs, text = hand_want(g, scoring, mirror)
-            _same(want, _gpu(eng, b, pes, scoring, **kw), f"hand {g} {scoring} {mirror}", bsw.matesw_last_stats(eng))
+            same_msw(want, _gpu(eng, b, pes, scoring, **kw), f"hand {g} {scoring} {mirror}", bsw.matesw_last_stats(eng))
     eng.close()
 
 
@@ -632,7 +602,7 @@ def test_gpu_pipeline_set_host_arrays():
     eng = bsw.Engine()
     bsw.set_reference(eng, p.T)
     got = bsw.matesw(eng, p.pes, a["reads"], a["off"], a["lens"], p.regs, p.info, p.first, bsw.matesw_opt(l_pac=p.l_pac))
-    _same(p.want, got, "pipeline set", bsw.matesw_last_stats(eng))
+    same_msw(p.want, got, "pipeline set", bsw.matesw_last_stats(eng))
     eng.close()
 
 
@@ -644,48 +614,25 @@ def test_gpu_pipeline_set_device_to_device():
     a = p.arr
     eng = bsw.Engine()
     bsw.set_reference(eng, p.T)
-    d = {k: hiprt.DeviceBuffer.from_array(np.ascontiguousarray(a[k])) for k in ("reads", "off", "lens", "seeds", "sr", "sc")}
-    n, nr = len(a["seeds"]), len(a["lens"])
-    d_regs, d_ext = hiprt.DeviceBuffer(n * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(n * 4)
-    bsw.chain2aln_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d["seeds"].ptr, d["sr"].ptr,
-                           d["sc"].ptr, n, d_regs.ptr, d_ext.ptr, p.eopt)
-    d_sreg, d_srd = hiprt.DeviceBuffer(n * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(n * 4)
-    d_info, d_first = hiprt.DeviceBuffer(n * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((nr + 1) * 4)
-    k = bsw.regs_select_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d["seeds"].ptr, d["sr"].ptr,
-                                 d["sc"].ptr, d_regs.ptr, d_ext.ptr, n, d_sreg.ptr, d_srd.ptr, d_info.ptr, d_first.ptr,
-                                 n, bsw.sel_opt(l_pac=p.l_pac))
+    b = ResidentBatch(eng, a["reads"], a["off"], a["lens"])
+    b.put(seeds=a["seeds"], sr=a["sr"], sc=a["sc"])
+    b.chain2aln(p.eopt)
+    k = b.select(bsw.sel_opt(l_pac=p.l_pac))
     assert k == len(p.regs)
     o = bsw.pe_opt(l_pac=p.l_pac)
-    pes = bsw.pe_stat_resident(eng, d_sreg.ptr, d_info.ptr, d_first.ptr, nr, k, o)
-    _same_pes(p.pes, pes, "device to device")
+    pes = b.pe_stat(o)
+    same_pes(p.pes, pes, "device to device")
     cap = len(p.mregs)
-    d_oreg, d_ord = hiprt.DeviceBuffer(cap * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(cap * 4)
-    d_oinfo, d_ofirst = hiprt.DeviceBuffer(cap * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((nr + 1) * 4)
-    m = bsw.matesw_resident(eng, pes, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d_sreg.ptr, d_info.ptr,
-                            d_first.ptr, k, d_oreg.ptr, d_ord.ptr, d_oinfo.ptr, d_ofirst.ptr, cap,
-                            bsw.matesw_opt(l_pac=p.l_pac))
+    m = b.matesw(pes, bsw.matesw_opt(l_pac=p.l_pac), cap=cap)
     assert m == cap
-    got = (d_oreg.download(np.zeros(cap, dtype=bsw.ALNREG_DTYPE)), d_ord.download(np.zeros(cap, np.int32)),
-           d_oinfo.download(np.zeros(cap, dtype=bsw.SELINFO_DTYPE)), d_ofirst.download(np.zeros(nr + 1, np.int32)))
-    _same(p.want, got, "device to device", bsw.matesw_last_stats(eng))
-    d_pairs = hiprt.DeviceBuffer((nr // 2) * bsw.PAIR_DTYPE.itemsize)
-    bsw.pe_pair_resident(eng, pes, d_oreg.ptr, d_oinfo.ptr, d_ofirst.ptr, nr, m, d_pairs.ptr, o)
-    gotp = (d_oreg.download(np.zeros(cap, dtype=bsw.ALNREG_DTYPE)), d_oinfo.download(np.zeros(cap, dtype=bsw.SELINFO_DTYPE)),
-            d_pairs.download(np.zeros(nr // 2, dtype=bsw.PAIR_DTYPE)))
-    _same_pair(p.paired, gotp, "device to device, paired", bsw.pe_last_stats(eng))
-    cs, ms = 16, 64
-    d_aln = hiprt.DeviceBuffer(m * bsw.ALN_DTYPE.itemsize)
-    d_cig, d_md = hiprt.DeviceBuffer(m * cs * 4), hiprt.DeviceBuffer(m * ms)
-    hiprt.check(hiprt.rt().hipMemset(ctypes.c_void_p(d_cig.ptr), 0, m * cs * 4))
-    hiprt.check(hiprt.rt().hipMemset(ctypes.c_void_p(d_md.ptr), 0, m * ms))
-    bsw.reg2aln_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d_oreg.ptr, d_ord.ptr, m, d_aln.ptr,
-                         d_cig.ptr, cs, d_md.ptr, ms, p.eopt)
-    aln = (d_aln.download(np.zeros(m, dtype=bsw.ALN_DTYPE)), d_cig.download(np.zeros((m, cs), dtype=np.uint32)),
-           d_md.download(np.zeros((m, ms), dtype=np.uint8)))
+    same_msw(p.want, fetch(b, *b.lists[0]), "device to device", bsw.matesw_last_stats(eng))
+    b.pe_pair(pes, o)
+    same_pair(p.paired, got_pair(b), "device to device, paired", bsw.pe_last_stats(eng))
+    b.reg2aln(p.eopt)
+    aln = got_aln(b)
     sel = np.zeros(m, dtype=bsw.ALNREG_DTYPE)
     for f in sp.ALNREG_FIELDS:
         sel[f] = p.paired[0][f]
-    from test_reg2aln import _same as same_aln
     same_aln(rp.reg2aln(p.T, p.l_pac, a["reads"], a["off"], a["lens"], sel, p.mread, p.mat, p.gaps, p.eopt.w), aln,
              "alignments of the rescued regions")
     eng.close()
@@ -702,7 +649,7 @@ def test_gpu_batch_sizes():
         k, m = p.first[2 * npairs], wf[2 * npairs]
         got = bsw.matesw(eng, p.pes, a["reads"][:npairs * 300], a["off"][:2 * npairs], a["lens"][:2 * npairs],
                          p.regs[:k], p.info[:k], p.first[:2 * npairs + 1], bsw.matesw_opt(l_pac=p.l_pac))
-        _same((wr[:m], wd[:m], wi[:m], wf[:2 * npairs + 1], tr), got, f"{npairs} pairs")
+        same_msw((wr[:m], wd[:m], wi[:m], wf[:2 * npairs + 1], tr), got, f"{npairs} pairs")
         assert bsw.matesw_last_stats(eng).n_pairs == npairs
     eng.close()
 
@@ -714,7 +661,7 @@ def test_gpu_list_lengths():
     assert tr.rounds >= 40 and tr.cnt["jobs"] > 400 and tr.cnt["pushed"] >= 10 and tr.cnt["drop_p"] + tr.cnt["drop_q"] >= 10
     eng = bsw.Engine()
     bsw.set_reference(eng, T)
-    _same(want, _gpu(eng, b, pes), "list lengths", bsw.matesw_last_stats(eng))
+    same_msw(want, _gpu(eng, b, pes), "list lengths", bsw.matesw_last_stats(eng))
     eng.close()
 
 
@@ -751,7 +698,7 @@ def test_gpu_errors_and_recovery():
     with pytest.raises(bsw.BswError, match="-34") as ei:
         bsw.matesw(eng, pes, reads, off, lens, regs, info, first, o, out_cap=need - 1)
     assert ei.value.needed == need and np.array_equal(ei.value.first, want[3])
-    _same(want, bsw.matesw(eng, pes, reads, off, lens, regs, info, first, o, out_cap=need), "exact capacity",
+    same_msw(want, bsw.matesw(eng, pes, reads, off, lens, regs, info, first, o, out_cap=need), "exact capacity",
           bsw.matesw_last_stats(eng))
     for v in (-1, 2 * L):
         r2 = regs.copy()
@@ -785,5 +732,5 @@ def test_gpu_errors_and_recovery():
         bsw.matesw(eng, _pes(FF=(1, 36000, 500.0, 50.0)), reads[:200], off[:2], lens[:2], r1, i1,
                    np.array([0, 1, 1], np.int32), bsw.matesw_opt(l_pac=40000))
     bsw.set_reference(eng, T)
-    _same(want, bsw.matesw(eng, pes, reads, off, lens, regs, info, first, o), "after the errors", bsw.matesw_last_stats(eng))
+    same_msw(want, bsw.matesw(eng, pes, reads, off, lens, regs, info, first, o), "after the errors", bsw.matesw_last_stats(eng))
     eng.close()

@@ -20,6 +20,7 @@ import hiprt
 import memchain_py
 import oracle
 from conftest import ROOT
+from resident import ResidentBatch
 from test_fmi import repetitive_ref, sample_reads
 
 
@@ -157,23 +158,18 @@ def test_c1_gpu_seeding_chaining_extension_equal_oracle(c1):
     ref, reads, off, lens, starts = c1
     f, mems, cnt, wseeds, wsr, wsc = _oracle_front(ref, reads, off, lens)
     fmi = bsw.Fmi(ref)
-    d_reads = hiprt.DeviceBuffer.from_array(reads)
-    (seeds, sr, sc), (d_seeds, d_sr, d_sc), (d_off, d_len) = bsw.seed_and_chain(fmi, d_reads, off, lens, cap=64)
+    eng = bsw.Engine()
+    b = ResidentBatch(eng, reads, off, lens)
+    seeds, sr, sc = b.seed_and_chain(fmi, cap=64)
     assert np.array_equal(sr, wsr) and np.array_equal(sc, wsc)
     for fld in ("rbeg", "qbeg", "len"):
         assert np.array_equal(seeds[fld], wseeds[fld]), fld
     T = _two_strand(ref)
     opt = bsw.ext_opt(l_pac=len(ref))
     want, wext = oracle.chain2aln(oracle.make_params(), opt, T, reads, off, lens, wseeds, wsr, wsc)
-    eng = bsw.Engine()
     bsw.set_reference(eng, T)
-    ns = len(seeds)
-    d_out = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize)
-    d_ext = hiprt.DeviceBuffer(ns * 4)
-    bsw.chain2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, len(lens), d_seeds.ptr, d_sr.ptr, d_sc.ptr, ns,
-                           d_out.ptr, d_ext.ptr, opt)
-    got = d_out.download(np.zeros(ns, dtype=bsw.ALNREG_DTYPE))
-    gext = d_ext.download(np.zeros(ns, dtype=np.int32))
+    b.chain2aln(opt)
+    got, gext = b.get("regs"), b.get("ext")
     assert np.array_equal(gext, wext)
     for fld in bsw.ALNREG_DTYPE.names:
         assert np.array_equal(got[fld], want[fld]), fld
@@ -226,18 +222,13 @@ def test_gpu_front_end_pe_reads_equal_oracle():
     opt = bsw.ext_opt(l_pac=len(ref))
     want, wext = oracle.chain2aln(oracle.make_params(), opt, T, reads, off, lens, wseeds, wsr, wsc)
     fmi = bsw.Fmi(ref)
-    d_reads = hiprt.DeviceBuffer.from_array(reads)
-    (seeds, sr, sc), (d_seeds, d_sr, d_sc), (d_off, d_len) = bsw.seed_and_chain(fmi, d_reads, off, lens, cap=256)
-    assert np.array_equal(sr, wsr) and np.array_equal(sc, wsc) and np.array_equal(seeds["rbeg"], wseeds["rbeg"])
     eng = bsw.Engine()
     bsw.set_reference(eng, T)
-    ns = len(seeds)
-    d_out = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize)
-    d_ext = hiprt.DeviceBuffer(ns * 4)
-    bsw.chain2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, len(lens), d_seeds.ptr, d_sr.ptr, d_sc.ptr, ns,
-                           d_out.ptr, d_ext.ptr, opt)
-    got = d_out.download(np.zeros(ns, dtype=bsw.ALNREG_DTYPE))
-    gext = d_ext.download(np.zeros(ns, dtype=np.int32))
+    b = ResidentBatch(eng, reads, off, lens)
+    seeds, sr, sc = b.seed_and_chain(fmi, cap=256)
+    assert np.array_equal(sr, wsr) and np.array_equal(sc, wsc) and np.array_equal(seeds["rbeg"], wseeds["rbeg"])
+    b.chain2aln(opt)
+    got, gext = b.get("regs"), b.get("ext")
     assert np.array_equal(gext, wext)
     for fld in bsw.ALNREG_DTYPE.names:
         assert np.array_equal(got[fld], want[fld]), fld

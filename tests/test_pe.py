@@ -11,7 +11,6 @@ is unpinned by the reference tree (it holds no source of these functions; bsw_pe
 
 import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -24,8 +23,10 @@ import pe_py as pp
 import reg2aln_py as rp
 import regsel_py as sp
 from conftest import ROOT
-from test_reg2aln import DEFAULT, SCORINGS
-from test_regsel import _mat_gaps, _select
+from resident import ResidentBatch
+from stagekit import (DEFAULT, SCORINGS, declared, engine_of, exported, got_aln, got_pair, mat_gaps, same_aln,
+                      same_pair, same_pes)
+from test_regsel import _select
 
 L = 100_000                                                  # l_pac of the hand-built pairs
 RL = 100                                                     # their read length
@@ -96,7 +97,7 @@ class PeBatch:
 
 
 def _run(batch, pes, scoring=DEFAULT, **optkw):
-    mat, gaps = _mat_gaps(scoring)
+    mat, gaps = mat_gaps(scoring)
     regs, info, first = batch.arrays(scoring[0])
     opt = pp.pe_opt(l_pac=L, b=scoring[1], **optkw)
     return pp.pe_pair(pes, regs, info, first, opt, mat, gaps)
@@ -383,7 +384,7 @@ class PeSet:
         self.sel = _select(T, self.arr, opt=self.sopt, csub=self.csub, frac_rep=self.frac_rep)
         self.regs, _, self.info, self.first, _ = self.sel
         self.opt = pp.pe_opt(l_pac=self.l_pac)
-        self.mat, self.gaps = _mat_gaps(DEFAULT)
+        self.mat, self.gaps = mat_gaps(DEFAULT)
         self.pes, self.tr_stat, self.isize = pp.pe_stat(self.regs, self.info, self.first, self.opt, 1)
         self.want = pp.pe_pair(self.pes, self.regs, self.info, self.first, self.opt, self.mat, self.gaps)
 
@@ -464,17 +465,9 @@ def test_combined_sets_reach_every_branch_with_margin():
 
 
 # ---------------------------------------------------------------- CPU: the header
-def _declared():
-    src = open(os.path.join(ROOT, "include", "bsw_pe.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return set(re.findall(r"\b(bsw_[a-z_0-9]+)\s*\(", src))
-
-
 def test_library_exports_the_pe_header():
-    assert _declared() == set(bsw.PE_SYMBOLS)
-    out = subprocess.run(["nm", "-D", "--defined-only", bsw.HIP_LIB], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (bsw_\w+)", out))
-    assert _declared() <= exported, _declared() - exported
+    assert declared("bsw_pe.h") == set(bsw.PE_SYMBOLS)
+    assert declared("bsw_pe.h") <= exported(), declared("bsw_pe.h") - exported()
     others = set(bsw.ABI_SYMBOLS) | set(bsw.ALN_SYMBOLS) | set(bsw.SEL_SYMBOLS)
     assert not set(bsw.PE_SYMBOLS) & others
     assert len(bsw.ABI_SYMBOLS) == 45 and bsw.hip_lib().bsw_abi_version() == 8
@@ -535,56 +528,23 @@ def test_defaults_and_invalid_arguments_need_no_device():
 
 
 # ---------------------------------------------------------------- GPU
-def _same_pes(want, got, tag):
-    for f in ("low", "high", "failed", "n"):
-        assert np.array_equal(want[f], got[f]), f"{tag}: {f} {got[f]}, want {want[f]}"
-    for f in ("avg", "std"):
-        for d in range(4):
-            assert abs(got[d][f] - want[d][f]) <= 1e-10 * abs(want[d][f]), f"{tag}: {f}[{d}] {got[d][f]!r}, want {want[d][f]!r}"
-
-
-def _same_pair(want, got, tag, st=None):
-    wr, wi, wp, tr = want
-    gr, gi, gp = got
-    assert len(wr) == len(gr) and len(wp) == len(gp), tag
-    for f in bsw.PAIR_DTYPE.names:
-        diff = wp[f] != gp[f]
-        bad = np.flatnonzero(diff.any(axis=1) if diff.ndim > 1 else diff)
-        assert len(bad) == 0, f"{tag}: pair.{f} differs at {len(bad)} pairs, first {bad[:5]}: want {wp[f][bad[:5]]} got {gp[f][bad[:5]]}"
-    for f in sp.ALNREG_FIELDS:
-        bad = np.flatnonzero(wr[f] != gr[f])
-        assert len(bad) == 0, f"{tag}: {f} differs at {len(bad)} regions, first {bad[:5]}: want {wr[f][bad[:5]]} got {gr[f][bad[:5]]}"
-    for f in bsw.SELINFO_DTYPE.names:
-        bad = np.flatnonzero(wi[f] != gi[f])
-        assert len(bad) == 0, f"{tag}: info.{f} differs at {len(bad)} regions, first {bad[:5]}: want {wi[f][bad[:5]]} got {gi[f][bad[:5]]}"
-    if st is not None:
-        for k, v in pp.stats_of(tr, len(wp)).items():
-            assert getattr(st, k) == v, f"{tag}: stats {k} = {getattr(st, k)}, want {v}"
-        assert st.kernel_ms > 0 or len(wp) == 0
-
-
-def _engine(scoring=DEFAULT):
-    a, b, od, ed, oi, ei = scoring
-    return bsw.Engine(bsw.default_params(a=a, b=b, o_del=od, e_del=ed, o_ins=oi, e_ins=ei))
-
-
 @pytest.mark.gpu
 def test_gpu_statistics_match_the_restatement():
     eng = bsw.Engine()
     regs, info, first = stat_batch().arrays()
     want, tr, _ = pp.pe_stat(regs, info, first, pp.pe_opt(l_pac=L), 1)
-    _same_pes(want, bsw.pe_stat(eng, regs, info, first, bsw.pe_opt(l_pac=L)), "hand-built")
+    same_pes(want, bsw.pe_stat(eng, regs, info, first, bsw.pe_opt(l_pac=L)), "hand-built")
     st = bsw.pe_last_stats(eng)
     assert list(st.n_cand) == list(want["n"]) and st.n_pairs == len(first) // 2 and st.kernel_ms > 0
     p = pe_set()
-    _same_pes(p.pes, bsw.pe_stat(eng, p.regs, p.info, p.first, bsw.pe_opt(l_pac=p.l_pac)), "pipeline set")
-    d = [hiprt.DeviceBuffer.from_array(np.ascontiguousarray(a)) for a in
-         (p.regs.astype(bsw.ALNREG_DTYPE), p.info, p.first)]
-    got = bsw.pe_stat_resident(eng, d[0].ptr, d[1].ptr, d[2].ptr, len(p.first) - 1, len(p.regs), bsw.pe_opt(l_pac=p.l_pac))
-    _same_pes(p.pes, got, "pipeline set, resident")
+    same_pes(p.pes, bsw.pe_stat(eng, p.regs, p.info, p.first, bsw.pe_opt(l_pac=p.l_pac)), "pipeline set")
+    b = ResidentBatch(eng, p.arr["reads"], p.arr["off"], p.arr["lens"])
+    b.put(sreg=p.regs, sinfo=p.info, sfirst=p.first)
+    got = b.pe_stat(bsw.pe_opt(l_pac=p.l_pac))
+    same_pes(p.pes, got, "pipeline set, resident")
     for mi in (300, 520):                                   # a max_ins inside the data
         o = pp.pe_opt(l_pac=p.l_pac, max_ins=mi)
-        _same_pes(pp.pe_stat(p.regs, p.info, p.first, o, 1)[0],
+        same_pes(pp.pe_stat(p.regs, p.info, p.first, o, 1)[0],
                   bsw.pe_stat(eng, p.regs, p.info, p.first, bsw.pe_opt(l_pac=p.l_pac, max_ins=mi)), f"max_ins {mi}")
     eng.close()
 
@@ -592,19 +552,19 @@ def test_gpu_statistics_match_the_restatement():
 @pytest.mark.gpu
 @pytest.mark.parametrize("scoring", SCORINGS)
 def test_gpu_hand_built_pairs(scoring):
-    eng = _engine(scoring)
+    eng = engine_of(scoring)
     for which in ("fr", "wide", "all"):
         b, P, want = hand_want(scoring, which)
         regs, info, first = b.arrays(scoring[0])
         got = bsw.pe_pair(eng, P, regs, info, first, bsw.pe_opt(l_pac=L, b=scoring[1]))
-        _same_pair(want, got, f"hand-built {scoring} {which}", bsw.pe_last_stats(eng))
+        same_pair(want, got, f"hand-built {scoring} {which}", bsw.pe_last_stats(eng))
     if scoring == DEFAULT:
         b = hand_batch()
         regs, info, first = b.arrays()
-        mat, gaps = _mat_gaps(DEFAULT)
+        mat, gaps = mat_gaps(DEFAULT)
         for kw in (dict(id0=1 << 40), dict(T=60, pen_unpaired=5), dict(mapQ_coef_len=0), dict(mask_level=0.9)):
             want = pp.pe_pair(PES_ALL, regs, info, first, pp.pe_opt(l_pac=L, **kw), mat, gaps)
-            _same_pair(want, bsw.pe_pair(eng, PES_ALL, regs, info, first, bsw.pe_opt(l_pac=L, **kw)), f"hand-built {kw}",
+            same_pair(want, bsw.pe_pair(eng, PES_ALL, regs, info, first, bsw.pe_opt(l_pac=L, **kw)), f"hand-built {kw}",
                        bsw.pe_last_stats(eng))
     eng.close()
 
@@ -614,10 +574,10 @@ def test_gpu_pipeline_set_host_arrays_and_end_to_end():
     p = pe_set()
     eng = bsw.Engine()
     o = bsw.pe_opt(l_pac=p.l_pac)
-    _same_pair(p.want, bsw.pe_pair(eng, p.pes, p.regs, p.info, p.first, o), "pipeline set", bsw.pe_last_stats(eng))
+    same_pair(p.want, bsw.pe_pair(eng, p.pes, p.regs, p.info, p.first, o), "pipeline set", bsw.pe_last_stats(eng))
     pes = bsw.pe_stat(eng, p.regs, p.info, p.first, o)      # the GPU's statistics into the GPU's pairing
     want = pp.pe_pair(pes, p.regs, p.info, p.first, p.opt, p.mat, p.gaps)
-    _same_pair(want, bsw.pe_pair(eng, pes, p.regs, p.info, p.first, o), "end to end", bsw.pe_last_stats(eng))
+    same_pair(want, bsw.pe_pair(eng, pes, p.regs, p.info, p.first, o), "end to end", bsw.pe_last_stats(eng))
     eng.close()
 
 
@@ -629,41 +589,23 @@ def test_gpu_pipeline_set_device_to_device():
     a = p.arr
     eng = bsw.Engine()
     bsw.set_reference(eng, p.T)
-    d = {k: hiprt.DeviceBuffer.from_array(np.ascontiguousarray(a[k])) for k in ("reads", "off", "lens", "seeds", "sr", "sc")}
-    d_csub, d_fr = hiprt.DeviceBuffer.from_array(p.csub), hiprt.DeviceBuffer.from_array(p.frac_rep)
-    n, nr = len(a["seeds"]), len(a["lens"])
-    d_regs, d_ext = hiprt.DeviceBuffer(n * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(n * 4)
-    bsw.chain2aln_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d["seeds"].ptr, d["sr"].ptr,
-                           d["sc"].ptr, n, d_regs.ptr, d_ext.ptr, p.eopt)
-    d_sreg, d_srd = hiprt.DeviceBuffer(n * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(n * 4)
-    d_info, d_first = hiprt.DeviceBuffer(n * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((nr + 1) * 4)
-    k = bsw.regs_select_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d["seeds"].ptr, d["sr"].ptr,
-                                 d["sc"].ptr, d_regs.ptr, d_ext.ptr, n, d_sreg.ptr, d_srd.ptr, d_info.ptr, d_first.ptr,
-                                 n, bsw.sel_opt(l_pac=p.l_pac), d_csub=d_csub.ptr, d_frac_rep=d_fr.ptr)
+    b = ResidentBatch(eng, a["reads"], a["off"], a["lens"])
+    b.put(seeds=a["seeds"], sr=a["sr"], sc=a["sc"])
+    b.chain2aln(p.eopt)
+    k = b.select(bsw.sel_opt(l_pac=p.l_pac), csub=p.csub, frac_rep=p.frac_rep)
     assert k == len(p.regs)
     o = bsw.pe_opt(l_pac=p.l_pac)
-    pes = bsw.pe_stat_resident(eng, d_sreg.ptr, d_info.ptr, d_first.ptr, nr, k, o)
-    _same_pes(p.pes, pes, "device to device")
-    d_pairs = hiprt.DeviceBuffer((nr // 2) * bsw.PAIR_DTYPE.itemsize)
-    bsw.pe_pair_resident(eng, pes, d_sreg.ptr, d_info.ptr, d_first.ptr, nr, k, d_pairs.ptr, o)
+    pes = b.pe_stat(o)
+    same_pes(p.pes, pes, "device to device")
+    b.pe_pair(pes, o)
     st = bsw.pe_last_stats(eng)
-    got = (d_sreg.download(np.zeros(n, dtype=bsw.ALNREG_DTYPE))[:k], d_info.download(np.zeros(n, dtype=bsw.SELINFO_DTYPE))[:k],
-           d_pairs.download(np.zeros(nr // 2, dtype=bsw.PAIR_DTYPE)))
-    _same_pair(p.want, got, "device to device", st)
-    assert np.array_equal(d_srd.download(np.zeros(n, np.int32))[:k], p.sel[1])      # d_sel_read stays valid
-    cs, ms = 16, 64
-    d_aln = hiprt.DeviceBuffer(k * bsw.ALN_DTYPE.itemsize)
-    d_cig, d_md = hiprt.DeviceBuffer(k * cs * 4), hiprt.DeviceBuffer(k * ms)
-    hiprt.check(hiprt.rt().hipMemset(ctypes.c_void_p(d_cig.ptr), 0, k * cs * 4))
-    hiprt.check(hiprt.rt().hipMemset(ctypes.c_void_p(d_md.ptr), 0, k * ms))
-    bsw.reg2aln_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d_sreg.ptr, d_srd.ptr, k, d_aln.ptr,
-                         d_cig.ptr, cs, d_md.ptr, ms, p.eopt)
-    aln = (d_aln.download(np.zeros(k, dtype=bsw.ALN_DTYPE)), d_cig.download(np.zeros((k, cs), dtype=np.uint32)),
-           d_md.download(np.zeros((k, ms), dtype=np.uint8)))
+    same_pair(p.want, got_pair(b), "device to device", st)
+    assert np.array_equal(b.get("sread"), p.sel[1])          # d_sel_read stays valid
+    b.reg2aln(p.eopt)
+    aln = got_aln(b)
     sel = np.zeros(k, dtype=bsw.ALNREG_DTYPE)
     for f in sp.ALNREG_FIELDS:
         sel[f] = p.want[0][f]
-    from test_reg2aln import _same as same_aln
     same_aln(rp.reg2aln(p.T, p.l_pac, a["reads"], a["off"], a["lens"], sel, p.sel[1], p.mat, p.gaps, p.eopt.w), aln,
              "alignments of the paired regions")
     eng.close()
@@ -679,10 +621,10 @@ def test_gpu_batch_sizes():
         k = p.first[2 * npairs]
         f = p.first[:2 * npairs + 1]
         got = bsw.pe_pair(eng, p.pes, p.regs[:k], p.info[:k], f, o)
-        _same_pair((wr[:k], wi[:k], wp[:npairs], tr), got, f"{npairs} pairs")
+        same_pair((wr[:k], wi[:k], wp[:npairs], tr), got, f"{npairs} pairs")
         assert bsw.pe_last_stats(eng).n_pairs == npairs
         want = pp.pe_stat(p.regs[:k], p.info[:k], f, p.opt, 1)[0]
-        _same_pes(want, bsw.pe_stat(eng, p.regs[:k], p.info[:k], f, o), f"{npairs} pairs")
+        same_pes(want, bsw.pe_stat(eng, p.regs[:k], p.info[:k], f, o), f"{npairs} pairs")
     eng.close()
 
 
@@ -693,9 +635,9 @@ def test_gpu_list_lengths():
     assert c["n_u"] > 4000 and c["u_many"] > 20 and c["general_path"] > 30 and want[3].margin >= 1e-6, (c, want[3].margin)
     eng = bsw.Engine()
     regs, info, first = b.arrays()
-    _same_pair(want, bsw.pe_pair(eng, PES_ALL, regs, info, first, bsw.pe_opt(l_pac=L)), "list lengths", bsw.pe_last_stats(eng))
+    same_pair(want, bsw.pe_pair(eng, PES_ALL, regs, info, first, bsw.pe_opt(l_pac=L)), "list lengths", bsw.pe_last_stats(eng))
     sw = pp.pe_stat(regs, info, first, pp.pe_opt(l_pac=L), 1)[0]
-    _same_pes(sw, bsw.pe_stat(eng, regs, info, first, bsw.pe_opt(l_pac=L)), "list lengths")
+    same_pes(sw, bsw.pe_stat(eng, regs, info, first, bsw.pe_opt(l_pac=L)), "list lengths")
     eng.close()
 
 
@@ -744,7 +686,7 @@ def test_gpu_errors_and_recovery():
     d_first = hiprt.DeviceBuffer.from_array(first)
     with pytest.raises(bsw.BswError, match="-34"):            # offsets past n_regs
         bsw.pe_pair_resident(eng, P, d[0].ptr, d[1].ptr, d_first.ptr, len(first) - 1, len(regs) - 1, d_pairs.ptr, o)
-    _same_pair(want, bsw.pe_pair(eng, P, regs, info, first, o), "after the errors", bsw.pe_last_stats(eng))
+    same_pair(want, bsw.pe_pair(eng, P, regs, info, first, o), "after the errors", bsw.pe_last_stats(eng))
     eng.close()
     eng = bsw.Engine()                                        # fresh slots: the first growth is this call's
     try:
@@ -756,5 +698,5 @@ def test_gpu_errors_and_recovery():
             bsw.pe_stat(eng, regs, info, first, o)
     finally:
         eng.set_option("test_fail_alloc", 0)
-    _same_pair(want, bsw.pe_pair(eng, P, regs, info, first, o), "after a failed growth", bsw.pe_last_stats(eng))
+    same_pair(want, bsw.pe_pair(eng, P, regs, info, first, o), "after a failed growth", bsw.pe_last_stats(eng))
     eng.close()

@@ -14,22 +14,21 @@ functions; bsw_rec.h restates them).
 
 import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import bsw
-import hiprt
 import pe_py as pp
 import rec_py as rq
 import reg2aln_py as rp
 import regsel_py as sp
 from conftest import ROOT
+from resident import ResidentBatch
+from stagekit import (DEFAULT, RECORDS, SCORINGS, declared, engine_of, exported, fetch, got_text, mat_gaps, revcomp,
+                      same_records, same_text)
 from test_matesw import L, REF, RL, T, T_MIRROR, MsBatch, ms_set, reg, rnd
-from test_reg2aln import DEFAULT, SCORINGS, revcomp
-from test_regsel import _mat_gaps
 
 RNAME = "chrT"
 LET = "ACGTN"
@@ -63,7 +62,7 @@ class Case:
 
     def run(self, scoring=DEFAULT, mirror=False, cigar_stride=16, md_stride=64, **kw):
         b = self.batch.mirrored() if mirror else self.batch
-        mat, gaps = _mat_gaps(scoring)
+        mat, gaps = mat_gaps(scoring)
         a = scoring[0]
         reads, off, lens, regs, info, first = b.arrays(a)
         info["mapq"] = [g.get("mapq", 0) for e in b.ends for g in e]
@@ -394,7 +393,7 @@ class ExtSet:
         self.sopt = sp.sel_opt(l_pac=self.l_pac)
         self.regs, _, self.info, self.first, _ = _select(Tt, self.arr, opt=self.sopt)
         self.opt = pp.pe_opt(l_pac=self.l_pac)
-        self.mat, self.gaps = _mat_gaps(DEFAULT)
+        self.mat, self.gaps = mat_gaps(DEFAULT)
         self.pes, _, _ = pp.pe_stat(self.regs, self.info, self.first, self.opt, 1)
         self.mregs, self.mread, self.minfo, self.mfirst, self.tr = mp.mate_rescue(
             self.pes, Tt, reads, off, lens, self.regs, self.info, self.first, mp.matesw_opt(l_pac=self.l_pac), self.mat,
@@ -461,17 +460,9 @@ def test_recomputed_secondary_all_is_the_carried_one():
 
 
 # ---------------------------------------------------------------- CPU: the header
-def _declared():
-    src = open(os.path.join(ROOT, "include", "bsw_rec.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return set(re.findall(r"\b(bsw_[a-z_0-9]+)\s*\(", src))
-
-
 def test_library_exports_the_rec_header():
-    assert _declared() == set(bsw.REC_SYMBOLS)
-    out = subprocess.run(["nm", "-D", "--defined-only", bsw.HIP_LIB], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (bsw_\w+)", out))
-    assert _declared() <= exported, _declared() - exported
+    assert declared("bsw_rec.h") == set(bsw.REC_SYMBOLS)
+    assert declared("bsw_rec.h") <= exported(), declared("bsw_rec.h") - exported()
     others = (set(bsw.ABI_SYMBOLS) | set(bsw.ALN_SYMBOLS) | set(bsw.SEL_SYMBOLS) | set(bsw.PE_SYMBOLS) |
               set(bsw.MATESW_SYMBOLS))
     assert not set(bsw.REC_SYMBOLS) & others
@@ -546,41 +537,8 @@ def test_defaults_and_invalid_arguments_need_no_device():
 
 
 # ---------------------------------------------------------------- GPU
-def _engine(scoring=DEFAULT):
-    a, b, od, ed, oi, ei = scoring
-    return bsw.Engine(bsw.default_params(a=a, b=b, o_del=od, e_del=ed, o_ins=oi, e_ins=ei))
-
-
 def _bopt(o):
     return bsw.rec_opt(**o)
-
-
-def _same_records(w, got, tag, st=None):
-    recs, first, aln, aln_reg, cig, md = got
-    assert np.array_equal(w.rec_first, first), f"{tag}: rec_first"
-    assert len(recs) == len(w.recs) and len(aln) == len(w.aln), f"{tag}: counts {len(recs)} {len(aln)}, want {len(w.recs)} {len(w.aln)}"
-    for f in rq.REC_DTYPE.names:
-        bad = np.flatnonzero(w.recs[f] != recs[f])
-        assert len(bad) == 0, f"{tag}: rec.{f} differs at {len(bad)} records, first {bad[:5]}: want {w.recs[f][bad[:5]]} got {recs[f][bad[:5]]}"
-    assert np.array_equal(w.aln_reg, aln_reg), f"{tag}: aln_reg"
-    for f in rp.ALN_DTYPE.names:
-        bad = np.flatnonzero(w.aln[f] != aln[f])
-        assert len(bad) == 0, f"{tag}: aln.{f} differs at {len(bad)} alignments, first {bad[:5]}: want {w.aln[f][bad[:5]]} got {aln[f][bad[:5]]}"
-    assert np.array_equal(w.cigar, cig), f"{tag}: cigar at {np.flatnonzero((w.cigar != cig).any(axis=1))[:5]}"
-    assert np.array_equal(w.md, md), f"{tag}: md at {np.flatnonzero((w.md != md).any(axis=1))[:5]}"
-    if st is not None:
-        for k, v in rq.stats_of(w).items():
-            assert getattr(st, k) == v, f"{tag}: stats {k} = {getattr(st, k)}, want {v}"
-
-
-def _same_text(text, toff, got, tag):
-    gt, go = got
-    assert np.array_equal(toff, go), f"{tag}: text_off differs at {np.flatnonzero(toff != go)[:5]}"
-    if gt != text:
-        k = next(i for i in range(min(len(gt), len(text))) if gt[i] != text[i])
-        r = int(np.searchsorted(toff, k, side="right")) - 1
-        raise AssertionError(f"{tag}: text differs at byte {k} (record {r}): want {text[toff[r]:toff[r + 1]]!r} got {gt[toff[r]:toff[r + 1]]!r}")
-    assert len(gt) == len(text), tag
 
 
 def _gpu_case(eng, c, w, tag, cigar_stride=16, md_stride=64):
@@ -589,10 +547,10 @@ def _gpu_case(eng, c, w, tag, cigar_stride=16, md_stride=64):
     o = _bopt(w.opt)
     got = bsw.records(eng, reads, off, lens, regs, info, first, c.pairs, o, cigar_stride, md_stride)
     st = bsw.rec_last_stats(eng)
-    _same_records(w, got, tag, st)
+    same_records(w, got, tag, st)
     assert (st.aln_ms > 0) == (len(w.aln) > 0) and st.helper_ms > 0, tag
     recs, rfirst, aln, aln_reg, cig, md = got
-    _same_text(w.text, w.text_off, bsw.sam_text(eng, recs, rfirst, aln, cig, md, reads, off, lens, c.names, c.quals, o,
+    same_text(w.text, w.text_off, bsw.sam_text(eng, recs, rfirst, aln, cig, md, reads, off, lens, c.names, c.quals, o,
                                                 c.pairs is not None), tag)
     st = bsw.rec_last_stats(eng)
     assert st.n_bytes == len(w.text) and st.text_ms > 0 and st.n_rec == len(w.recs), tag
@@ -601,7 +559,7 @@ def _gpu_case(eng, c, w, tag, cigar_stride=16, md_stride=64):
 @pytest.mark.gpu
 @pytest.mark.parametrize("scoring", SCORINGS)
 def test_gpu_hand_sets(scoring):
-    eng = _engine(scoring)
+    eng = engine_of(scoring)
     for mirror in (False, True):
         bsw.set_reference(eng, T_MIRROR if mirror else T)
         for name, mk in HAND.items():
@@ -613,7 +571,7 @@ def test_gpu_hand_sets(scoring):
 @pytest.mark.gpu
 @pytest.mark.parametrize("flags", [rq.SOFTCLIP, rq.NO_MULTI, rq.KEEP_SUPP_MAPQ, 7])
 def test_gpu_option_flags(flags):
-    eng = _engine()
+    eng = engine_of()
     bsw.set_reference(eng, T)
     for name in ("supp", "sa3", "pe"):
         c = HAND[name]()
@@ -632,41 +590,13 @@ def test_gpu_pipeline_set_host_arrays():
     o = _bopt(s.opt)
     got = bsw.records(eng, a["reads"], a["off"], a["lens"], s.regs, s.info, p.mfirst, s.pairs, o)
     st = bsw.rec_last_stats(eng)
-    _same_records(s.res, got, "pipeline set", st)
+    same_records(s.res, got, "pipeline set", st)
     # only the needed regions are aligned
     assert st.n_aln == rq.stats_of(s.res)["n_aln"] < len(s.regs)
     recs, rfirst, aln, aln_reg, cig, md = got
-    _same_text(s.text, s.text_off, bsw.sam_text(eng, recs, rfirst, aln, cig, md, a["reads"], a["off"], a["lens"], s.names,
+    same_text(s.text, s.text_off, bsw.sam_text(eng, recs, rfirst, aln, cig, md, a["reads"], a["off"], a["lens"], s.names,
                                                 s.quals, o, True), "pipeline set")
     eng.close()
-
-
-def _dl(buf, n, dtype, shape=None):
-    return buf.download(np.zeros(n if shape is None else shape, dtype=dtype))
-
-
-def _resident_records_and_text(eng, s, d, d_regs, d_info, d_first, d_pairs, nr, n_regs, opt, names, quals, paired):
-    """bsw_records_resident -> bsw_sam_text_resident on device arrays; -> (records tuple, (text, text_off))"""
-    rc, ac, cs, ms = nr + n_regs, max(n_regs, 1), 16, 64
-    d_recs, d_rfirst = hiprt.DeviceBuffer(rc * 88), hiprt.DeviceBuffer((nr + 1) * 4)
-    d_aln, d_areg = hiprt.DeviceBuffer(ac * 40), hiprt.DeviceBuffer(ac * 4)
-    d_cig, d_md = hiprt.DeviceBuffer(ac * cs * 4), hiprt.DeviceBuffer(ac * ms)
-    hiprt.check(hiprt.rt().hipMemset(ctypes.c_void_p(d_cig.ptr), 0, ac * cs * 4))
-    hiprt.check(hiprt.rt().hipMemset(ctypes.c_void_p(d_md.ptr), 0, ac * ms))
-    n_rec, n_aln = bsw.records_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d_regs, d_info, d_first,
-                                        n_regs, d_pairs, d_recs.ptr, d_rfirst.ptr, rc, d_aln.ptr, d_areg.ptr, d_cig.ptr,
-                                        cs, d_md.ptr, ms, ac, opt)
-    rec = (_dl(d_recs, rc, bsw.REC_DTYPE)[:n_rec], _dl(d_rfirst, nr + 1, np.int32), _dl(d_aln, ac, bsw.ALN_DTYPE)[:n_aln],
-           _dl(d_areg, ac, np.int32)[:n_aln], _dl(d_cig, 0, np.uint32, (ac, cs))[:n_aln], _dl(d_md, 0, np.uint8, (ac, ms))[:n_aln])
-    nm, nm_off = bsw._names_host(names)
-    d_nm, d_nmo = hiprt.DeviceBuffer.from_array(nm), hiprt.DeviceBuffer.from_array(nm_off)
-    d_q = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(quals))
-    cap = len(s.text) + 5
-    d_text, d_toff = hiprt.DeviceBuffer(cap), hiprt.DeviceBuffer((n_rec + 1) * 8)
-    nb = bsw.sam_text_resident(eng, d_recs.ptr, d_rfirst.ptr, n_rec, d_aln.ptr, d_cig.ptr, cs, d_md.ptr, ms, n_aln,
-                               d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d_nm.ptr, d_nmo.ptr, d_q.ptr, paired,
-                               d_text.ptr, d_toff.ptr, cap, opt)
-    return rec, (_dl(d_text, cap, np.uint8)[:nb].tobytes(), _dl(d_toff, n_rec + 1, np.int64))
 
 
 @pytest.mark.gpu
@@ -677,17 +607,14 @@ def test_gpu_pipeline_set_device_to_device():
     p, a = s.p, s.p.arr
     eng = bsw.Engine()
     bsw.set_reference(eng, p.T)
-    d = {k: hiprt.DeviceBuffer.from_array(np.ascontiguousarray(a[k])) for k in ("reads", "off", "lens")}
-    nr, m = len(a["lens"]), len(p.mregs)
-    d_regs = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(p.mregs, dtype=bsw.ALNREG_DTYPE))
-    d_info = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(p.minfo, dtype=bsw.SELINFO_DTYPE))
-    d_first = hiprt.DeviceBuffer.from_array(np.ascontiguousarray(p.mfirst, dtype=np.int32))
-    d_pairs = hiprt.DeviceBuffer((nr // 2) * bsw.PAIR_DTYPE.itemsize)
-    bsw.pe_pair_resident(eng, p.pes, d_regs.ptr, d_info.ptr, d_first.ptr, nr, m, d_pairs.ptr, bsw.pe_opt(l_pac=p.l_pac))
-    rec, txt = _resident_records_and_text(eng, s, d, d_regs.ptr, d_info.ptr, d_first.ptr, d_pairs.ptr, nr, m, _bopt(s.opt),
-                                          s.names, s.quals, True)
-    _same_records(s.res, rec, "device to device", bsw.rec_last_stats(eng))
-    _same_text(s.text, s.text_off, txt, "device to device")
+    b = ResidentBatch(eng, a["reads"], a["off"], a["lens"], s.quals)
+    b.put(mreg=p.mregs, minfo=p.minfo, mfirst=p.mfirst)
+    b.pe_pair(p.pes, bsw.pe_opt(l_pac=p.l_pac))
+    b.records(_bopt(s.opt))
+    rec = fetch(b, *RECORDS)
+    b.sam_text(_bopt(s.opt), s.names, True, cap=len(s.text) + 5)
+    same_records(s.res, rec, "device to device", bsw.rec_last_stats(eng))
+    same_text(s.text, s.text_off, got_text(b), "device to device")
     eng.close()
 
 
@@ -706,21 +633,16 @@ def test_gpu_single_end_from_regs_select_resident():
     assert c["rec_supp"] > 0 and c["supp_capped"] > 0 and c["xa_member"] > 0 and c["xa_dropped_many"] > 0 and c["rec_unmapped"] > 0
     eng = bsw.Engine()
     bsw.set_reference(eng, p.T)
-    d = {k: hiprt.DeviceBuffer.from_array(np.ascontiguousarray(a[k])) for k in ("reads", "off", "lens", "seeds", "sr", "sc")}
-    n = len(a["seeds"])
-    d_regs, d_ext = hiprt.DeviceBuffer(n * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(n * 4)
-    bsw.chain2aln_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr_all, d["seeds"].ptr, d["sr"].ptr,
-                           d["sc"].ptr, n, d_regs.ptr, d_ext.ptr, p.eopt)
-    d_sreg, d_srd = hiprt.DeviceBuffer(n * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(n * 4)
-    d_info, d_first = hiprt.DeviceBuffer(n * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((nr_all + 1) * 4)
-    k = bsw.regs_select_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr_all, d["seeds"].ptr, d["sr"].ptr,
-                                 d["sc"].ptr, d_regs.ptr, d_ext.ptr, n, d_sreg.ptr, d_srd.ptr, d_info.ptr, d_first.ptr,
-                                 n, bsw.sel_opt(l_pac=p.l_pac))
+    b = ResidentBatch(eng, a["reads"], a["off"], a["lens"], quals)
+    b.put(seeds=a["seeds"], sr=a["sr"], sc=a["sc"])
+    b.chain2aln(p.eopt)
+    k = b.select(bsw.sel_opt(l_pac=p.l_pac))
     assert k == len(p.regs)
-    rec, txt = _resident_records_and_text(eng, s, d, d_sreg.ptr, d_info.ptr, d_first.ptr, 0, nr_all, k, _bopt(opt), names,
-                                          quals, False)
-    _same_records(s.res, rec, "single-end", bsw.rec_last_stats(eng))
-    _same_text(s.text, s.text_off, txt, "single-end")
+    b.records(_bopt(opt), paired=False)
+    rec = fetch(b, *RECORDS)
+    b.sam_text(_bopt(opt), names, False, cap=len(s.text) + 5)
+    same_records(s.res, rec, "single-end", bsw.rec_last_stats(eng))
+    same_text(s.text, s.text_off, got_text(b), "single-end")
     eng.close()
 
 
@@ -741,10 +663,10 @@ def test_gpu_batch_sizes():
         sub = rq.Result()
         sub.recs, sub.rec_first, sub.aln, sub.aln_reg = w.recs[:nrec], w.rec_first[:nr + 1], w.aln[:nal], w.aln_reg[:nal]
         sub.cigar, sub.md = w.cigar[:nal], w.md[:nal]
-        _same_records(sub, got, f"{npairs} pairs", bsw.rec_last_stats(eng))
+        same_records(sub, got, f"{npairs} pairs", bsw.rec_last_stats(eng))
         recs, rfirst, aln, aln_reg, cig, md = got
         nb = int(s.text_off[nrec])
-        _same_text(s.text[:nb], s.text_off[:nrec + 1],
+        same_text(s.text[:nb], s.text_off[:nrec + 1],
                    bsw.sam_text(eng, recs, rfirst, aln, cig, md, a["reads"][:nr * 150], a["off"][:nr], a["lens"][:nr],
                                 s.names[:npairs], s.quals[:nr * 150], o, True), f"{npairs} pairs")
     eng.close()
@@ -769,7 +691,7 @@ def case_lists(n, xa):
 
 @pytest.mark.gpu
 def test_gpu_list_lengths():
-    eng = _engine()
+    eng = engine_of()
     bsw.set_reference(eng, T)
     for n, xa in ((0, 0), (1, 0), (2, 1), (17, 5), (17, 6), (46, 5), (46, 6)):
         c = case_lists(n, xa)
@@ -783,7 +705,7 @@ def test_gpu_list_lengths():
 def test_gpu_read_and_name_lengths():
     """the copy loop's edges: reads of 1, 31, 32, 33 and 151 bases on both strands, mapped and not, with and
     without quals; names of 1 and 255 bytes"""
-    eng = _engine()
+    eng = engine_of()
     bsw.set_reference(eng, T)
     for quals in (True, False):
         b = MsBatch()
@@ -818,12 +740,12 @@ def test_gpu_errors_and_recovery():
             bsw.records(eng, reads, off, lens, regs, info, first, c.pairs, o, **kw)
         assert ei.value.needed == (nrec, naln) and np.array_equal(ei.value.rec_first, w.rec_first), kw
     got = bsw.records(eng, reads, off, lens, regs, info, first, c.pairs, o, rec_cap=nrec, aln_cap=naln)
-    _same_records(w, got, "exact capacities", bsw.rec_last_stats(eng))
+    same_records(w, got, "exact capacities", bsw.rec_last_stats(eng))
     recs, rfirst, aln, aln_reg, cig, md = got
     with pytest.raises(bsw.BswError, match="-34") as ei:
         bsw.sam_text(eng, recs, rfirst, aln, cig, md, reads, off, lens, c.names, None, o, True, text_cap=len(w.text) - 1)
     assert ei.value.needed == len(w.text) and np.array_equal(ei.value.text_off, w.text_off)
-    _same_text(w.text, w.text_off, bsw.sam_text(eng, recs, rfirst, aln, cig, md, reads, off, lens, c.names, None, o, True,
+    same_text(w.text, w.text_off, bsw.sam_text(eng, recs, rfirst, aln, cig, md, reads, off, lens, c.names, None, o, True,
                                                 text_cap=len(w.text)), "exact text capacity")
     long_names = [b"x" * 256] + c.names[1:]
     with pytest.raises(bsw.BswError, match="-34"):

@@ -18,21 +18,14 @@ import numpy as np
 import pytest
 
 import bsw
-import hiprt
 import oracle
 import ksw_global_py as kg
 import reg2aln_py as rp
 from conftest import ROOT
-from ksw_ext_ref import bwa_fill_scmat
+from resident import ResidentBatch
+from stagekit import DEFAULT, SCORINGS, declared, exported, got_aln, mat_gaps, revcomp, same_aln
 
-DEFAULT = (1, 4, 6, 1, 6, 1)
-SCORINGS = [DEFAULT, (1, 3, 5, 2, 3, 1), (2, 5, 0, 1, 1, 2)]
 LET = "ACGTN"
-
-
-def revcomp(codes):
-    c = np.asarray(codes, dtype=np.uint8)
-    return np.where(c < 4, 3 - c, c)[::-1].astype(np.uint8)
 
 
 def _reg(qb, qe, rb, re, truesc, w=100):
@@ -108,13 +101,8 @@ def hand():
     return Hand()
 
 
-def _mat_gaps(scoring):
-    a, b, od, ed, oi, ei = scoring
-    return [int(v) for v in bwa_fill_scmat(a, b)], (od, ed, oi, ei)
-
-
 def _one(hand, name, W=100, scoring=DEFAULT, dp=None, cigar_stride=16, md_stride=64):
-    mat, gaps = _mat_gaps(scoring)
+    mat, gaps = mat_gaps(scoring)
     read, reg = hand.cases[name]
     kw = {"dp": dp} if dp else {}
     f, cg, md, br = rp.reg2aln_one(hand.T, hand.l_pac, read, reg, mat, gaps, W, cigar_stride, md_stride, **kw)
@@ -177,7 +165,7 @@ def test_rejected_regions(hand):
         assert f == dict(pos=-1, is_rev=0, n_cigar=0, NM=-1, score=0, w=0, n_pass=1, md_len=0, flags=rp.REJECTED), name
         assert br == {"rejected"}
     with pytest.raises(ValueError):
-        rp.reg2aln_one(hand.T, hand.l_pac, hand.cases["exact"][0], _reg(0, 61, 500, 561, 60), *_mat_gaps(DEFAULT),
+        rp.reg2aln_one(hand.T, hand.l_pac, hand.cases["exact"][0], _reg(0, 61, 500, 561, 60), *mat_gaps(DEFAULT),
                        100, 16, 64)
 
 
@@ -199,7 +187,7 @@ def test_recipes_agree_under_the_band_matrix_dp(hand):
 
 
 def _hand_reference(hand, scoring, W, cigar_stride=16, md_stride=64):
-    mat, gaps = _mat_gaps(scoring)
+    mat, gaps = mat_gaps(scoring)
     b = hand.batch(mirrors=True)
     b[3]["truesc"] *= scoring[0]                 # (the recipes' truesc are in units of a = 1)
     return b, rp.reg2aln(hand.T, hand.l_pac, *b[:5], mat, gaps, W, cigar_stride, md_stride)
@@ -215,17 +203,9 @@ def test_hand_batch_reaches_every_branch(hand):
 
 
 # ---------------------------------------------------------------- CPU: the header
-def _declared():
-    src = open(os.path.join(ROOT, "include", "bsw_aln.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return set(re.findall(r"\b(bsw_[a-z_0-9]+)\s*\(", src))
-
-
 def test_library_exports_the_aln_header():
-    assert _declared() == set(bsw.ALN_SYMBOLS)
-    out = subprocess.run(["nm", "-D", "--defined-only", bsw.HIP_LIB], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (bsw_\w+)", out))
-    assert _declared() <= exported, _declared() - exported
+    assert declared("bsw_aln.h") == set(bsw.ALN_SYMBOLS)
+    assert declared("bsw_aln.h") <= exported(), declared("bsw_aln.h") - exported()
     assert not set(bsw.ALN_SYMBOLS) & set(bsw.ABI_SYMBOLS)
     assert bsw.hip_lib().bsw_abi_version() == 8
 
@@ -314,7 +294,7 @@ class Pipeline:
         self.sr = np.array(sr, dtype=np.int32)
         self.sc = np.zeros(len(sr), dtype=np.int32)
         self.opt = bsw.ext_opt(l_pac=ref_len)
-        self.mat, self.gaps = _mat_gaps(DEFAULT)
+        self.mat, self.gaps = mat_gaps(DEFAULT)
         self.regs, self.ext = oracle.chain2aln(oracle.make_params(), self.opt, T, self.reads, self.off, self.lens,
                                                self.seeds, self.sr, self.sc)
         pick = np.flatnonzero(self.ext)[::25]
@@ -362,26 +342,6 @@ def test_pipeline_set_holds_every_kind_of_region(pipe):
 
 
 # ---------------------------------------------------------------- GPU
-def _same(want, got, tag):
-    wa, wc, wm = want[:3]
-    ga, gc, gm = got
-    assert len(wa) == len(ga)
-    ovf = wa["n_cigar"] < 0
-    for f in bsw.ALN_DTYPE.names:
-        m = np.ones(len(wa), bool) if f in ("score", "w", "n_pass", "flags") else ~ovf
-        bad = np.flatnonzero((wa[f] != ga[f]) & m)
-        assert len(bad) == 0, f"{tag}: {f} differs at {len(bad)} regions, first {bad[:5]}: want {wa[f][bad[:5]]} got {ga[f][bad[:5]]}"
-    keep = np.arange(wc.shape[1])[None, :] < np.where(ovf, 0, wa["n_cigar"])[:, None]
-    bad = np.flatnonzero(((wc != gc) & keep).any(axis=1))
-    assert len(bad) == 0, f"{tag}: CIGAR differs at {len(bad)} regions, first {bad[:5]}: want {wc[bad[:1]]} got {gc[bad[:1]]}"
-    if wm is not None:
-        keep = np.arange(wm.shape[1])[None, :] < np.where(ovf, 0, np.maximum(wa["md_len"], 0))[:, None]
-        bad = np.flatnonzero(((wm != gm) & keep).any(axis=1))
-        assert len(bad) == 0, f"{tag}: MD differs at {len(bad)} regions, first {bad[:5]}: want {bytes(wm[bad[0]])} got {bytes(gm[bad[0]])}"
-    else:
-        assert gm is None
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("scoring", SCORINGS)
 def test_gpu_hand_built_regions(hand, scoring):
@@ -403,7 +363,7 @@ def test_gpu_hand_built_regions(hand, scoring):
     bsw.set_reference(eng, hand.T)
     for W, (bt, want) in refs.items():
         got = bsw.reg2aln(eng, *bt[:5], bsw.ext_opt(w=W, l_pac=hand.l_pac))
-        _same(want, got, f"hand-built {scoring} W={W}")
+        same_aln(want, got, f"hand-built {scoring} W={W}")
         st = bsw.aln_last_stats(eng)
         cnt = rp.branch_counts(want[3])
         assert (st.n_regs, st.n_rejected, st.n_gapfree) == (len(bt[3]), cnt["rejected"], cnt["gapfree"])
@@ -418,7 +378,7 @@ def test_gpu_pipeline_regions_host_arrays(pipe):
     eng = bsw.Engine()
     bsw.set_reference(eng, pipe.T)
     got = bsw.reg2aln(eng, pipe.reads, pipe.off, pipe.lens, pipe.all_regs, pipe.all_read, pipe.opt)
-    _same(pipe.want, got, "pipeline regions")
+    same_aln(pipe.want, got, "pipeline regions")
     st = bsw.aln_last_stats(eng)
     cnt = rp.branch_counts(pipe.want[3])
     assert (st.n_rejected, st.n_gapfree, st.n_dp[0]) == (cnt["rejected"], cnt["gapfree"], cnt["dp"])
@@ -432,25 +392,15 @@ def test_gpu_pipeline_device_to_device(pipe):
     p = pipe
     eng = bsw.Engine()
     bsw.set_reference(eng, p.T)
-    d = {k: hiprt.DeviceBuffer.from_array(v) for k, v in
-         dict(reads=p.reads, off=p.off, lens=p.lens, seeds=p.seeds, sr=p.sr, sc=p.sc).items()}
+    b = ResidentBatch(eng, p.reads, p.off, p.lens)
+    b.put(seeds=p.seeds, sr=p.sr, sc=p.sc)
     n = len(p.seeds)
-    d_regs = hiprt.DeviceBuffer(n * bsw.ALNREG_DTYPE.itemsize)
-    d_ext = hiprt.DeviceBuffer(n * 4)
-    bsw.chain2aln_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, len(p.lens), d["seeds"].ptr, d["sr"].ptr,
-                           d["sc"].ptr, n, d_regs.ptr, d_ext.ptr, p.opt)
-    cs, ms = 16, 64
-    d_aln = hiprt.DeviceBuffer(n * bsw.ALN_DTYPE.itemsize)
-    d_cig, d_md = hiprt.DeviceBuffer(n * cs * 4), hiprt.DeviceBuffer(n * ms)
-    hiprt.check(hiprt.rt().hipMemset(ctypes.c_void_p(d_cig.ptr), 0, n * cs * 4))
-    hiprt.check(hiprt.rt().hipMemset(ctypes.c_void_p(d_md.ptr), 0, n * ms))
-    bsw.reg2aln_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, len(p.lens), d_regs.ptr, d["sr"].ptr, n,
-                         d_aln.ptr, d_cig.ptr, cs, d_md.ptr, ms, p.opt)
-    got = (d_aln.download(np.zeros(n, dtype=bsw.ALN_DTYPE)), d_cig.download(np.zeros((n, cs), dtype=np.uint32)),
-           d_md.download(np.zeros((n, ms), dtype=np.uint8)))
-    regs = d_regs.download(np.zeros(n, dtype=bsw.ALNREG_DTYPE))
+    b.chain2aln(p.opt)
+    b.reg2aln(p.opt)
+    got = got_aln(b)
+    regs = b.get("regs")
     assert all(np.array_equal(regs[f], p.regs[f]) for f in bsw.ALNREG_DTYPE.names)
-    _same(p.subset(np.arange(n)), got, "device to device")
+    same_aln(p.subset(np.arange(n)), got, "device to device")
     eng.close()
 
 
@@ -469,7 +419,7 @@ def test_gpu_batch_sizes_and_uniform_batches(pipe):
     for tag, idx in kinds.items():
         assert len(idx) > 0 or tag == "empty"
         got = bsw.reg2aln(eng, p.reads, p.off, p.lens, p.all_regs[idx], p.all_read[idx], p.opt)
-        _same(p.subset(idx), got, tag)
+        same_aln(p.subset(idx), got, tag)
         st = bsw.aln_last_stats(eng)
         assert st.n_regs == len(idx)
         if tag == "gap-free":
@@ -497,14 +447,14 @@ def test_gpu_long_read_takes_the_wide_global_kernel():
     reads = np.concatenate([r for r, _ in items])
     off, lens = np.array([0, 250], np.int64), np.array([250, 250], np.int32)
     regs = np.array([g for _, g in items], dtype=bsw.ALNREG_DTYPE)
-    mat, gaps = _mat_gaps(DEFAULT)
+    mat, gaps = mat_gaps(DEFAULT)
     want = rp.reg2aln(T, l_pac, reads, off, lens, regs, [0, 1], mat, gaps, 100)
     assert rp.cigar_str(want[1][0, :want[0]["n_cigar"][0]]) == rp.cigar_str(want[1][1, :want[0]["n_cigar"][1]])
     assert "4I" in rp.cigar_str(want[1][0, :3]) and list(want[0]["w"]) == [66, 66] and list(want[0]["NM"]) == [16, 16]
     eng = bsw.Engine()
     bsw.set_reference(eng, T)
     got = bsw.reg2aln(eng, reads, off, lens, regs, [0, 1], bsw.ext_opt(l_pac=l_pac))
-    _same(want, got, "250 bp")
+    same_aln(want, got, "250 bp")
     assert bsw.global_last_stats(eng).n_wide == 2
     eng.close()
 
@@ -519,7 +469,7 @@ def test_gpu_overflow_flags(hand, cigar_stride, md_stride):
     eng = bsw.Engine()
     bsw.set_reference(eng, hand.T)
     got = bsw.reg2aln(eng, *bt[:5], bsw.ext_opt(l_pac=hand.l_pac), cigar_stride=cigar_stride, md_stride=md_stride)
-    _same(want, got, f"strides {cigar_stride}, {md_stride}")
+    same_aln(want, got, f"strides {cigar_stride}, {md_stride}")
     eng.close()
 
 
@@ -542,7 +492,7 @@ def test_gpu_errors(hand):
             bsw.reg2aln(eng, bt[0], bt[1], bt[2], regs, bt[4], opt)
     with pytest.raises(bsw.BswError, match="-34"):            # a read index outside the reads
         bsw.reg2aln(eng, bt[0], bt[1], bt[2], bt[3], np.array([0, 2], np.int32), opt)
-    mat, gaps = _mat_gaps(DEFAULT)
+    mat, gaps = mat_gaps(DEFAULT)
     want = rp.reg2aln(hand.T, hand.l_pac, *bt[:5], mat, gaps, 100)
     eng.close()
     eng = bsw.Engine()                                        # fresh slots: the first growth is this call's
@@ -553,5 +503,5 @@ def test_gpu_errors(hand):
             bsw.reg2aln(eng, *bt[:5], opt)
     finally:
         eng.set_option("test_fail_alloc", 0)
-    _same(want, bsw.reg2aln(eng, *bt[:5], opt), "after a failed growth")
+    same_aln(want, bsw.reg2aln(eng, *bt[:5], opt), "after a failed growth")
     eng.close()

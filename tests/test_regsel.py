@@ -12,27 +12,19 @@ source of these functions; bsw_sel.h restates them).
 
 import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import bsw
-import hiprt
 import oracle
 import reg2aln_py as rp
 import regsel_py as sp
 from conftest import ROOT
-from ksw_ext_ref import bwa_fill_scmat
-from test_reg2aln import DEFAULT, SCORINGS, revcomp
-
-REG_FIELDS = sp.ALNREG_FIELDS
-
-
-def _mat_gaps(scoring):
-    a, b, od, ed, oi, ei = scoring
-    return [int(v) for v in bwa_fill_scmat(a, b)], (od, ed, oi, ei)
+from resident import ResidentBatch
+from stagekit import (DEFAULT, REG_FIELDS, SCORINGS, declared, exported, fetch, got_aln, mat_gaps, revcomp, same_aln,
+                      same_sel)
 
 
 # ---------------------------------------------------------------- batches
@@ -131,7 +123,7 @@ def small_text(seed=4, n=9000):
 
 
 def _select(T, arr, scoring=DEFAULT, opt=None, **kw):
-    mat, gaps = _mat_gaps(scoring)
+    mat, gaps = mat_gaps(scoring)
     return sp.regs_select(T, arr["reads"], arr["off"], arr["lens"], arr["seeds"], arr["sr"], arr["sc"], arr["regs"],
                           arr["ext"], mat, gaps, opt or sp.sel_opt(l_pac=len(T) // 2, b=scoring[1]), **kw)
 
@@ -452,17 +444,9 @@ def test_combined_batches_reach_every_branch_with_margin():
 
 
 # ---------------------------------------------------------------- CPU: the header
-def _declared():
-    src = open(os.path.join(ROOT, "include", "bsw_sel.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return set(re.findall(r"\b(bsw_[a-z_0-9]+)\s*\(", src))
-
-
 def test_library_exports_the_sel_header():
-    assert _declared() == set(bsw.SEL_SYMBOLS)
-    out = subprocess.run(["nm", "-D", "--defined-only", bsw.HIP_LIB], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (bsw_\w+)", out))
-    assert _declared() <= exported, _declared() - exported
+    assert declared("bsw_sel.h") == set(bsw.SEL_SYMBOLS)
+    assert declared("bsw_sel.h") <= exported(), declared("bsw_sel.h") - exported()
     assert not set(bsw.SEL_SYMBOLS) & set(bsw.ABI_SYMBOLS) and not set(bsw.SEL_SYMBOLS) & set(bsw.ALN_SYMBOLS)
     import hashlib
     assert len(bsw.ABI_SYMBOLS) == 45 and bsw.hip_lib().bsw_abi_version() == 8
@@ -501,24 +485,6 @@ def test_defaults_and_invalid_arguments_need_no_device():
 
 
 # ---------------------------------------------------------------- GPU
-def _same(want, got, tag, st=None):
-    wr, wrd, wi, wf, tr = want
-    gr, grd, gi, gf = got
-    assert np.array_equal(wf, gf), f"{tag}: read offsets differ, first at read {np.flatnonzero(wf != gf)[:5]}"
-    assert len(wr) == len(gr), f"{tag}: n_sel {len(gr)}, want {len(wr)}"
-    assert np.array_equal(wrd, grd), f"{tag}: sel_read differs"
-    for f in REG_FIELDS:
-        bad = np.flatnonzero(wr[f] != gr[f])
-        assert len(bad) == 0, f"{tag}: {f} differs at {len(bad)} regions, first {bad[:5]}: want {wr[f][bad[:5]]} got {gr[f][bad[:5]]}"
-    for f in bsw.SELINFO_DTYPE.names:
-        bad = np.flatnonzero(wi[f] != gi[f])
-        assert len(bad) == 0, f"{tag}: {f} differs at {len(bad)} regions, first {bad[:5]}: want {wi[f][bad[:5]]} got {gi[f][bad[:5]]}"
-    if st is not None:
-        for k, v in sp.stats_of(tr).items():
-            assert getattr(st, k) == v, f"{tag}: stats {k} = {getattr(st, k)}, want {v}"
-        assert st.n_sel == len(wr)
-
-
 def _gpu_select(eng, arr, opt, scoring=DEFAULT, **kw):
     o = bsw.sel_opt(**{k: v for k, v in opt.items()})
     return bsw.regs_select(eng, arr["reads"], arr["off"], arr["lens"], arr["seeds"], arr["sr"], arr["sc"], arr["regs"],
@@ -535,12 +501,12 @@ def test_gpu_hand_built_reads(scoring):
         bsw.set_reference(eng, T)
         got = _gpu_select(eng, arr, opt)
         st = bsw.sel_last_stats(eng)
-        _same(want, got, f"hand-built {scoring} patch={patch}", st)
+        same_sel(want, got, f"hand-built {scoring} patch={patch}", st)
         assert st.n_reads == len(arr["lens"]) and (st.dp_ms > 0) == (st.rounds > 0) and st.helper_ms > 0
     if scoring == DEFAULT:
         for kw in (dict(mask_level_redun=1.0), dict(mapQ_coef_len=0), dict(id0=1 << 40), dict(max_chain_gap=100)):
             T, bt, arr, opt, want = hand_want(**kw)
-            _same(want, _gpu_select(eng, arr, opt), f"hand-built {kw}", bsw.sel_last_stats(eng))
+            same_sel(want, _gpu_select(eng, arr, opt), f"hand-built {kw}", bsw.sel_last_stats(eng))
     eng.close()
 
 
@@ -551,9 +517,9 @@ def test_gpu_pipeline_set_host_arrays(which):
     eng = bsw.Engine()
     bsw.set_reference(eng, p.T)
     got = _gpu_select(eng, p.full, p.opt, csub=p.csub, frac_rep=p.full_frac)
-    _same(p.want, got, which, bsw.sel_last_stats(eng))
+    same_sel(p.want, got, which, bsw.sel_last_stats(eng))
     got = _gpu_select(eng, p.plain, p.opt)
-    _same(p.want_plain, got, which + " plain", bsw.sel_last_stats(eng))
+    same_sel(p.want_plain, got, which + " plain", bsw.sel_last_stats(eng))
     assert bsw.sel_last_stats(eng).rounds == 0 and bsw.sel_last_stats(eng).dp_ms == 0
     eng.close()
 
@@ -566,36 +532,19 @@ def test_gpu_pipeline_set_device_to_device(which):
     a = p.plain
     eng = bsw.Engine()
     bsw.set_reference(eng, p.T)
-    d = {k: hiprt.DeviceBuffer.from_array(np.ascontiguousarray(a[k])) for k in ("reads", "off", "lens", "seeds", "sr", "sc")}
-    n, nr = len(a["seeds"]), len(a["lens"])
-    d_regs = hiprt.DeviceBuffer(n * bsw.ALNREG_DTYPE.itemsize)
-    d_ext = hiprt.DeviceBuffer(n * 4)
-    bsw.chain2aln_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d["seeds"].ptr, d["sr"].ptr,
-                           d["sc"].ptr, n, d_regs.ptr, d_ext.ptr, p.eopt)
-    d_sreg, d_srd = hiprt.DeviceBuffer(n * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(n * 4)
-    d_info, d_first = hiprt.DeviceBuffer(n * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((nr + 1) * 4)
-    k = bsw.regs_select_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d["seeds"].ptr, d["sr"].ptr,
-                                 d["sc"].ptr, d_regs.ptr, d_ext.ptr, n, d_sreg.ptr, d_srd.ptr, d_info.ptr, d_first.ptr,
-                                 n, bsw.sel_opt(l_pac=p.l_pac))
+    b = ResidentBatch(eng, a["reads"], a["off"], a["lens"])
+    b.put(seeds=a["seeds"], sr=a["sr"], sc=a["sc"])
+    b.chain2aln(p.eopt)
+    k = b.select(bsw.sel_opt(l_pac=p.l_pac))
     wr = p.want_plain[0]
     assert k == len(wr)
-    got = (d_sreg.download(np.zeros(n, dtype=bsw.ALNREG_DTYPE))[:k], d_srd.download(np.zeros(n, np.int32))[:k],
-           d_info.download(np.zeros(n, dtype=bsw.SELINFO_DTYPE))[:k], d_first.download(np.zeros(nr + 1, np.int32)))
-    _same(p.want_plain, got, which + " device to device", bsw.sel_last_stats(eng))
-    cs, ms = 16, 64
-    d_aln = hiprt.DeviceBuffer(k * bsw.ALN_DTYPE.itemsize)
-    d_cig, d_md = hiprt.DeviceBuffer(k * cs * 4), hiprt.DeviceBuffer(k * ms)
-    hiprt.check(hiprt.rt().hipMemset(ctypes.c_void_p(d_cig.ptr), 0, k * cs * 4))
-    hiprt.check(hiprt.rt().hipMemset(ctypes.c_void_p(d_md.ptr), 0, k * ms))
-    bsw.reg2aln_resident(eng, d["reads"].ptr, d["off"].ptr, d["lens"].ptr, nr, d_sreg.ptr, d_srd.ptr, k, d_aln.ptr,
-                         d_cig.ptr, cs, d_md.ptr, ms, p.eopt)
-    aln = (d_aln.download(np.zeros(k, dtype=bsw.ALN_DTYPE)), d_cig.download(np.zeros((k, cs), dtype=np.uint32)),
-           d_md.download(np.zeros((k, ms), dtype=np.uint8)))
-    mat, gaps = _mat_gaps(DEFAULT)
+    same_sel(p.want_plain, fetch(b, *b.lists[0]), which + " device to device", bsw.sel_last_stats(eng))
+    b.reg2aln(p.eopt)
+    aln = got_aln(b)
+    mat, gaps = mat_gaps(DEFAULT)
     sel = np.zeros(k, dtype=bsw.ALNREG_DTYPE)
     for f in REG_FIELDS:
         sel[f] = wr[f]
-    from test_reg2aln import _same as same_aln
     same_aln(rp.reg2aln(p.T, p.l_pac, a["reads"], a["off"], a["lens"], sel, p.want_plain[1], mat, gaps, p.eopt.w), aln,
              which + ": alignments of the survivors")
     eng.close()
@@ -618,7 +567,7 @@ def test_gpu_batch_sizes():
         sub, m = _first_reads(p.full, nr)
         got = _gpu_select(eng, sub, p.opt, csub=p.csub[m], frac_rep=p.full_frac[:nr])
         k = wf[nr]
-        _same((wr[:k], wrd[:k], wi[:k], wf[:nr + 1], tr), got, f"n_reads={nr}")
+        same_sel((wr[:k], wrd[:k], wi[:k], wf[:nr + 1], tr), got, f"n_reads={nr}")
         assert bsw.sel_last_stats(eng).n_reads == nr and bsw.sel_last_stats(eng).n_sel == k
     eng.close()
 
@@ -658,7 +607,7 @@ def test_gpu_regions_per_read():
         want = _select(T, arr, opt=opt)
         got = _gpu_select(eng, arr, opt)
         st = bsw.sel_last_stats(eng)
-        _same(want, got, tag, st)
+        same_sel(want, got, tag, st)
         if tag == "mixed":
             c = want[4].cnt
             assert c["drop_p"] > 10 and c["drop_q"] > 10 and c["patch_dp"] > 10 and c["patch_ok"] > 0 and c["secondary"] > 10, c
@@ -683,7 +632,7 @@ def test_gpu_errors_and_recovery():
     with pytest.raises(bsw.BswError, match="-34") as ei:
         _gpu_select(eng, arr, opt, sel_cap=need - 1)
     assert ei.value.needed == need
-    _same(want, _gpu_select(eng, arr, opt, sel_cap=need), "sel_cap exact")
+    same_sel(want, _gpu_select(eng, arr, opt, sel_cap=need), "sel_cap exact")
     for field, v in (("qe", 152), ("qb", -1), ("re", len(T) + 1), ("rb", -1)):
         bad = dict(arr, regs=arr["regs"].copy())
         bad["regs"][0][field] = v
@@ -706,5 +655,5 @@ def test_gpu_errors_and_recovery():
             _gpu_select(eng, arr, opt)
     finally:
         eng.set_option("test_fail_alloc", 0)
-    _same(want, _gpu_select(eng, arr, opt), "after a failed growth", bsw.sel_last_stats(eng))
+    same_sel(want, _gpu_select(eng, arr, opt), "after a failed growth", bsw.sel_last_stats(eng))
     eng.close()

@@ -32,8 +32,9 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, ROOT)
 import bsw  # noqa: E402
 import hiprt  # noqa: E402
+from resident import ResidentBatch  # noqa: E402
 from bench import pe_reads  # noqa: E402
-from reg2aln_bench import spread  # noqa: E402
+from reg2aln_bench import spread, timed  # noqa: E402
 
 STAGES = ("chain_s", "ext_s", "select_s", "stat_s", "stat_ms", "matesw_s", "matesw_ms", "pair_s", "pair_ms", "reg2aln_ms",
           "rec_s", "rec_aln_ms", "rec_helper_ms", "text_s", "text_ms")
@@ -91,11 +92,9 @@ def main():
     popt = bsw.pe_opt(l_pac=l_pac)
     mopt = bsw.matesw_opt(l_pac=l_pac)
     ropt = bsw.rec_opt(w=args.w, l_pac=l_pac, rname="chrS")
-    d_reads = hiprt.DeviceBuffer.from_array(reads)
-    d_quals = hiprt.DeviceBuffer.from_array((33 + (np.arange(len(reads)) * 7) % 41).astype(np.uint8))
-    nm, nm_off = bsw._names_host([b"frag%08d" % i for i in range(n // 2)])
-    d_nm, d_nmo = hiprt.DeviceBuffer.from_array(nm), hiprt.DeviceBuffer.from_array(nm_off)
-    d_off, d_len = hiprt.DeviceBuffer.from_array(off), hiprt.DeviceBuffer.from_array(lens)
+    b = ResidentBatch(eng, reads, off, lens, quals=(33 + (np.arange(len(reads)) * 7) % 41).astype(np.uint8))
+    names = [b"frag%08d" % i for i in range(n // 2)]
+    d_reads, d_off, d_len = (b.buf[x] for x in ("reads", "off", "lens"))
     icap = 256
     d_mems, d_cnt = hiprt.DeviceBuffer(n * icap * bsw.BWTINTV_DTYPE.itemsize), hiprt.DeviceBuffer(n * 4)
     bsw._check(fmi.collect_intv_device(d_reads.ptr, d_off.ptr, d_len.ptr, n, RL, d_mems.ptr, icap, d_cnt.ptr))
@@ -115,85 +114,55 @@ def main():
         assert rc_ in (0, -34), rc_
         need = max(need, ns_)
     S = need + 1024
-    d_seeds, d_sr, d_sc = hiprt.DeviceBuffer(S * bsw.SEED_DTYPE.itemsize), hiprt.DeviceBuffer(S * 4), hiprt.DeviceBuffer(S * 4)
-    d_regs, d_ext = hiprt.DeviceBuffer(S * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(S * 4)
-    d_sreg, d_srd = hiprt.DeviceBuffer(S * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(S * 4)
-    d_info, d_first = hiprt.DeviceBuffer(S * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((n + 1) * 4)
+    d_seeds, d_sr, d_sc = (b.alloc(x, S) for x in ("seeds", "sr", "sc"))
     cap = S + 8 * len(hit) + 1024                            # the rescue's output: the lists plus at most 4 per call
-    d_oreg, d_ord = hiprt.DeviceBuffer(cap * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(cap * 4)
-    d_oinfo, d_ofirst = hiprt.DeviceBuffer(cap * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((n + 1) * 4)
-    d_pairs = hiprt.DeviceBuffer((n // 2) * bsw.PAIR_DTYPE.itemsize)
-    cs, ms = 16, 64
-    rcap, acap = n + cap, cap
-    d_aln, d_cig, d_md = hiprt.DeviceBuffer(acap * 40), hiprt.DeviceBuffer(acap * cs * 4), hiprt.DeviceBuffer(acap * ms)
-    d_recs, d_rfirst, d_areg = hiprt.DeviceBuffer(rcap * 88), hiprt.DeviceBuffer((n + 1) * 4), hiprt.DeviceBuffer(acap * 4)
-    b_aln, b_cig, b_md = hiprt.DeviceBuffer(acap * 40), hiprt.DeviceBuffer(acap * cs * 4), hiprt.DeviceBuffer(acap * ms)
-    d_toff = hiprt.DeviceBuffer((rcap + 1) * 8)
     st = {}
 
     def chain():
         rc_, st["ns"] = fmi.mem_chain_device(d_len.ptr, n, d_mems.ptr, icap, d_cnt.ptr, d_seeds.ptr, d_sr.ptr, d_sc.ptr, S)
         bsw._check(rc_)
+        b.n["seeds"] = st["ns"]
 
     def extend():
-        bsw.chain2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr, st["ns"],
-                               d_regs.ptr, d_ext.ptr, opt)
+        b.chain2aln(opt)
 
     def select():
-        st["k"] = bsw.regs_select_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr,
-                                           d_regs.ptr, d_ext.ptr, st["ns"], d_sreg.ptr, d_srd.ptr, d_info.ptr, d_first.ptr,
-                                           S, sopt)
+        st["k"] = b.select(sopt)
 
     def stat():
-        st["pes"] = bsw.pe_stat_resident(eng, d_sreg.ptr, d_info.ptr, d_first.ptr, n, st["k"], popt)
+        st["pes"] = b.pe_stat(popt)
 
     def rescue():
-        st["m"] = bsw.matesw_resident(eng, st["pes"], d_reads.ptr, d_off.ptr, d_len.ptr, n, d_sreg.ptr, d_info.ptr,
-                                      d_first.ptr, st["k"], d_oreg.ptr, d_ord.ptr, d_oinfo.ptr, d_ofirst.ptr, cap, mopt)
+        st["m"] = b.matesw(st["pes"], mopt, cap=cap)
 
     def pair():
-        bsw.pe_pair_resident(eng, st["pes"], d_oreg.ptr, d_oinfo.ptr, d_ofirst.ptr, n, st["m"], d_pairs.ptr, popt)
+        b.pe_pair(st["pes"], popt)
 
     def all_regions():
-        bsw.reg2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_oreg.ptr, d_ord.ptr, st["m"], b_aln.ptr, b_cig.ptr,
-                             cs, b_md.ptr, ms, opt)
+        b.reg2aln(opt, into="all.aln")
 
     def records():
-        st["n"] = bsw.records_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_oreg.ptr, d_oinfo.ptr, d_ofirst.ptr,
-                                       st["m"], d_pairs.ptr, d_recs.ptr, d_rfirst.ptr, rcap, d_aln.ptr, d_areg.ptr, d_cig.ptr,
-                                       cs, d_md.ptr, ms, acap, ropt)
+        b.records(ropt)
 
-    def text(d_text, tcap):
-        n_rec, n_aln = st["n"]
-        return bsw.sam_text_resident(eng, d_recs.ptr, d_rfirst.ptr, n_rec, d_aln.ptr, d_cig.ptr, cs, d_md.ptr, ms, n_aln,
-                                     d_reads.ptr, d_off.ptr, d_len.ptr, n, d_nm.ptr, d_nmo.ptr, d_quals.ptr, True, d_text,
-                                     d_toff.ptr, tcap, ropt)
+    def text(tcap):
+        return b.sam_text(ropt, None, True, cap=tcap)
 
     front = (chain, extend, select, stat, rescue, pair, all_regions, records)
-
-    def timed(f, *a):
-        t = time.perf_counter()
-        f(*a)
-        return time.perf_counter() - t
 
     size = {}
     for case in args.cases:                                  # the size of each case's text
         use(case)
         for f in front:
             f()
-        try:
-            text(0, 0)
-            size[case] = 0
-        except bsw.BswError as e:
-            size[case] = e.needed
-    d_text = hiprt.DeviceBuffer(max(size.values()) + 4)
+        size[case] = b.sam_text(ropt, names, True)
+    b.alloc("text", max(size.values()) + 4)
     t = {c: {m: [] for m in STAGES} for c in args.cases}
     for _ in range(args.reps):
         for case in args.cases:
             use(case)
             for f in front:                                  # untimed: see the docstring
                 f()
-            text(d_text.ptr, size[case])
+            text(size[case])
             x = t[case]
             x["chain_s"].append(timed(chain))
             x["ext_s"].append(timed(extend))
@@ -213,7 +182,7 @@ def main():
             rs = bsw.rec_last_stats(eng)
             x["rec_aln_ms"].append(rs.aln_ms)
             x["rec_helper_ms"].append(rs.helper_ms)
-            x["text_s"].append(timed(text, d_text.ptr, size[case]))
+            x["text_s"].append(timed(text, size[case]))
             x["text_ms"].append(bsw.rec_last_stats(eng).text_ms)
             x["counts"] = {"seeds": int(st["ns"]), "selected": int(st["k"]), "after_rescue": int(st["m"]),
                            "matesw_jobs": ms_.n_jobs, "paired": ps.n_paired, "proper": ps.n_proper, "records": rs.n_rec,

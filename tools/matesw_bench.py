@@ -27,8 +27,9 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, ROOT)
 import bsw  # noqa: E402
 import hiprt  # noqa: E402
+from resident import ResidentBatch  # noqa: E402
 from bench import pe_reads  # noqa: E402
-from reg2aln_bench import spread  # noqa: E402
+from reg2aln_bench import spread, timed  # noqa: E402
 
 
 def unseedable(reads, n_pairs, L, f, seed=21):
@@ -132,38 +133,23 @@ def main():
         reads, off, lens = pe_reads(ref, args.pairs, args.read_len, seed=42)
         n_mut = unseedable(reads, args.pairs, args.read_len, f)
         n = len(lens)
-        d_reads = hiprt.DeviceBuffer.from_array(reads)
-        (_, sr, _), (d_seeds, d_sr, d_sc), (d_off, d_len) = bsw.seed_and_chain(fmi, d_reads, off, lens)
-        ns = len(sr)
-        d_regs, d_ext = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(ns * 4)
-        bsw.chain2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr, ns,
-                               d_regs.ptr, d_ext.ptr, opt)
-        d_sreg, d_srd = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(ns * 4)
-        d_info, d_first = hiprt.DeviceBuffer(ns * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((n + 1) * 4)
-        k = bsw.regs_select_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr,
-                                     d_regs.ptr, d_ext.ptr, ns, d_sreg.ptr, d_srd.ptr, d_info.ptr, d_first.ptr, ns, sopt)
-        pes = bsw.pe_stat_resident(eng, d_sreg.ptr, d_info.ptr, d_first.ptr, n, k, popt)
+        b = ResidentBatch(eng, reads, off, lens)
+        b.seed_and_chain(fmi)
+        b.chain2aln(opt)
+        k = b.select(sopt)
+        pes = b.pe_stat(popt)
         log(f"f = {f}: {n} reads ({n_mut} mates unseedable) -> {k} regions; FR [{pes[1]['low']}, {pes[1]['high']}]")
         cap = k + 8 * n_mut + 1024
-        d_oreg, d_ord = hiprt.DeviceBuffer(cap * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(cap * 4)
-        d_oinfo, d_ofirst = hiprt.DeviceBuffer(cap * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((n + 1) * 4)
-        d_pairs = hiprt.DeviceBuffer((n // 2) * bsw.PAIR_DTYPE.itemsize)
-        h_sreg = d_sreg.download(np.zeros(ns, dtype=bsw.ALNREG_DTYPE))
-        h_info = d_info.download(np.zeros(ns, dtype=bsw.SELINFO_DTYPE))
-        d_preg, d_pinfo = hiprt.DeviceBuffer.from_array(h_sreg), hiprt.DeviceBuffer.from_array(h_info)
+        h_sreg, first = b.get("sreg"), b.get("sfirst")
+        pb = ResidentBatch(eng, reads, off, lens)            # the pairing updates in place: it gets lists of its own
+        pb.put(sreg=h_sreg, sinfo=b.get("sinfo"), sfirst=first)
         state = {}
 
         def rescue():
-            state["m"] = bsw.matesw_resident(eng, pes, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_sreg.ptr, d_info.ptr,
-                                             d_first.ptr, k, d_oreg.ptr, d_ord.ptr, d_oinfo.ptr, d_ofirst.ptr, cap, mo)
+            state["m"] = b.matesw(pes, mo, cap=cap)
 
         def pair():
-            bsw.pe_pair_resident(eng, pes, d_preg.ptr, d_pinfo.ptr, d_first.ptr, n, k, d_pairs.ptr, popt)
-
-        def timed(fn):
-            t = time.perf_counter()
-            fn()
-            return time.perf_counter() - t
+            pb.pe_pair(pes, popt)
 
         rescue()
         st = bsw.matesw_last_stats(eng)
@@ -175,7 +161,6 @@ def main():
         if not args.only_new:
             pair()
             if st.n_jobs:
-                first = d_first.download(np.zeros(n + 1, np.int32))
                 jp, jr, jq = host_jobs(T, l_pac, reads, off, lens, h_sreg, first, pes, mo, 1)
                 jobs = (hiprt.DeviceBuffer.from_array(jp), hiprt.DeviceBuffer.from_array(jr),
                         hiprt.DeviceBuffer.from_array(jq), hiprt.DeviceBuffer(max(len(jp), 1) * bsw.KSWR_DTYPE.itemsize), len(jp))

@@ -25,9 +25,9 @@ sys.path.insert(0, os.path.join(ROOT, "bwa-mem2-arm_amd", "py"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, ROOT)
 import bsw  # noqa: E402
-import hiprt  # noqa: E402
+from resident import ResidentBatch  # noqa: E402
 from bench import pe_reads  # noqa: E402
-from reg2aln_bench import spread  # noqa: E402
+from reg2aln_bench import spread, timed  # noqa: E402
 
 
 def main():
@@ -56,33 +56,20 @@ def main():
     opt = bsw.ext_opt(w=args.w, l_pac=l_pac)
     sopt = bsw.sel_opt(w=args.w, l_pac=l_pac)
     popt = bsw.pe_opt(l_pac=l_pac)
-    d_reads = hiprt.DeviceBuffer.from_array(reads)
-    (_, sr, _), (d_seeds, d_sr, d_sc), (d_off, d_len) = bsw.seed_and_chain(fmi, d_reads, off, lens)
-    ns = len(sr)
-    d_regs, d_ext = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(ns * 4)
-    bsw.chain2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr, ns, d_regs.ptr,
-                           d_ext.ptr, opt)
+    b = ResidentBatch(eng, reads, off, lens)
+    ns = len(b.seed_and_chain(fmi)[1])
+    b.chain2aln(opt)
     log(f"{n} reads -> {ns} region slots (skipped seeds included)")
-    d_sreg, d_srd = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(ns * 4)
-    d_info, d_first = hiprt.DeviceBuffer(ns * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((n + 1) * 4)
-    d_pairs = hiprt.DeviceBuffer((n // 2) * bsw.PAIR_DTYPE.itemsize)
     state = {}
 
     def select():
-        state["k"] = bsw.regs_select_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr,
-                                              d_regs.ptr, d_ext.ptr, ns, d_sreg.ptr, d_srd.ptr, d_info.ptr, d_first.ptr,
-                                              ns, sopt)
+        state["k"] = b.select(sopt)
 
     def stat():
-        state["pes"] = bsw.pe_stat_resident(eng, d_sreg.ptr, d_info.ptr, d_first.ptr, n, state["k"], popt)
+        state["pes"] = b.pe_stat(popt)
 
     def pair():
-        bsw.pe_pair_resident(eng, state["pes"], d_sreg.ptr, d_info.ptr, d_first.ptr, n, state["k"], d_pairs.ptr, popt)
-
-    def timed(f):
-        t = time.perf_counter()
-        f()
-        return time.perf_counter() - t
+        b.pe_pair(state["pes"], popt)
 
     select()                                                 # warm-up: buffers grown, code loaded
     stat()
@@ -98,8 +85,7 @@ def main():
         tc.append(timed(pair))
         kc.append(bsw.pe_last_stats(eng).kernel_ms)
     st = bsw.pe_last_stats(eng)
-    first = d_first.download(np.zeros(n + 1, np.int32))
-    pairs = d_pairs.download(np.zeros(n // 2, dtype=bsw.PAIR_DTYPE))
+    first, pairs = b.get("sfirst"), b.get("pairs")
     per = np.diff(first)
     pes = state["pes"]
     out = {"tool": "pe_bench", "pairs": n // 2, "reads": n, "read_len": args.read_len, "ref_mb": args.ref_mb,

@@ -30,8 +30,9 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, ROOT)
 import bsw  # noqa: E402
 import hiprt  # noqa: E402
+from resident import ResidentBatch  # noqa: E402
 from bench import pe_reads  # noqa: E402
-from reg2aln_bench import spread  # noqa: E402
+from reg2aln_bench import spread, timed  # noqa: E402
 
 
 def main():
@@ -61,75 +62,39 @@ def main():
     sopt = bsw.sel_opt(w=args.w, l_pac=l_pac)
     popt = bsw.pe_opt(l_pac=l_pac)
     ropt = bsw.rec_opt(w=args.w, l_pac=l_pac, rname="chrS")
-    d_reads = hiprt.DeviceBuffer.from_array(reads)
-    d_quals = hiprt.DeviceBuffer.from_array((33 + (np.arange(len(reads)) * 7) % 41).astype(np.uint8))
+    b = ResidentBatch(eng, reads, off, lens, quals=(33 + (np.arange(len(reads)) * 7) % 41).astype(np.uint8))
     names = [b"frag%08d" % i for i in range(n // 2)]
-    nm, nm_off = bsw._names_host(names)
-    d_nm, d_nmo = hiprt.DeviceBuffer.from_array(nm), hiprt.DeviceBuffer.from_array(nm_off)
-    (_, sr, _), (d_seeds, d_sr, d_sc), (d_off, d_len) = bsw.seed_and_chain(fmi, d_reads, off, lens)
-    ns = len(sr)
-    d_regs, d_ext = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(ns * 4)
-    bsw.chain2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr, ns, d_regs.ptr,
-                           d_ext.ptr, opt)
+    ns = len(b.seed_and_chain(fmi)[1])
+    b.chain2aln(opt)
     log(f"{n} reads -> {ns} region slots (skipped seeds included)")
-    d_sreg, d_srd = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(ns * 4)
-    d_info, d_first = hiprt.DeviceBuffer(ns * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((n + 1) * 4)
-    d_pairs = hiprt.DeviceBuffer((n // 2) * bsw.PAIR_DTYPE.itemsize)
-    cs, ms = 16, 64
-    state = {}
 
     def select():
-        state["k"] = bsw.regs_select_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr,
-                                              d_regs.ptr, d_ext.ptr, ns, d_sreg.ptr, d_srd.ptr, d_info.ptr, d_first.ptr,
-                                              ns, sopt)
+        b.select(sopt)
 
     def stat_pair():
-        pes = bsw.pe_stat_resident(eng, d_sreg.ptr, d_info.ptr, d_first.ptr, n, state["k"], popt)
-        bsw.pe_pair_resident(eng, pes, d_sreg.ptr, d_info.ptr, d_first.ptr, n, state["k"], d_pairs.ptr, popt)
+        b.pe_pair(b.pe_stat(popt), popt)
 
     select()
     stat_pair()
-    k = state["k"]
-    rc, ac = n + k, k
-    d_aln, d_cig, d_md = hiprt.DeviceBuffer(ac * 40), hiprt.DeviceBuffer(ac * cs * 4), hiprt.DeviceBuffer(ac * ms)
-    d_recs, d_rfirst, d_areg = hiprt.DeviceBuffer(rc * 88), hiprt.DeviceBuffer((n + 1) * 4), hiprt.DeviceBuffer(ac * 4)
-    # (b) writes arrays of its own: the records' alignments stay what (c) left for (d)
-    b_aln, b_cig, b_md = hiprt.DeviceBuffer(ac * 40), hiprt.DeviceBuffer(ac * cs * 4), hiprt.DeviceBuffer(ac * ms)
+    k = b.n["sreg"]
 
     def all_regions():
-        bsw.reg2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_sreg.ptr, d_srd.ptr, k, b_aln.ptr, b_cig.ptr, cs,
-                             b_md.ptr, ms, opt)
+        # writes arrays of its own: the records' alignments stay what (c) left for (d)
+        b.reg2aln(opt, into="all.aln")
 
     def records():
-        state["n"] = bsw.records_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_sreg.ptr, d_info.ptr, d_first.ptr, k,
-                                          d_pairs.ptr, d_recs.ptr, d_rfirst.ptr, rc, d_aln.ptr, d_areg.ptr, d_cig.ptr, cs,
-                                          d_md.ptr, ms, ac, ropt)
+        b.records(ropt)
 
     records()                                                # warm-up, and the size of the text
-    n_rec, n_aln = state["n"]
-    d_toff = hiprt.DeviceBuffer((n_rec + 1) * 8)
-    try:
-        bsw.sam_text_resident(eng, d_recs.ptr, d_rfirst.ptr, n_rec, d_aln.ptr, d_cig.ptr, cs, d_md.ptr, ms, n_aln,
-                              d_reads.ptr, d_off.ptr, d_len.ptr, n, d_nm.ptr, d_nmo.ptr, d_quals.ptr, True, 0, d_toff.ptr,
-                              0, ropt)
-        n_bytes = 0
-    except bsw.BswError as e:
-        n_bytes = e.needed
-    d_text, d_copy = hiprt.DeviceBuffer(n_bytes), hiprt.DeviceBuffer(n_bytes)
+    n_bytes = b.sam_text(ropt, names, True)                  # (the sizing call, then one with exactly that room)
+    d_copy = hiprt.DeviceBuffer(n_bytes)
 
     def text():
-        return bsw.sam_text_resident(eng, d_recs.ptr, d_rfirst.ptr, n_rec, d_aln.ptr, d_cig.ptr, cs, d_md.ptr, ms, n_aln,
-                                     d_reads.ptr, d_off.ptr, d_len.ptr, n, d_nm.ptr, d_nmo.ptr, d_quals.ptr, True,
-                                     d_text.ptr, d_toff.ptr, n_bytes, ropt)
+        return b.sam_text(ropt, None, True, cap=n_bytes)
 
     def copy():
-        hiprt.check(hiprt.rt().hipMemcpy(ctypes.c_void_p(d_copy.ptr), ctypes.c_void_p(d_text.ptr), n_bytes, hiprt.D2D))
+        hiprt.check(hiprt.rt().hipMemcpy(ctypes.c_void_p(d_copy.ptr), ctypes.c_void_p(b.buf["text"].ptr), n_bytes, hiprt.D2D))
         hiprt.synchronize()
-
-    def timed(f):
-        t = time.perf_counter()
-        f()
-        return time.perf_counter() - t
 
     all_regions()
     text()

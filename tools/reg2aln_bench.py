@@ -21,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bwa-mem2-arm_amd", "py"))
 import bsw  # noqa: E402
 import hiprt  # noqa: E402
+from resident import ResidentBatch  # noqa: E402
 
 
 def make_reads(ref, n, L, seed, p_sub, p_n, indel_frac):
@@ -88,6 +89,12 @@ def spread(xs):
     return {"min": xs[0], "median": xs[len(xs) // 2], "max": xs[-1], "n": len(xs)}
 
 
+def timed(f, *a):
+    t = time.perf_counter()
+    f(*a)
+    return time.perf_counter() - t
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=1_000_000)
@@ -117,26 +124,21 @@ def main():
     eng = bsw.Engine()
     bsw.set_reference(eng, T)
     opt = bsw.ext_opt(w=args.w, l_pac=l_pac)
-    d_reads = hiprt.DeviceBuffer.from_array(reads)
-    (_, sr, _), (d_seeds, d_sr, d_sc), (d_off, d_len) = bsw.seed_and_chain(fmi, d_reads, off, lens)
+    b = ResidentBatch(eng, reads, off, lens)
+    _, sr, _ = b.seed_and_chain(fmi)
     ns = len(sr)
-    d_regs, d_ext = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(ns * 4)
-    bsw.chain2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr, ns, d_regs.ptr,
-                           d_ext.ptr, opt)
+    b.chain2aln(opt)                                         # its regions, one per seed, are the current lists
     log(f"{n} reads -> {ns} regions (skipped seeds included)")
     cs, ms = args.cigar_stride, args.md_stride
-    d_aln = hiprt.DeviceBuffer(ns * bsw.ALN_DTYPE.itemsize)
-    d_cig, d_md = hiprt.DeviceBuffer(ns * cs * 4), hiprt.DeviceBuffer(max(1, ns * ms))
 
     def new_call():
         t = time.perf_counter()
-        bsw.reg2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_regs.ptr, d_sr.ptr, ns, d_aln.ptr, d_cig.ptr,
-                             cs, d_md.ptr if ms else 0, ms, opt)
+        b.reg2aln(opt, cs, ms)
         return time.perf_counter() - t
 
     old_call = None
     if not args.only_new:
-        regs = d_regs.download(np.zeros(ns, dtype=bsw.ALNREG_DTYPE))
+        regs = b.get("regs")
         t0 = time.perf_counter()
         pairs, tbuf, qbuf, n_w0 = first_pass_jobs(T, l_pac, reads, off, regs, sr, args.w)
         log(f"{len(pairs)} first-pass jobs built on the host in {time.perf_counter() - t0:.1f} s")

@@ -22,8 +22,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bwa-mem2-arm_amd", "py"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import bsw  # noqa: E402
-import hiprt  # noqa: E402
-from reg2aln_bench import make_reads, spread  # noqa: E402
+from resident import ResidentBatch  # noqa: E402
+from reg2aln_bench import make_reads, spread, timed  # noqa: E402
 
 
 def main():
@@ -56,44 +56,32 @@ def main():
     bsw.set_reference(eng, T)
     opt = bsw.ext_opt(w=args.w, l_pac=l_pac)
     sopt = bsw.sel_opt(w=args.w, l_pac=l_pac)
-    d_reads = hiprt.DeviceBuffer.from_array(reads)
-    (_, sr, _), (d_seeds, d_sr, d_sc), (d_off, d_len) = bsw.seed_and_chain(fmi, d_reads, off, lens)
-    ns = len(sr)
-    d_regs, d_ext = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(ns * 4)
-    bsw.chain2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr, ns, d_regs.ptr,
-                           d_ext.ptr, opt)
+    b = ResidentBatch(eng, reads, off, lens)
+    ns = len(b.seed_and_chain(fmi)[1])
+    b.chain2aln(opt)
     log(f"{n} reads -> {ns} region slots (skipped seeds included)")
     cs, ms = args.cigar_stride, args.md_stride
-    d_aln = hiprt.DeviceBuffer(ns * bsw.ALN_DTYPE.itemsize)
-    d_cig, d_md = hiprt.DeviceBuffer(ns * cs * 4), hiprt.DeviceBuffer(max(1, ns * ms))
-    d_sreg, d_srd = hiprt.DeviceBuffer(ns * bsw.ALNREG_DTYPE.itemsize), hiprt.DeviceBuffer(ns * 4)
-    d_info, d_first = hiprt.DeviceBuffer(ns * bsw.SELINFO_DTYPE.itemsize), hiprt.DeviceBuffer((n + 1) * 4)
 
-    def aln(regs_ptr, read_ptr, k):
-        bsw.reg2aln_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, regs_ptr, read_ptr, k, d_aln.ptr, d_cig.ptr, cs,
-                             d_md.ptr if ms else 0, ms, opt)
+    def aln(cur):
+        """over the extension's region slots ("c") or the selection's survivors ("s")"""
+        b.cur = cur
+        b.reg2aln(opt, cs, ms)
 
     def select():
-        return bsw.regs_select_resident(eng, d_reads.ptr, d_off.ptr, d_len.ptr, n, d_seeds.ptr, d_sr.ptr, d_sc.ptr,
-                                        d_regs.ptr, d_ext.ptr, ns, d_sreg.ptr, d_srd.ptr, d_info.ptr, d_first.ptr, ns,
-                                        sopt)
-
-    def timed(f):
-        t = time.perf_counter()
-        f()
-        return time.perf_counter() - t
+        return b.select(sopt)
 
     def both():
-        aln(d_sreg.ptr, d_srd.ptr, select())
+        select()
+        aln("s")
 
     k = select()                                             # warm-up: buffers grown, code loaded
     if not args.only_new:
-        aln(d_regs.ptr, d_sr.ptr, ns)
-        aln(d_sreg.ptr, d_srd.ptr, k)
+        aln("c")
+        aln("s")
     ta, tb, tc, hs, ds = [], [], [], [], []
     for _ in range(args.reps):
         if not args.only_new:
-            ta.append(timed(lambda: aln(d_regs.ptr, d_sr.ptr, ns)))
+            ta.append(timed(lambda: aln("c")))
         tb.append(timed(select))
         st = bsw.sel_last_stats(eng)
         hs.append(st.helper_ms)
@@ -101,7 +89,7 @@ def main():
         if not args.only_new:
             tc.append(timed(both))
     st = bsw.sel_last_stats(eng)
-    info = d_info.download(np.zeros(ns, dtype=bsw.SELINFO_DTYPE))[:k]
+    info = b.get("sinfo")
     out = {"tool": "regsel_bench", "reads": n, "read_len": args.read_len, "ref_mb": args.ref_mb, "w": args.w,
            "p_sub": args.p_sub, "p_n": args.p_n, "indel_frac": args.indel_frac, "cigar_stride": cs, "md_stride": ms,
            "region_slots": ns, "regions_in": st.n_regs_in, "survivors": k, "redundant": st.n_redundant,
