@@ -22,6 +22,7 @@ constexpr int kNumWvClasses = 3;
 constexpr int kWvCols[kNumWvClasses] = {4, 8, 16};
 constexpr int kNumClasses = kWvClass0 + kNumWvClasses;
 static_assert(kNumClasses <= kMetaCounts, "class counts");
+static_assert(kNumLaneClasses <= kMetaRedoWords && kMetaRedo + kMetaRedoWords <= kMetaWords, "redo-list lengths");
 
 // Lifetime predictor for the sort key (scheduling only, results never depend on it): does the
 // query look like an extension of the target near the seed?  Identity of query[10, 40) with
@@ -379,8 +380,11 @@ int run_dp(const KParams &kp, Slot &s)
         for (int c = 0; c < kNumLaneClasses; ++c) {
             const int32_t np = counts[kPkClass0 + c];
             if (np > 0) {
+                // its redo list: d_keys2's slice at the class's offset (the sort is done with it),
+                // the length in the class's d_meta word, zeroed with the class counts (run_plan)
                 BSW_TRY(launch_pc_kernel(kLaneQmax[c], kp, w, d_pairs, s.d_order + off, np, d_ref, d_qer,
-                                         d_err, next_stream()));
+                                         d_err, reinterpret_cast<int32_t *>(s.d_keys2.p) + off,
+                                         s.d_meta + kMetaRedo + c, next_stream()));
                 s.stats.n_launches++;
                 s.stats.n_packed += np;
                 if (cell_bits == 8) s.stats.n_u8 += np;

@@ -44,7 +44,9 @@ constexpr int kMetaMaxq = kMetaCounts * kMetaSpread;   // d_meta: counts[32][16]
 constexpr int kMetaErr = kMetaMaxq + 1;
 constexpr int kMetaFlag = kMetaErr + 1;     // row-group kernel: a pair outside its contract
 constexpr int kMetaCnt = kMetaFlag + 1;     // extension pipeline: band-retry count readback
-constexpr int kMetaWords = kMetaCnt + 1;
+constexpr int kMetaRedo = kMetaCnt + 1;     // packed-column classes: redo-list lengths (left prune), device only
+constexpr int kMetaRedoWords = 5;
+constexpr int kMetaWords = kMetaRedo + kMetaRedoWords;
 constexpr int kKeyBits = 32;                // 4 class + 8 qlen + 1 related + 11 tlen + 8 h0 bits
 constexpr int32_t kStageBlk = 4096;         // host pipeline: pairs per staging block (a chunk is whole blocks)
 
@@ -169,6 +171,7 @@ struct BSW_HIDDEN Slot {
     DevBuf<uint8_t> d_ref, d_qer;
     DevBuf<uint32_t> d_keys, d_keys2;   // radix sort: the four grow together (grow_sort), d_order.cap
     DevBuf<int32_t> d_vals, d_order;    //   is their shared capacity
+                                        // (d_keys2 after the sort: the packed-column classes' redo lists, run_dp)
     DevBuf<uint8_t> d_tmp;
     DevBuf<int32_t> d_meta;             // counts[kMetaCounts], maxq_wide, err
     PinnedBuf<int32_t> h_meta;          // pinned mirror

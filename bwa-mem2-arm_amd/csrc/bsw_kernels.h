@@ -65,9 +65,12 @@ hipError_t launch_lane_kernel(int qmax, const KParams &kp, int32_t w, SeqPair *p
 
 // Packed-column lane kernel (bsw_pc.hip): kp.pk_ok scoring, qlen < qmax (strictly: slot qlen
 // must fall inside a 4-column group), h0 + min(len1, len2) <= 255; 64 pairs per wave.
+// redo[0 .. n) and *rcnt (zero on entry) are the class's redo list and its counter: the classes
+// that carry the left prune list the lanes they could not vouch for there
+// and a second launch on `s`, the kernel without the rule, computes them.
 hipError_t launch_pc_kernel(int qmax, const KParams &kp, int32_t w, SeqPair *pairs,
                             const int32_t *order, int32_t n, const uint8_t *ref,
-                            const uint8_t *qer, int32_t *err, hipStream_t s);
+                            const uint8_t *qer, int32_t *err, int32_t *redo, int32_t *rcnt, hipStream_t s);
 
 // Wave-per-alignment band kernel (bsw_wv.hip): one SeqPair per wavefront, the row spread over
 // the 64 lanes as a sliding window of 64 * cols absolute columns (cols = 4, 8 or 16).  Needs

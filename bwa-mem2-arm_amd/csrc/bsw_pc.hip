@@ -46,7 +46,7 @@ constexpr int kPcChunkDw = 17;           // dwords per lane per 64-row target ch
 #define BSW_PC_EXP_HALFHEAD 0
 #endif
 #ifdef BSW_PC_STATS
-__device__ unsigned long long g_pc_stats[11];
+__device__ unsigned long long g_pc_stats[13];
 // per-wave schedule record (tools/pc_times.py): start / end (s_memrealtime, 100 MHz), XCC id and
 // HW_ID (CU / SIMD / SE), rows run -- the launch's occupancy over time, ramp-up and tail
 constexpr int kPcTimesMax = 1 << 16;
@@ -682,14 +682,81 @@ __device__ __forceinline__ int pc_ubscan(std::integer_sequence<int, G...>, const
 #endif
 template <int QMAX> constexpr bool pc_left_skip() { return BSW_PC_LEFT_SKIP && QMAX >= BSW_PC_SKIP_QMIN; }
 
+// Left prune: at the refresh gz also passes over a NON-zero group when no
+// cell of it can reach gscore (hence best) in any lane that stays alive -- the early stop's per-cell
+// bound (item 10) applied to a prefix of the row.  Precheck (uniform, once per refresh): i > wl_max
+// (every static beg > 0) and every staying lane has end == qlen and gsc > 0.  Then per lane
+//   H plane: slots s > beg with H > 0:   H + (qlen - s)     < gsc
+//   E plane: slots s >= beg with E > 0:  E + (qlen - 1 - s) < gsc
+// in the style of pc_ub_reg; the group's plane registers are then zeroed in every lane (the left
+// skip's invariant holds literally) and the wave is marked pruned: from the next row on the row-end
+// certificate sends the lanes whose fate the zeroed cells could have changed to the redo pass.
+//   BSW_PC_LEFT_PRUNE 0 : off, the walk of item 11 alone (make ab AB_FLAGS=-DBSW_PC_LEFT_PRUNE=0)
+#ifndef BSW_PC_LEFT_PRUNE
+#define BSW_PC_LEFT_PRUNE 1
+#endif
+//   BSW_PC_PRUNE_QMIN   : the smallest QMAX class that carries it.  The byte planes never do: the rule's
+//                        state costs them scratch (QMAX 128, 160) or a wave per SIMD (96), as it costs the
+//                        int16 96 class its third wave (168 -> 175 VGPRs)
+#ifndef BSW_PC_PRUNE_QMIN
+#define BSW_PC_PRUNE_QMIN 128
+#endif
+template <int QMAX, bool BY> constexpr bool pc_left_prune()
+{
+    return BSW_PC_LEFT_PRUNE && !BY && pc_left_skip<QMAX>() && QMAX >= BSW_PC_PRUNE_QMIN;
+}
+//   BSW_PC_PRUNE_BRANCH : 1, the row-end certificate behind one uniform branch on the wave's mark; 0, as
+//                        selects on every row (not separable on the GPU)
+#ifndef BSW_PC_PRUNE_BRANCH
+#define BSW_PC_PRUNE_BRANCH 1
+#endif
+constexpr int kPcPruned = 1 << 8;         // the wave's pruned mark, a spare bit of gz's register
+template <bool PRUNE> __device__ __forceinline__ int pc_gz_of(int gz) { return PRUNE ? (gz & (kPcPruned - 1)) : gz; }
+
+// one plane register of the prune bound (slots 2K, 2K+1): c = v + gain where v > 0 (gw = packed
+// qlen for H, qlen - 1 for E), cleared where the slot is left of the lane's first one (bw = packed
+// beg for H: s > beg; beg - 1 for E: s >= beg), ub = max(ub, c).  0 <= v <= 255; a positive v sits in
+// a slot <= qlen (slots past qlen are never written and start at 0), so the gain is >= 0 there.
+template <int K>
+__device__ __forceinline__ void pc_pb_reg(uint32_t v, uint32_t gw, uint32_t bw, uint32_t &ub)
+{
+    constexpr uint32_t SC = (uint32_t)(2 * K) | ((uint32_t)(2 * K + 1) << 16);
+    uint32_t c, m;
+    asm volatile(
+        "v_pk_sub_i16 %[c], %[gw], %[sc]\n\t"               // the slot's gain
+        "v_pk_min_u16 %[m], %[v], 1 op_sel_hi:[1,0]\n\t"    // v > 0
+        "v_pk_mul_lo_u16 %[c], %[c], %[m]\n\t"
+        "v_pk_add_u16 %[c], %[c], %[v]\n\t"
+        "v_pk_sub_i16 %[m], %[bw], %[sc]\n\t"               // first - s < 0  <=>  s > first
+        "v_pk_ashrrev_i16 %[m], 15, %[m] op_sel_hi:[0,1]\n\t"
+        "v_and_b32_e32 %[c], %[c], %[m]\n\t"
+        "v_pk_max_u16 %[ub], %[ub], %[c]\n\t"
+        : [ub] "+v"(ub), [c] "=&v"(c), [m] "=&v"(m)
+        : [v] "v"(v), [gw] "v"(gw), [sc] "s"(SC), [bw] "v"(bw));
+}
+
+// positive parts of an int16 E register (the E plane is unclamped, PC_PH1)
+__device__ __forceinline__ uint32_t pc_pos2(uint32_t e)
+{
+    uint32_t r;
+    asm volatile("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(e));
+    return r;
+}
+
+struct PcPrune {                          // the refresh's prune state
+    bool pre;                             // uniform: the precheck holds on this row
+    int qlen, beg, gsc;                   // per lane
+    uint32_t npr;                         // BSW_PC_STATS: groups pruned
+};
+
 // group G of the walk: taken only when gz == G (uniform); z = the group's H registers or-ed with
 // the positive parts of its E registers (the int16 E plane is unclamped, PC_PH1)
-template <int QMAX, bool BY, int G>
-__device__ __forceinline__ void pc_gz_group(const uint32_t (&hh)[(BY ? QMAX / 4 : QMAX / 2)],
-                                            const uint32_t (&ee)[(BY ? QMAX / 4 : QMAX / 2)], bool live, int &gz)
+template <int QMAX, bool BY, bool PRUNE, int G>
+__device__ __forceinline__ void pc_gz_group(uint32_t (&hh)[(BY ? QMAX / 4 : QMAX / 2)],
+                                            uint32_t (&ee)[(BY ? QMAX / 4 : QMAX / 2)], bool live, int &gz, PcPrune &pp)
 {
     if constexpr (G < QMAX / 4) {
-        if (gz != G) return;
+        if (pc_gz_of<PRUNE>(gz) != G) return;
         uint32_t z;
         if constexpr (BY) {
             asm volatile("v_or_b32_e32 %0, %1, %2" : "=v"(z) : "v"(hh[G]), "v"(ee[G]));
@@ -702,36 +769,65 @@ __device__ __forceinline__ void pc_gz_group(const uint32_t (&hh)[(BY ? QMAX / 4 
                          : "=&v"(z), "=&v"(t)
                          : "v"(ee[2 * G]), "v"(ee[2 * G + 1]), "v"(hh[2 * G]), "v"(hh[2 * G + 1]));
         }
-        if (__ballot(live && z != 0u) == 0) gz = G + 1;
+        if (__ballot(live && z != 0u) == 0) {
+            gz = PRUNE ? gz + 1 : G + 1;
+        } else if constexpr (PRUNE) {
+            if (!pp.pre) return;                           // uniform
+            uint32_t ub = 0;
+            const uint32_t qw = pack2(pp.qlen), qm1w = pack2(pp.qlen - 1);
+            const uint32_t bgw = pack2(pp.beg), bgm1w = pack2(pp.beg - 1);
+            static_assert(!BY, "the byte planes are compiled without the prune");
+            pc_pb_reg<2 * G + 1>(hh[2 * G + 1], qw, bgw, ub);
+            pc_pb_reg<2 * G>(hh[2 * G], qw, bgw, ub);
+            pc_pb_reg<2 * G + 1>(pc_pos2(ee[2 * G + 1]), qm1w, bgm1w, ub);
+            pc_pb_reg<2 * G>(pc_pos2(ee[2 * G]), qm1w, bgm1w, ub);
+            const int u = (int)max(ub & 0xffffu, ub >> 16);
+            if (__ballot(live && u >= pp.gsc) == 0) {
+                hh[2 * G] = 0u; hh[2 * G + 1] = 0u; ee[2 * G] = 0u; ee[2 * G + 1] = 0u;
+                gz = (G + 1) | kPcPruned;
+#ifdef BSW_PC_STATS
+                pp.npr += 1;
+#endif
+            }
+        }
     }
 }
 
-template <int QMAX, bool BY, int S, int... K>
-__device__ __forceinline__ void pc_gz_seg(std::integer_sequence<int, K...>, const uint32_t (&hh)[(BY ? QMAX / 4 : QMAX / 2)],
-                                          const uint32_t (&ee)[(BY ? QMAX / 4 : QMAX / 2)], bool live, int &gz)
+template <int QMAX, bool BY, bool PRUNE, int S, int... K>
+__device__ __forceinline__ void pc_gz_seg(std::integer_sequence<int, K...>, uint32_t (&hh)[(BY ? QMAX / 4 : QMAX / 2)],
+                                          uint32_t (&ee)[(BY ? QMAX / 4 : QMAX / 2)], bool live, int &gz, PcPrune &pp)
 {
-    if ((gz >> 3) != S) return;                            // uniform
-    (pc_gz_group<QMAX, BY, 8 * S + K>(hh, ee, live, gz), ...);
+    if ((pc_gz_of<PRUNE>(gz) >> 3) != S) return;            // uniform
+    (pc_gz_group<QMAX, BY, PRUNE, 8 * S + K>(hh, ee, live, gz, pp), ...);
 }
 
-template <int QMAX, bool BY, int... S>
-__device__ __forceinline__ void pc_gz_refresh(std::integer_sequence<int, S...>, const uint32_t (&hh)[(BY ? QMAX / 4 : QMAX / 2)],
-                                              const uint32_t (&ee)[(BY ? QMAX / 4 : QMAX / 2)], bool live, int &gz)
+template <int QMAX, bool BY, bool PRUNE, int... S>
+__device__ __forceinline__ void pc_gz_refresh(std::integer_sequence<int, S...>, uint32_t (&hh)[(BY ? QMAX / 4 : QMAX / 2)],
+                                              uint32_t (&ee)[(BY ? QMAX / 4 : QMAX / 2)], bool live, int &gz, PcPrune &pp)
 {
-    (pc_gz_seg<QMAX, BY, S>(std::make_integer_sequence<int, 8>{}, hh, ee, live, gz), ...);
+    (pc_gz_seg<QMAX, BY, PRUNE, S>(std::make_integer_sequence<int, 8>{}, hh, ee, live, gz, pp), ...);
 }
 
 // WPB waves per workgroup: with 1, a wave's slot (and its LDS) is reused as soon as that wave
 // ends, instead of when the slowest of its block's waves ends.
-template <int QMAX, int WPB, bool BY>
+//
+// The classes that carry the left prune (§3 item 12) send their redo lanes to a second pass: such a
+// lane stores no outputs and appends its pair index to redo[] (one atomic add on *rcnt per wave).
+// REDO: that second pass, the instance without the rule -- `order` is the redo list and its lane
+// count is *rcnt, at most n.  It is launched for the worst case (every pair listed) with WPB = 4,
+// which quarters the blocks that find nothing to do.
+template <int QMAX, int WPB, bool BY, bool REDO>
 __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams kp, const int32_t w,
                                                     SeqPair *__restrict__ pairs,
                                                     const int32_t *__restrict__ order,
-                                                    const int32_t n,
+                                                    const int32_t n_in,
                                                     const uint8_t *__restrict__ ref,
                                                     const uint8_t *__restrict__ qer,
-                                                    int32_t *__restrict__ err)
+                                                    int32_t *__restrict__ err,
+                                                    int32_t *__restrict__ redo,
+                                                    int32_t *__restrict__ rcnt)
 {
+    constexpr bool PRUNE = !REDO && pc_left_prune<QMAX, BY>();
     constexpr int NG = QMAX / 4;        // groups = query words (4 codes each)
     constexpr int CDW = kPcChunkDw;     // target dwords per lane per 64-row chunk
 #ifdef BSW_PC_STATS
@@ -739,6 +835,11 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
 #endif
     __shared__ uint32_t s_tgt[WPB][2][CDW][64];   // 8.7 KB per wave
     __shared__ uint2 s_prof[8];                           // per-row score profiles, by target code
+    int32_t n = n_in;
+    if constexpr (REDO) {               // the list's length, read once, before any other access;
+        n = min(n, *rcnt);              // a block past it has nothing to do
+        if ((int)(blockIdx.x * blockDim.x) >= n) return;
+    }
     if (threadIdx.x < 8) s_prof[threadIdx.x] = make_uint2(kp.prof[threadIdx.x][0], kp.prof[threadIdx.x][1]);
     __syncthreads();
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -858,6 +959,7 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
 #endif
     int gz = 0;                             // left skip: groups below gz are all-zero in every live lane
     (void)gz;
+    PcPrune pp{false, 0, 0, 0, 0u};         // left prune: the refresh's inputs
     for (int i = 0;; ++i) {
         const bool act = alive && i < tlen;
         alive = act;
@@ -918,7 +1020,7 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
             r.fast = gbits(gfa, gfn);
             r.left = gbits(glo, gln + 1);
             if constexpr (pc_left_skip<QMAX>()) {   // groups below gz leave the entered set; the FAST
-                const uint64_t keep = ~0ull << gz;  // test comes first in a group, so its set too
+                const uint64_t keep = ~0ull << pc_gz_of<PRUNE>(gz);   // test comes first in a group, so its set too
                 r.enter &= keep;
                 r.fast &= keep;
             }
@@ -965,6 +1067,24 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
                 best_i = better ? i : best_i;
                 best_j = better ? mj : best_j;
                 best = better ? m : best;
+                if constexpr (PRUNE) {
+                    // the certificate of a pruned wave (§3 item 12), before the early stop: zeroed
+                    // cells only lower values, all below gscore, so a lane whose row has a new best
+                    // or is far from z-drop whatever mj is (dz <= best - m) is in its true state;
+                    // one whose row maximum is 0 retires with its outputs final; the others -- and a
+                    // lane whose band end would leave qlen (h1 == 0) -- are computed again.  The
+                    // mark travels in the low bit of sp (SeqPair is 4-byte aligned).
+#if BSW_PC_PRUNE_BRANCH
+                    if (gz & kPcPruned)
+#endif
+                    {
+                        const bool rd = (gz & kPcPruned) != 0 &&
+                                        ((act && !better && m > 0 && kp.zdrop > 0 && best - m > kp.zdrop) ||
+                                         (alive && h1 == 0));
+                        alive = alive && !rd;
+                        sp = (SeqPair *)((uintptr_t)sp | (uintptr_t)rd);
+                    }
+                }
             }
 #if BSW_PC_EARLY_STOP
             {   // early stop, after this row's best / gscore updates.  gsc <= best
@@ -1008,8 +1128,18 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
             }
 #endif
             if constexpr (pc_left_skip<QMAX>()) {
-                if ((i & BSW_PC_SKIP_MASK) == BSW_PC_SKIP_ROW)
-                    pc_gz_refresh<QMAX, BY>(std::make_integer_sequence<int, (NG + 7) / 8>{}, hh, ee, alive, gz);
+                if ((i & BSW_PC_SKIP_MASK) == BSW_PC_SKIP_ROW) {
+                    if constexpr (PRUNE) {         // the prune's precheck: every static beg > 0, and
+                                                   // every staying lane at the query's end with gsc > 0
+                        pp.pre = i > wl_max && __ballot(alive && !(end == qlen && gsc > 0)) == 0;
+                        // (qlen through an opaque move: its packed forms are then built in the walk,
+                        // not hoisted into registers that live across the groups)
+                        asm volatile("v_mov_b32_e32 %0, %1" : "=v"(pp.qlen) : "v"(qlen));
+                        pp.beg = beg; pp.gsc = gsc;
+                    }
+                    pc_gz_refresh<QMAX, BY, PRUNE>(std::make_integer_sequence<int, (NG + 7) / 8>{}, hh, ee, alive, gz,
+                                                   pp);
+                }
             }
 #ifdef BSW_PC_STATS
             nrows += act;
@@ -1062,6 +1192,29 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
         }
     }
 #endif
+    if constexpr (PRUNE) {
+        // redo lanes: their pair index (read again: no register held it across the loop) appended to
+        // the class's list, one atomic add per wave, lanes at base + rank.  At most one entry per
+        // valid lane of the launch, so every index written is below the class's pair count.
+        const bool rd = ((uintptr_t)sp & 1u) != 0;          // never an invalid lane (sp == nullptr)
+        const unsigned long long rb = __ballot(rd);
+        if (rb) {                                           // uniform
+            int base = 0;
+            if (ln == __ffsll((long long)rb) - 1) base = atomicAdd(rcnt, (int)__popcll(rb));
+            base = __shfl(base, __ffsll((long long)rb) - 1);
+            if (rd) {
+                const unsigned g = blockIdx.x * blockDim.x + threadIdx.x;
+                redo[base + (int)__popcll(rb & ((1ull << ln) - 1ull))] = order ? order[g] : (int)g;
+            }
+        }
+#ifdef BSW_PC_STATS
+        if (ln == 0) {
+            atomicAdd(&g_pc_stats[11], (unsigned long long)pp.npr);
+            atomicAdd(&g_pc_stats[12], (unsigned long long)__popcll(rb));
+        }
+#endif
+        if (rd) sp = nullptr;
+    }
     if (sp) {
         sp->score = best;
         sp->tle = best_i + 1;
@@ -1074,12 +1227,13 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
 
 #ifdef BSW_PC_STATS
 // [rows, groups entered, fast, masked-R, masked-L, lastpos scans, waves, uniform-end rows, early-stop scan
-// rows, lanes retired by the scalar bound, lanes retired by the per-cell bound] summed over waves
+// rows, lanes retired by the scalar bound, lanes retired by the per-cell bound, non-zero groups the left
+// prune passed over, redo lanes] summed over waves
 extern "C" int bsw_pc_stats(unsigned long long *out, int reset)
 {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pc_stats), 11 * sizeof(unsigned long long)) != hipSuccess) return -5;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pc_stats), 13 * sizeof(unsigned long long)) != hipSuccess) return -5;
     if (reset) {
-        unsigned long long z[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        unsigned long long z[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_pc_stats), z, sizeof(z)) != hipSuccess) return -5;
     }
     return 0;
@@ -1095,29 +1249,40 @@ extern "C" int bsw_pc_times(unsigned long long *out, int n)
 
 template <int QMAX>
 static void launch_pc_q(const KParams &kp, int32_t w, SeqPair *pairs, const int32_t *order, int32_t n,
-                        const uint8_t *ref, const uint8_t *qer, int32_t *err, hipStream_t s)
+                        const uint8_t *ref, const uint8_t *qer, int32_t *err, int32_t *redo, int32_t *rcnt,
+                        hipStream_t s)
 {
     const unsigned grid = (unsigned)((n + 63) / 64);
     // one wave per workgroup: a finished wave's slot and LDS are reused at once
     if (kp.kern8 == 2)                 // byte planes (BSW_OPT_KERNEL8 = 2)
-        hipLaunchKernelGGL((pc_kernel<QMAX, 1, true>), dim3(grid), dim3(64), 0, s, kp, w, pairs, order, n,
-                           ref, qer, err);
+        hipLaunchKernelGGL((pc_kernel<QMAX, 1, true, false>), dim3(grid), dim3(64), 0, s, kp, w, pairs, order, n,
+                           ref, qer, err, redo, rcnt);
     else
-        hipLaunchKernelGGL((pc_kernel<QMAX, 1, false>), dim3(grid), dim3(64), 0, s, kp, w, pairs, order,
-                           n, ref, qer, err);
+        hipLaunchKernelGGL((pc_kernel<QMAX, 1, false, false>), dim3(grid), dim3(64), 0, s, kp, w, pairs, order,
+                           n, ref, qer, err, redo, rcnt);
+    if constexpr (pc_left_prune<QMAX, false>()) {
+        // the redo pass behind it on the same stream: no host round trip, so
+        // the grid is sized for every pair listed and the blocks past *rcnt return at once
+        constexpr int kRedoWpb = 4;
+        const unsigned rgrid = (unsigned)((n + 64 * kRedoWpb - 1) / (64 * kRedoWpb));
+        if (kp.kern8 != 2)             // (the byte planes do not carry the rule)
+            hipLaunchKernelGGL((pc_kernel<QMAX, kRedoWpb, false, true>), dim3(rgrid), dim3(64 * kRedoWpb), 0, s, kp, w,
+                               pairs, redo, n, ref, qer, err, nullptr, rcnt);
+    }
 }
 
 hipError_t launch_pc_kernel(int qmax, const KParams &kp, int32_t w, SeqPair *pairs,
                             const int32_t *order, int32_t n, const uint8_t *ref,
-                            const uint8_t *qer, int32_t *err, hipStream_t s)
+                            const uint8_t *qer, int32_t *err, int32_t *redo, int32_t *rcnt, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
+    if (!redo || !rcnt) return hipErrorInvalidValue;
     switch (qmax) {
-    case 32: launch_pc_q<32>(kp, w, pairs, order, n, ref, qer, err, s); break;
-    case 64: launch_pc_q<64>(kp, w, pairs, order, n, ref, qer, err, s); break;
-    case 96: launch_pc_q<96>(kp, w, pairs, order, n, ref, qer, err, s); break;
-    case 128: launch_pc_q<128>(kp, w, pairs, order, n, ref, qer, err, s); break;
-    case 160: launch_pc_q<160>(kp, w, pairs, order, n, ref, qer, err, s); break;
+    case 32: launch_pc_q<32>(kp, w, pairs, order, n, ref, qer, err, redo, rcnt, s); break;
+    case 64: launch_pc_q<64>(kp, w, pairs, order, n, ref, qer, err, redo, rcnt, s); break;
+    case 96: launch_pc_q<96>(kp, w, pairs, order, n, ref, qer, err, redo, rcnt, s); break;
+    case 128: launch_pc_q<128>(kp, w, pairs, order, n, ref, qer, err, redo, rcnt, s); break;
+    case 160: launch_pc_q<160>(kp, w, pairs, order, n, ref, qer, err, redo, rcnt, s); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

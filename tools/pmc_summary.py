@@ -6,7 +6,7 @@ workload key, profiles/pmc_latest.json (read by bench.py for roofline.traffic). 
 from the profiled run's own JSON line (<src>/trace.log: roofline.pmc_key, bench.workload_key), so a
 bench line only ever finds the counters of a pass that ran its own workload.
 """
-import csv, glob, json, os, shutil, sys
+import csv, glob, json, os, re, shutil, sys
 from collections import defaultdict
 
 args = sys.argv[1:]
@@ -57,6 +57,9 @@ def short(name):
         if kern in name:
             for q in ('160', '128', '96', '80', '64', '48', '32', '16', '10', '8', '6', '4'):
                 if f'ILi{q}E' in name or f'<{q},' in name or f'<{q}>' in name:
+                    # the packed-column kernel's redo pass (its fourth template argument) apart
+                    if kern == 'pc_kernel' and re.search(r'ELb[01]ELb1EE|, (true|false), true>', name):
+                        return f'pc_kernel<{q}>:redo'
                     return f'{kern}<{q}>'
             return kern
     for k in ('wide_kernel', 'plan_kernel', 'Radix', 'radix', 'Onesweep', 'onesweep'):
