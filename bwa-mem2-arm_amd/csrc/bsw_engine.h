@@ -28,6 +28,7 @@
 #include "../../include/bsw_pe.h"
 #include "../../include/bsw_matesw.h"
 #include "../../include/bsw_rec.h"
+#include "../../include/bsw_bam.h"
 #include "../../include/bsw_contigs.h"
 #include "bsw_contig_seg.h"
 #include "bsw_kernels.h"
@@ -280,6 +281,8 @@ struct DeviceCtx {
     int32_t n_ctg = 0;
     int64_t ctg_sum = 0;
     std::vector<int64_t> h_ctg_off;     // the prefix sums on the host (the host window builder, bsw_ext.cpp)
+    std::vector<uint8_t> h_ctg_names;   // the names and their offsets on the host (bsw_bam_header)
+    std::vector<int32_t> h_ctg_name_off;
 
     // the table fits a call that names l_pac (0: a one-strand reference of refres_len bases)
     bool ctg_ok(int64_t l_pac) const { return n_ctg == 0 || ctg_sum == (l_pac > 0 ? l_pac : refres_len); }
@@ -430,6 +433,7 @@ struct bsw_ctx {
     bsw_pe_stats_t pe_last{};
     bsw_matesw_stats_t matesw_last{};
     bsw_rec_stats_t rec_last{};
+    bsw_bam_stats_t bam_last{};
     struct Pinned { std::mutex mu; bsw::PinnedBuf<uint8_t> b; } pin[2];
     int glob_band = 0;                  // BSW_OPT_GLOB_BAND
     int64_t ext_chunk = 0;              // BSW_OPT_EXT_CHUNK (0: the int32-offset bound)

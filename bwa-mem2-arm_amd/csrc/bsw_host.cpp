@@ -912,6 +912,8 @@ int bsw_set_contigs(bsw_ctx_t *ctx, int32_t n, const int64_t *len, const char *c
         dc.n_ctg = n;
         dc.ctg_sum = off[(size_t)n];
         dc.h_ctg_off = off;
+        dc.h_ctg_names = bytes;
+        dc.h_ctg_name_off = name_off;
         staged[d] = Staged();
     }
     return BSW_OK;

@@ -16,7 +16,10 @@
 //                            from the tail of one and the head of the other and stored once after the
 //                            block's barrier; only the at most three bytes at either end of a BLOCK's
 //                            range are byte stores.
-// Both text kernels run ONE emitter (emit_line) over two sinks, so the lengths are the bytes written.
+//   bam_len_kernel, bam_write_kernel   the same two passes for BAM alignment blocks (include/bsw_bam.h):
+//                            kRecBamGroup lanes per record, the text's sinks, window and edge dwords
+// Both text kernels run ONE emitter (emit_line) over two sinks, so the lengths are the bytes written;
+// both BAM kernels run emit_bam over the same two.
 // The lists are short (bsw_pe.hip's general kernel): XA membership is recounted per record instead
 // of kept in per-read arrays.
 #include <hip/hip_runtime.h>
@@ -288,13 +291,21 @@ struct CountSink {                      // one work item per record: the line's 
     __device__ __forceinline__ void copy(const uint8_t *, int k) { n += k; }
     __device__ __forceinline__ void seq(const uint8_t *, int qb, int qe, bool) { n += qe - qb; }
     __device__ __forceinline__ void qual(const uint8_t *, int qb, int qe, bool) { n += qe - qb; }
+    // (the binary puts of the BAM emitter)
+    __device__ __forceinline__ void u8(uint32_t) { ++n; }
+    __device__ __forceinline__ void u16(uint32_t) { n += 2; }
+    __device__ __forceinline__ void u32(uint32_t) { n += 4; }
+    __device__ __forceinline__ void rep(uint8_t, int k) { n += k; }
+    __device__ __forceinline__ void seq4(const uint8_t *, int qb, int qe, bool) { n += (qe - qb + 1) >> 1; }
+    __device__ __forceinline__ void qual33(const uint8_t *, int qb, int qe, bool) { n += qe - qb; }
 };
 
 constexpr int kWin = 512;               // bytes of a group's LDS window
 
-// kRecTextGroup lanes of one wave assemble a line.  win[0] is the byte at global offset gbase (a
-// multiple of 4); fill = the bytes assembled so far, the same on every lane of the group: every
+// G lanes of one wave assemble a line (the text kernel: kRecTextGroup; the BAM kernel, a block:
+// kRecBamGroup).  win[0] is the byte at global offset gbase (a multiple of 4); fill = the bytes assembled so far, the same on every lane of the group: every
 // lane runs every call, lane 0 alone writes what is not a bulk copy.
+template <int G>
 struct LdsSink {
     uint8_t *win;                       // the group's window, 4-byte aligned
     uint32_t *out;                      // the text, as dwords
@@ -325,7 +336,7 @@ struct LdsSink {
             head_pending = false;
         }
         const uint32_t *w = (const uint32_t *)win;
-        for (int d = d0 + lane; d < nd; d += kRecTextGroup) out[(gbase >> 2) + d] = w[d];
+        for (int d = d0 + lane; d < nd; d += G) out[(gbase >> 2) + d] = w[d];
         uint8_t keep = 0;
         if (lane < rem) keep = win[nd * 4 + lane];
         fence();
@@ -374,7 +385,7 @@ struct LdsSink {
         while (done < k) {
             if (fill == kWin) flush();
             const int c = min(k - done, kWin - fill);
-            for (int t = lane; t < c; t += kRecTextGroup) win[fill + t] = src(done + t);
+            for (int t = lane; t < c; t += G) win[fill + t] = src(done + t);
             fill += c;
             done += c;
         }
@@ -390,6 +401,40 @@ struct LdsSink {
     __device__ __forceinline__ void qual(const uint8_t *s, int qb, int qe, bool rev)
     {
         bulk(qe - qb, [&](int t) { return s[rev ? qe - 1 - t : qb + t]; });
+    }
+    // the binary puts of the BAM emitter, little-endian: one byte per lane (G >= 4)
+    __device__ __forceinline__ void u8(uint32_t v)
+    {
+        room(1);
+        if (lane == 0) win[fill] = (uint8_t)v;
+        ++fill;
+    }
+    __device__ __forceinline__ void u16(uint32_t v)
+    {
+        room(2);
+        if (lane < 2) win[fill + lane] = (uint8_t)(v >> (8 * lane));
+        fill += 2;
+    }
+    __device__ __forceinline__ void u32(uint32_t v)
+    {
+        room(4);
+        if (lane < 4) win[fill + lane] = (uint8_t)(v >> (8 * lane));
+        fill += 4;
+    }
+    __device__ __forceinline__ void rep(uint8_t c, int k) { bulk(k, [&](int) { return c; }); }
+    // two bases per byte, the first in the high nibble: A 1, C 2, G 4, T 8, the rest 15
+    __device__ __forceinline__ void seq4(const uint8_t *s, int qb, int qe, bool rev)
+    {
+        const int n = qe - qb;
+        auto nib = [&](int j) {
+            const int c = s[rev ? qe - 1 - j : qb + j];
+            return c >= 4 ? 15u : rev ? 8u >> c : 1u << c;
+        };
+        bulk((n + 1) >> 1, [&](int t) { return (uint8_t)(nib(2 * t) << 4 | (2 * t + 1 < n ? nib(2 * t + 1) : 0u)); });
+    }
+    __device__ __forceinline__ void qual33(const uint8_t *s, int qb, int qe, bool rev)
+    {
+        bulk(qe - qb, [&](int t) { return (uint8_t)(s[rev ? qe - 1 - t : qb + t] - 33); });
     }
     // the last whole dwords out; the line's last (end & 3) bytes to the edge they share with the next line
     __device__ __forceinline__ void finish()
@@ -614,7 +659,7 @@ __global__ __launch_bounds__(kRecTextBlock) void rec_text_write_kernel(RecText t
     __syncthreads();
     if (g < nvalid) {
         const int64_t o = text_off[r0 + g];
-        LdsSink s;
+        LdsSink<kRecTextGroup> s;
         s.win = (uint8_t *)win[g];
         s.out = (uint32_t *)text;
         s.head = (uint8_t *)&edge[g];
@@ -642,7 +687,237 @@ __global__ __launch_bounds__(kRecTextBlock) void rec_text_write_kernel(RecText t
     }
 }
 
+// ---------------------------------------------------------------- BAM (include/bsw_bam.h)
+// the UCSC binning scheme, 14-bit smallest bin, 5 levels; beg = -1, end = 0 gives 4680 (arithmetic shifts)
+__device__ __forceinline__ int reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+
+// what the binary fields cannot hold, on top of text_record_ok
+__device__ __forceinline__ bool bam_record_ok(const RecText &t, int i)
+{
+    if (!text_record_ok(t, i)) return false;
+    const bsw_rec_t &p = t.recs[i];
+    const int ni = t.paired ? p.read >> 1 : p.read;
+    if (t.name_off[ni + 1] - t.name_off[ni] > BSW_BAM_MAX_NAME) return false;
+    if (p.tlen < INT32_MIN || p.tlen > INT32_MAX) return false;
+    if (p.pos >= 0 && p.pos - place_of(t, p.pos).base > INT32_MAX) return false;
+    if (p.mpos >= 0 && p.mpos - place_of(t, p.mpos).base > INT32_MAX) return false;
+    return p.aln < 0 || t.aln[p.aln].n_cigar <= 0xffff;
+}
+
+// an integer tag with the smallest type that holds v, as the text parser picks it
+template <class S>
+__device__ __forceinline__ void put_int_tag(S &s, const char *tag, int32_t v)
+{
+    s.lit(tag, 2);
+    if (v >= 0) {
+        if (v <= 0xff) { s.ch('C'); s.u8(v); }
+        else if (v <= 0xffff) { s.ch('S'); s.u16(v); }
+        else { s.ch('I'); s.u32(v); }
+    } else {
+        if (v >= -128) { s.ch('c'); s.u8(v); }
+        else if (v >= -32768) { s.ch('s'); s.u16(v); }
+        else { s.ch('i'); s.u32(v); }
+    }
+}
+
+// block = the record's bytes behind block_size: the count pass passes 0, the write pass the
+// difference of its offsets.  The Z values are emit_line's own calls.
+template <class S>
+__device__ __forceinline__ void emit_bam(S &s, const RecText &t, int i, uint32_t block)
+{
+    const bsw_rec_t p = t.recs[i];
+    const int r = p.read, which = p.which;
+    const bool soft = t.flags & BSW_REC_SOFTCLIP;
+    const char clip = soft ? 0 : (which ? 'H' : 'S');
+    const int ni = t.paired ? r >> 1 : r;
+    const int64_t n0 = t.name_off[ni];
+    const int l_name = (int)(t.name_off[ni + 1] - n0);
+    const int ncig = p.aln >= 0 ? t.aln[p.aln].n_cigar : 0;
+    const uint32_t *cg = t.cigar + (size_t)max(p.aln, 0) * t.cigar_stride;
+    Place at = {nullptr, 0, -1, 0, 0};                   // (an empty range: nothing is near it)
+    int64_t pos = -1, mpos = -1;
+    int mrid = -1;
+    if (p.pos >= 0) {
+        at = place_of(t, p.pos);
+        pos = p.pos - at.base;
+    }
+    if (p.mpos >= 0) {
+        const Place mt = place_near(t, p.mpos, at);
+        mrid = mt.rid;
+        mpos = p.mpos - mt.base;
+    }
+    int qb = 0, qe = t.read_len[r];
+    if (ncig && which && !soft) {
+        const int c5 = (cg[0] & 15u) >= 3 ? (int)(cg[0] >> 4) : 0, c3 = (cg[ncig - 1] & 15u) >= 3 ? (int)(cg[ncig - 1] >> 4) : 0;
+        if (p.is_rev) { qe -= c5; qb += c3; }
+        else { qb += c5; qe -= c3; }
+    }
+    const int bin = reg2bin(pos, pos + (ncig ? cigar_rlen(cg, ncig) : 1));
+    // the fixed part: nine dwords
+    s.u32(block);
+    s.u32((uint32_t)at.rid);
+    s.u32((uint32_t)pos);
+    s.u32((uint32_t)(l_name + 1) | (uint32_t)((p.pos >= 0 ? p.mapq : 0) & 0xff) << 8 | (uint32_t)(bin & 0xffff) << 16);
+    s.u32((uint32_t)ncig | (uint32_t)(p.sam_flag & 0xffff) << 16);
+    s.u32((uint32_t)(qe - qb));
+    s.u32((uint32_t)mrid);
+    s.u32((uint32_t)mpos);
+    s.u32((uint32_t)p.tlen);
+    s.copy(t.names + n0, l_name);
+    s.u8(0);
+    for (int k = 0; k < ncig; ++k) {
+        const uint32_t w = cg[k];
+        uint32_t op = w & 15u;
+        if (op >= 3) op = clip ? (clip == 'S' ? 4u : 5u) : (op == 3 ? 4u : 5u);
+        s.u32((w & ~15u) | op);
+    }
+    const int64_t ro = t.read_off[r];
+    s.seq4(t.reads + ro, qb, qe, p.is_rev != 0);
+    if (t.quals) s.qual33(t.quals + ro, qb, qe, p.is_rev != 0);
+    else s.rep(0xff, qe - qb);
+    if (ncig) {
+        put_int_tag(s, "NM", t.aln[p.aln].NM);
+        s.lit("MDZ", 3);
+        s.copy(t.md + (size_t)p.aln * t.md_stride, t.aln[p.aln].md_len);
+        s.u8(0);
+    }
+    if (p.m_aln >= 0) {
+        s.lit("MCZ", 3);
+        put_cigar(s, t.cigar + (size_t)p.m_aln * t.cigar_stride, t.aln[p.m_aln].n_cigar, clip);
+        s.u8(0);
+    }
+    put_int_tag(s, "AS", p.score);
+    if (p.sub >= 0) put_int_tag(s, "XS", p.sub);
+    if (!(p.flag & 0x100)) {
+        const int f0 = t.rec_first[r];
+        bool any = false;
+        for (int j = 0; j < p.n_list; ++j) any |= j != which && !(t.recs[f0 + j].flag & 0x100);
+        if (any) {
+            s.lit("SAZ", 3);
+            for (int j = 0; j < p.n_list; ++j) {
+                if (j == which || (t.recs[f0 + j].flag & 0x100)) continue;
+                const int qa = t.recs[f0 + j].aln;
+                const bsw_aln_t a = t.aln[qa];
+                const Place sa = place_near(t, a.pos, at);
+                s.copy(sa.name, sa.len);
+                s.ch(',');
+                s.num(a.pos - sa.base + 1);
+                s.ch(',');
+                s.ch(a.is_rev ? '-' : '+');
+                s.ch(',');
+                put_cigar(s, t.cigar + (size_t)qa * t.cigar_stride, a.n_cigar, 0);
+                s.ch(',');
+                s.num(t.recs[f0 + j].mapq);
+                s.ch(',');
+                s.num(a.NM);
+                s.ch(';');
+            }
+            s.u8(0);
+        }
+    }
+    if (p.xa_n > 0) {
+        s.lit("XAZ", 3);
+        for (int j = p.xa_first; j < p.xa_first + p.xa_n; ++j) {
+            const bsw_aln_t a = t.aln[j];
+            const Place xa = place_near(t, a.pos, at);
+            s.copy(xa.name, xa.len);
+            s.ch(',');
+            s.ch(a.is_rev ? '-' : '+');
+            s.num(a.pos - xa.base + 1);
+            s.ch(',');
+            put_cigar(s, t.cigar + (size_t)j * t.cigar_stride, a.n_cigar, 0);
+            s.ch(',');
+            s.num(a.NM);
+            s.ch(';');
+        }
+        s.u8(0);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void bam_len_kernel(RecText t, int64_t *len, int32_t *meta)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i > t.n_rec) return;
+    if (i == t.n_rec) {
+        len[i] = 0;
+        return;
+    }
+    if (!bam_record_ok(t, i)) {
+        atomicOr(meta + kRecErr, 1);
+        len[i] = 0;
+        return;
+    }
+    CountSink s;
+    emit_bam(s, t, i, 0u);
+    len[i] = s.n;
+}
+
+constexpr int kBamPerBlock = kRecTextBlock / kRecBamGroup;
+
+// rec_text_write_kernel's shape with kRecBamGroup lanes per record: the blocks are not dword-aligned
+// (names vary), so the dword two records share goes through the edge words here too
+__global__ __launch_bounds__(kRecTextBlock) void bam_write_kernel(RecText t, const int64_t *bam_off, uint8_t *bam)
+{
+    __shared__ uint32_t win[kBamPerBlock][kWin / 4];
+    __shared__ uint32_t edge[kBamPerBlock + 1];
+    const int g = threadIdx.x / kRecBamGroup, lane = threadIdx.x % kRecBamGroup;
+    const int r0 = blockIdx.x * kBamPerBlock;
+    const int nvalid = min(kBamPerBlock, t.n_rec - r0);
+    if (threadIdx.x <= kBamPerBlock) edge[threadIdx.x] = 0;
+    __syncthreads();
+    if (g < nvalid) {
+        const int64_t o = bam_off[r0 + g];
+        LdsSink<kRecBamGroup> s;
+        s.win = (uint8_t *)win[g];
+        s.out = (uint32_t *)bam;
+        s.head = (uint8_t *)&edge[g];
+        s.tail = (uint8_t *)&edge[g + 1];
+        s.gbase = o & ~(int64_t)3;
+        s.fill = s.k0 = (int)(o & 3);
+        s.lane = lane;
+        s.head_pending = s.k0 != 0;
+        emit_bam(s, t, r0 + g, (uint32_t)(bam_off[r0 + g + 1] - o - 4));
+        s.finish();
+    }
+    __syncthreads();
+    // the dwords two records share; the block's own two ends byte by byte
+    const int b = threadIdx.x;
+    if (b <= nvalid) {
+        const int64_t o = bam_off[r0 + b];
+        const int k = (int)(o & 3);
+        if (k) {
+            const uint8_t *e = (const uint8_t *)&edge[b];
+            uint8_t *at = bam + (o & ~(int64_t)3);
+            if (b > 0 && b < nvalid) *(uint32_t *)at = edge[b];
+            else if (b == 0) for (int j = k; j < 4; ++j) at[j] = e[j];
+            else for (int j = 0; j < k; ++j) at[j] = e[j];
+        }
+    }
+}
+
 }  // namespace
+
+hipError_t launch_rec_bam_len(const RecText &t, int64_t *len, int32_t *meta, hipStream_t s)
+{
+    bam_len_kernel<<<grid_for((int64_t)t.n_rec + 1, kBlock), kBlock, 0, s>>>(t, len, meta);
+    return hipGetLastError();
+}
+
+hipError_t launch_rec_bam_write(const RecText &t, const int64_t *bam_off, uint8_t *bam, hipStream_t s)
+{
+    if (t.n_rec == 0) return hipSuccess;
+    bam_write_kernel<<<grid_for(t.n_rec, kBamPerBlock), kRecTextBlock, 0, s>>>(t, bam_off, bam);
+    return hipGetLastError();
+}
 
 hipError_t launch_rec_count(const RecParams &p, const RecLists &l, int32_t *nrec, int32_t *naln, int32_t *meta,
                             hipStream_t s)

@@ -3,6 +3,7 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 #include "../../include/bsw_rec.h"
+#include "../../include/bsw_bam.h"
 #include "bsw_contig_seg.h"
 
 namespace bsw {
@@ -45,6 +46,11 @@ constexpr int kRecErr = 0, kRecUnmapped = 1, kRecSupp = 2, kRecXa = 3, kRecOverf
 constexpr int kRecTextGroup = BSW_REC_TEXT_GROUP;       // lanes per record in the write kernel
 constexpr int kRecTextBlock = 256;      // its block: 256 / kRecTextGroup records, consecutive in the text
 static_assert(kRecTextGroup >= 4 && 64 % kRecTextGroup == 0, "a group is lanes of one wave, four of them take the edge bytes");
+#ifndef BSW_REC_BAM_GROUP
+#define BSW_REC_BAM_GROUP 4             // measured: 4 / 8 / 16 lanes gave write_ms 1.02 / 1.15 / 1.58 (`make abrec AB_FLAGS=-DBSW_REC_BAM_GROUP=N`)
+#endif
+constexpr int kRecBamGroup = BSW_REC_BAM_GROUP;         // lanes per record in the BAM write kernel, same block
+static_assert(kRecBamGroup >= 4 && 64 % kRecBamGroup == 0, "a group is lanes of one wave, four of them take the edge bytes");
 
 // One work item per read.  Count pass: nrec[r] and naln[r] (nrec[n_reads] = naln[n_reads] = 0),
 // validation into meta[kRecErr].  Fill pass (rec_first / aln_first = their exclusive scans): the
@@ -64,5 +70,10 @@ hipError_t launch_rec_finish(const RecLists &l, const ContigView &ctg, const int
 hipError_t launch_rec_text_len(const RecText &t, int64_t *len, int32_t *meta, hipStream_t s);
 // the lines at text + text_off[i]; text is 4-byte aligned
 hipError_t launch_rec_text_write(const RecText &t, const int64_t *text_off, uint8_t *text, hipStream_t s);
+// the same two passes for BAM alignment blocks (include/bsw_bam.h): len[i] = the bytes of record i's block,
+// validation (the text's and what the binary fields cannot hold) into meta[kRecErr]; the blocks at
+// bam + bam_off[i], bam 4-byte aligned, no byte at or behind bam + bam_off[n_rec] written
+hipError_t launch_rec_bam_len(const RecText &t, int64_t *len, int32_t *meta, hipStream_t s);
+hipError_t launch_rec_bam_write(const RecText &t, const int64_t *bam_off, uint8_t *bam, hipStream_t s);
 
 }  // namespace bsw

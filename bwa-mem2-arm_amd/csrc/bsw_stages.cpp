@@ -1210,16 +1210,16 @@ static int records_device(bsw_ctx_t *ctx, DeviceCtx &dc, Slot &s, hipStream_t st
     return h_meta[kRecRejected] || h_meta[kRecOverflow] ? BSW_E_RANGE : BSW_OK;
 }
 
-struct TextIo {                         // call 2's outputs
-    uint8_t *text;
-    int64_t *text_off;
+struct OutIo {                          // call 2's outputs, either form: SAM lines or BAM blocks
+    uint8_t *out;
+    int64_t *off;
 };
 
-static int sam_text_check_args(const bsw_rec_opt_t *opt, int32_t n_rec, int32_t n_aln, int32_t n_reads, int32_t paired,
-                               int32_t cigar_stride, int32_t md_stride, int64_t text_cap)
+static int rec_out_check_args(const bsw_rec_opt_t *opt, int32_t n_rec, int32_t n_aln, int32_t n_reads, int32_t paired,
+                              int32_t cigar_stride, int32_t md_stride, int64_t out_cap)
 {
     if (const int rc = rec_check_opt(opt)) return rc;
-    if (n_rec < 0 || n_aln < 0 || n_reads < 0 || text_cap < 0 || cigar_stride < 1 || md_stride < 1) return BSW_E_INVAL;
+    if (n_rec < 0 || n_aln < 0 || n_reads < 0 || out_cap < 0 || cigar_stride < 1 || md_stride < 1) return BSW_E_INVAL;
     return paired && (n_reads & 1) ? BSW_E_INVAL : BSW_OK;
 }
 
@@ -1238,10 +1238,15 @@ static void make_rec_text(const DeviceCtx &dc, const bsw_rec_opt_t &opt, int32_t
     t.rname_len = (int32_t)strnlen(opt.rname, sizeof(opt.rname));
 }
 
-// lengths -> scan -> one readback of the total -> write
-static int sam_text_device(Slot &s, hipStream_t st, const bsw_rec_opt_t &opt, RecText &t, const TextIo &io,
-                           int64_t text_cap, int64_t *n_bytes, float &text_ms)
+// call 2 has two output forms on the same arrays: SAM lines (bsw_rec.h) and BAM alignment blocks (bsw_bam.h)
+enum class RecForm { Text, Bam };
+
+// lengths -> scan -> one readback (error word + total) -> write; the time of the first half onto
+// len_ms, of the write kernel onto write_ms (the text form reports their sum as text_ms)
+static int rec_out_device(RecForm form, Slot &s, hipStream_t st, const bsw_rec_opt_t &opt, RecText &t, const OutIo &io,
+                          int64_t out_cap, int64_t *n_bytes, float &len_ms, float &write_ms)
 {
+    const bool bam = form == RecForm::Bam;
     *n_bytes = 0;
     size_t scan_bytes = 0;
     BSW_TRY(launch_scan64(nullptr, &scan_bytes, nullptr, nullptr, t.n_rec, st));
@@ -1258,30 +1263,35 @@ static int sam_text_device(Slot &s, hipStream_t st, const bsw_rec_opt_t &opt, Re
     BSW_TRY(hipMemcpyAsync(s.d_rmeta + kRecMetaWords, h_name, sizeof(opt.rname), hipMemcpyHostToDevice, st));
     t.rname = (const uint8_t *)(s.d_rmeta + kRecMetaWords);
     BSW_TRY(tm.begin());
-    BSW_TRY(launch_rec_text_len(t, s.d_rlen, s.d_rmeta, st));
-    BSW_TRY(launch_scan64(s.d_tmp, &scan_bytes, s.d_rlen, io.text_off, t.n_rec, st));
+    BSW_TRY(bam ? launch_rec_bam_len(t, s.d_rlen, s.d_rmeta, st) : launch_rec_text_len(t, s.d_rlen, s.d_rmeta, st));
+    BSW_TRY(launch_scan64(s.d_tmp, &scan_bytes, s.d_rlen, io.off, t.n_rec, st));
     BSW_TRY(tm.end());
     BSW_TRY(hipMemcpyAsync(s.h_meta, s.d_rmeta, kRecMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    BSW_TRY(hipMemcpyAsync(h_tot, io.text_off + t.n_rec, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_tot, io.off + t.n_rec, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     BSW_TRY(hipStreamSynchronize(st));
-    BSW_TRY(tm.add(text_ms));
+    BSW_TRY(tm.add(len_ms));
     if (s.h_meta[kRecErr]) return BSW_E_RANGE;
     *n_bytes = *h_tot;
-    if (*n_bytes > text_cap) return BSW_E_RANGE;
+    if (*n_bytes > out_cap) return BSW_E_RANGE;
     BSW_TRY(tm.begin());
-    BSW_TRY(launch_rec_text_write(t, io.text_off, io.text, st));
+    BSW_TRY(bam ? launch_rec_bam_write(t, io.off, io.out, st) : launch_rec_text_write(t, io.off, io.out, st));
     BSW_TRY(tm.end());
     BSW_TRY(hipStreamSynchronize(st));
-    BSW_TRY(tm.add(text_ms));
+    BSW_TRY(tm.add(write_ms));
     return BSW_OK;
 }
 
-// the text call's counters onto the last stats, whose other fields are the last records call's
-static void put_text_stats(bsw_ctx_t *ctx, int64_t n_bytes, float text_ms)
+// the text call's counters onto the last stats, whose other fields are the last records call's; the
+// BAM call's are a struct of their own
+static void put_out_stats(RecForm form, bsw_ctx_t *ctx, int32_t n_rec, int64_t n_bytes, float len_ms, float write_ms)
 {
     std::lock_guard<std::mutex> g(ctx->stats_mu);
-    ctx->rec_last.n_bytes = n_bytes;
-    ctx->rec_last.text_ms = text_ms;
+    if (form == RecForm::Bam) {
+        ctx->bam_last = bsw_bam_stats_t{n_rec, 0, n_bytes, len_ms, write_ms};
+    } else {
+        ctx->rec_last.n_bytes = n_bytes;
+        ctx->rec_last.text_ms = len_ms + write_ms;
+    }
 }
 
 }  // namespace bsw
@@ -1395,19 +1405,20 @@ int bsw_records(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const uint8_t *reads, 
     return rc;
 }
 
-int bsw_sam_text_resident(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *d_recs,
-                          const int32_t *d_rec_first, int32_t n_rec, const bsw_aln_t *d_aln,
-                          const uint32_t *d_cigar, int32_t cigar_stride, const uint8_t *d_md, int32_t md_stride,
-                          int32_t n_aln, const uint8_t *d_reads, const int64_t *d_read_off,
-                          const int32_t *d_read_len, int32_t n_reads, const uint8_t *d_names,
-                          const int64_t *d_name_off, const uint8_t *d_quals, int32_t paired, uint8_t *d_text,
-                          int64_t *d_text_off, int64_t text_cap, int64_t *n_bytes, void *stream)
+// call 2 in either form, every array in HBM
+static int rec_out_resident(bsw::RecForm form, bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *d_recs,
+                            const int32_t *d_rec_first, int32_t n_rec, const bsw_aln_t *d_aln,
+                            const uint32_t *d_cigar, int32_t cigar_stride, const uint8_t *d_md, int32_t md_stride,
+                            int32_t n_aln, const uint8_t *d_reads, const int64_t *d_read_off,
+                            const int32_t *d_read_len, int32_t n_reads, const uint8_t *d_names,
+                            const int64_t *d_name_off, const uint8_t *d_quals, int32_t paired, uint8_t *d_out,
+                            int64_t *d_out_off, int64_t out_cap, int64_t *n_bytes, void *stream)
 {
-    if (const int rc = bsw::sam_text_check_args(opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, text_cap))
+    if (const int rc = bsw::rec_out_check_args(opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, out_cap))
         return rc;
-    if (!ctx || !n_bytes || !d_text_off || !d_name_off || (n_rec > 0 && (!d_recs || !d_rec_first)) ||
+    if (!ctx || !n_bytes || !d_out_off || !d_name_off || (n_rec > 0 && (!d_recs || !d_rec_first)) ||
         (n_aln > 0 && (!d_aln || !d_cigar || !d_md)) || (n_reads > 0 && (!d_reads || !d_read_off || !d_read_len || !d_names)) ||
-        (text_cap > 0 && !d_text) || ((uintptr_t)d_text & 3))
+        (out_cap > 0 && !d_out) || ((uintptr_t)d_out & 3))
         return BSW_E_INVAL;
     bsw::DeviceCtx &dc = *ctx->devs[0];
     std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the contig table stays put
@@ -1417,28 +1428,29 @@ int bsw_sam_text_resident(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_re
     t.reads = d_reads; t.names = d_names; t.quals = d_quals;
     t.read_off = d_read_off; t.name_off = d_name_off; t.read_len = d_read_len;
     bsw::make_rec_text(dc, *opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, t);
-    float text_ms = 0.f;
+    float len_ms = 0.f, write_ms = 0.f;
     const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
         hipStream_t st = stream ? (hipStream_t)stream : s.stream;
-        return bsw::sam_text_device(s, st, *opt, t, {d_text, d_text_off}, text_cap, n_bytes, text_ms);
+        return bsw::rec_out_device(form, s, st, *opt, t, {d_out, d_out_off}, out_cap, n_bytes, len_ms, write_ms);
     });
     if (rc) return rc;
-    bsw::put_text_stats(ctx, *n_bytes, text_ms);
+    bsw::put_out_stats(form, ctx, n_rec, *n_bytes, len_ms, write_ms);
     return BSW_OK;
 }
 
-int bsw_sam_text(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *recs, const int32_t *rec_first,
-                 int32_t n_rec, const bsw_aln_t *aln, const uint32_t *cigar, int32_t cigar_stride,
-                 const uint8_t *md, int32_t md_stride, int32_t n_aln, const uint8_t *reads,
-                 const int64_t *read_off, const int32_t *read_len, int32_t n_reads, const uint8_t *names,
-                 const int64_t *name_off, const uint8_t *quals, int32_t paired, uint8_t *text, int64_t *text_off,
-                 int64_t text_cap, int64_t *n_bytes)
+// the same with host arrays
+static int rec_out_host(bsw::RecForm form, bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *recs,
+                        const int32_t *rec_first, int32_t n_rec, const bsw_aln_t *aln, const uint32_t *cigar,
+                        int32_t cigar_stride, const uint8_t *md, int32_t md_stride, int32_t n_aln, const uint8_t *reads,
+                        const int64_t *read_off, const int32_t *read_len, int32_t n_reads, const uint8_t *names,
+                        const int64_t *name_off, const uint8_t *quals, int32_t paired, uint8_t *out, int64_t *out_off,
+                        int64_t out_cap, int64_t *n_bytes)
 {
-    if (const int rc = bsw::sam_text_check_args(opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, text_cap))
+    if (const int rc = bsw::rec_out_check_args(opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, out_cap))
         return rc;
-    if (!ctx || !n_bytes || !text_off || !name_off || (n_rec > 0 && (!recs || !rec_first)) ||
+    if (!ctx || !n_bytes || !out_off || !name_off || (n_rec > 0 && (!recs || !rec_first)) ||
         (n_aln > 0 && (!aln || !cigar || !md)) || (n_reads > 0 && (!reads || !read_off || !read_len || !names)) ||
-        (text_cap > 0 && !text))
+        (out_cap > 0 && !out))
         return BSW_E_INVAL;
     int64_t rbytes;
     if (const int rc = bsw::reads_extent(read_off, read_len, n_reads, &rbytes)) return rc;
@@ -1461,32 +1473,140 @@ int bsw_sam_text(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *recs
     const auto d_names = io.in(names, (size_t)name_off[nn]);
     const auto d_name_off = io.in(name_off, nn + 1);
     const auto d_quals = io.in_opt(quals, (size_t)rbytes);
-    const auto d_text = io.out(text, (size_t)text_cap);
-    const auto d_text_off = io.out(text_off, nc + 1);
+    const auto d_out = io.out(out, (size_t)out_cap);
+    const auto d_out_off = io.out(out_off, nc + 1);
     bsw::RecText t{};
     bsw::make_rec_text(dc, *opt, n_rec, n_aln, n_reads, paired, cigar_stride, md_stride, t);
-    float text_ms = 0.f;
+    float len_ms = 0.f, write_ms = 0.f;
     const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
         BSW_TRY(io.stage(s));
         t.recs = d_recs; t.rec_first = d_rec_first; t.aln = d_aln; t.cigar = d_cigar; t.md = d_md;
         t.reads = d_reads; t.names = d_names; t.quals = d_quals;
         t.read_off = d_read_off; t.name_off = d_name_off; t.read_len = d_read_len;
-        const int r = bsw::sam_text_device(s, s.stream, *opt, t, {d_text, d_text_off}, text_cap, n_bytes, text_ms);
-        if (r == BSW_E_RANGE && *n_bytes > text_cap) {     // (d_text_off is still written)
-            BSW_TRY(io.back(d_text_off));
+        const int r = bsw::rec_out_device(form, s, s.stream, *opt, t, {d_out, d_out_off}, out_cap, n_bytes, len_ms,
+                                          write_ms);
+        if (r == BSW_E_RANGE && *n_bytes > out_cap) {      // (d_out_off is still written)
+            BSW_TRY(io.back(d_out_off));
             BSW_TRY(hipStreamSynchronize(s.stream));
         }
         if (r) return r;
-        BSW_TRY(io.back(d_text, (size_t)*n_bytes));
-        BSW_TRY(io.back(d_text_off));
+        BSW_TRY(io.back(d_out, (size_t)*n_bytes));
+        BSW_TRY(io.back(d_out_off));
         BSW_TRY(hipStreamSynchronize(s.stream));
         return BSW_OK;
     });
     if (rc) return rc;
-    bsw::put_text_stats(ctx, *n_bytes, text_ms);
+    bsw::put_out_stats(form, ctx, n_rec, *n_bytes, len_ms, write_ms);
     return BSW_OK;
 }
 
+int bsw_sam_text_resident(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *d_recs,
+                          const int32_t *d_rec_first, int32_t n_rec, const bsw_aln_t *d_aln,
+                          const uint32_t *d_cigar, int32_t cigar_stride, const uint8_t *d_md, int32_t md_stride,
+                          int32_t n_aln, const uint8_t *d_reads, const int64_t *d_read_off,
+                          const int32_t *d_read_len, int32_t n_reads, const uint8_t *d_names,
+                          const int64_t *d_name_off, const uint8_t *d_quals, int32_t paired, uint8_t *d_text,
+                          int64_t *d_text_off, int64_t text_cap, int64_t *n_bytes, void *stream)
+{
+    return rec_out_resident(bsw::RecForm::Text, ctx, opt, d_recs, d_rec_first, n_rec, d_aln, d_cigar, cigar_stride, d_md,
+                            md_stride, n_aln, d_reads, d_read_off, d_read_len, n_reads, d_names, d_name_off, d_quals, paired,
+                            d_text, d_text_off, text_cap, n_bytes, stream);
+}
+
+int bsw_sam_text(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *recs, const int32_t *rec_first,
+                 int32_t n_rec, const bsw_aln_t *aln, const uint32_t *cigar, int32_t cigar_stride,
+                 const uint8_t *md, int32_t md_stride, int32_t n_aln, const uint8_t *reads,
+                 const int64_t *read_off, const int32_t *read_len, int32_t n_reads, const uint8_t *names,
+                 const int64_t *name_off, const uint8_t *quals, int32_t paired, uint8_t *text, int64_t *text_off,
+                 int64_t text_cap, int64_t *n_bytes)
+{
+    return rec_out_host(bsw::RecForm::Text, ctx, opt, recs, rec_first, n_rec, aln, cigar, cigar_stride, md, md_stride, n_aln,
+                        reads, read_off, read_len, n_reads, names, name_off, quals, paired, text, text_off, text_cap, n_bytes);
+}
+
 int bsw_rec_last_stats(bsw_ctx_t *ctx, bsw_rec_stats_t *out) { return bsw::get_stats(ctx, &bsw_ctx::rec_last, out); }
+
+// ---------------------------------------------------------------- BAM (include/bsw_bam.h)
+int bsw_bam_records_resident(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *d_recs,
+                             const int32_t *d_rec_first, int32_t n_rec, const bsw_aln_t *d_aln,
+                             const uint32_t *d_cigar, int32_t cigar_stride, const uint8_t *d_md, int32_t md_stride,
+                             int32_t n_aln, const uint8_t *d_reads, const int64_t *d_read_off,
+                             const int32_t *d_read_len, int32_t n_reads, const uint8_t *d_names,
+                             const int64_t *d_name_off, const uint8_t *d_quals, int32_t paired, uint8_t *d_bam,
+                             int64_t *d_bam_off, int64_t bam_cap, int64_t *n_bytes, void *stream)
+{
+    return rec_out_resident(bsw::RecForm::Bam, ctx, opt, d_recs, d_rec_first, n_rec, d_aln, d_cigar, cigar_stride, d_md,
+                            md_stride, n_aln, d_reads, d_read_off, d_read_len, n_reads, d_names, d_name_off, d_quals, paired,
+                            d_bam, d_bam_off, bam_cap, n_bytes, stream);
+}
+
+int bsw_bam_records(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const bsw_rec_t *recs, const int32_t *rec_first,
+                    int32_t n_rec, const bsw_aln_t *aln, const uint32_t *cigar, int32_t cigar_stride,
+                    const uint8_t *md, int32_t md_stride, int32_t n_aln, const uint8_t *reads,
+                    const int64_t *read_off, const int32_t *read_len, int32_t n_reads, const uint8_t *names,
+                    const int64_t *name_off, const uint8_t *quals, int32_t paired, uint8_t *bam, int64_t *bam_off,
+                    int64_t bam_cap, int64_t *n_bytes)
+{
+    return rec_out_host(bsw::RecForm::Bam, ctx, opt, recs, rec_first, n_rec, aln, cigar, cigar_stride, md, md_stride, n_aln,
+                        reads, read_off, read_len, n_reads, names, name_off, quals, paired, bam, bam_off, bam_cap, n_bytes);
+}
+
+int bsw_bam_header(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const char *sam_text, int32_t l_text, uint8_t *out,
+                   int64_t cap, int64_t *n_bytes)
+{
+    if (const int rc = bsw::rec_check_opt(opt)) return rc;
+    if (!ctx || !n_bytes || l_text < 0 || cap < 0 || (l_text > 0 && !sam_text) || (cap > 0 && !out)) return BSW_E_INVAL;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the contig table stays put
+    if (!bsw::text_ctg_ok(dc, *opt)) return BSW_E_INVAL;
+    const int32_t n_ref = dc.n_ctg > 0 ? dc.n_ctg : 1;
+    // one reference: its name's bytes and its length
+    auto ref = [&](int32_t k, const uint8_t *&name, int32_t &l_name, int64_t &l_ref) {
+        if (dc.n_ctg > 0) {
+            name = dc.h_ctg_names.data() + dc.h_ctg_name_off[k];
+            l_name = dc.h_ctg_name_off[k + 1] - dc.h_ctg_name_off[k];
+            l_ref = dc.h_ctg_off[k + 1] - dc.h_ctg_off[k];
+        } else {
+            name = (const uint8_t *)opt->rname;
+            l_name = (int32_t)strnlen(opt->rname, sizeof(opt->rname));
+            l_ref = opt->l_pac;
+        }
+    };
+    int64_t need = 4 + 4 + (int64_t)l_text + 4;
+    for (int32_t k = 0; k < n_ref; ++k) {
+        const uint8_t *name;
+        int32_t l_name;
+        int64_t l_ref;
+        ref(k, name, l_name, l_ref);
+        if (l_ref > INT32_MAX) return BSW_E_RANGE;
+        need += 4 + l_name + 1 + 4;
+    }
+    *n_bytes = need;
+    if (cap < need) return BSW_E_RANGE;
+    uint8_t *w = out;
+    auto put32 = [&](int32_t v) {
+        for (int b = 0; b < 4; ++b) *w++ = (uint8_t)((uint32_t)v >> (8 * b));
+    };
+    memcpy(w, "BAM\1", 4);
+    w += 4;
+    put32(l_text);
+    if (l_text) memcpy(w, sam_text, (size_t)l_text);
+    w += l_text;
+    put32(n_ref);
+    for (int32_t k = 0; k < n_ref; ++k) {
+        const uint8_t *name;
+        int32_t l_name;
+        int64_t l_ref;
+        ref(k, name, l_name, l_ref);
+        put32(l_name + 1);
+        memcpy(w, name, (size_t)l_name);
+        w += l_name;
+        *w++ = 0;
+        put32((int32_t)l_ref);
+    }
+    return BSW_OK;
+}
+
+int bsw_bam_last_stats(bsw_ctx_t *ctx, bsw_bam_stats_t *out) { return bsw::get_stats(ctx, &bsw_ctx::bam_last, out); }
 
 }  // extern "C"

@@ -53,6 +53,8 @@ REC_SYMBOLS = ("bsw_rec_opt_default", "bsw_records", "bsw_records_resident", "bs
                "bsw_rec_last_stats")
 # include/bsw_contigs.h (additive to ABI 8: BSW_CONTIGS_API)
 CONTIGS_SYMBOLS = ("bsw_set_contigs", "bsw_fmi_set_contigs")
+# include/bsw_bam.h (additive likewise)
+BAM_SYMBOLS = ("bsw_bam_records", "bsw_bam_records_resident", "bsw_bam_header", "bsw_bam_last_stats")
 CONTIG_MAX_NAME = 63
 
 # include/bsw.h engine options (bsw_set_option)
@@ -249,6 +251,12 @@ def hip_lib():
         L.bsw_sam_text_resident.argtypes = L.bsw_sam_text.argtypes + [P]
         L.bsw_rec_last_stats.argtypes = [P, P]
         for f in REC_SYMBOLS[1:]:
+            getattr(L, f).restype = ctypes.c_int
+        L.bsw_bam_records.argtypes = L.bsw_sam_text.argtypes
+        L.bsw_bam_records_resident.argtypes = L.bsw_sam_text_resident.argtypes
+        L.bsw_bam_header.argtypes = [P, P, P, i32, P, i64, P]
+        L.bsw_bam_last_stats.argtypes = [P, P]
+        for f in BAM_SYMBOLS:
             getattr(L, f).restype = ctypes.c_int
         L.bsw_set_contigs.argtypes = [P, i32, P, ctypes.POINTER(ctypes.c_char_p)]
         L.bsw_set_contigs.restype = ctypes.c_int
@@ -1199,6 +1207,86 @@ def sam_text_resident(engine, d_recs: int, d_rec_first: int, n_rec: int, d_aln: 
 def rec_last_stats(engine) -> RecStats:
     st = RecStats()
     _check(hip_lib().bsw_rec_last_stats(engine._ctx, ctypes.byref(st)))
+    return st
+
+
+# ---------------------------------------------------------------- BAM records (bsw_bam.h)
+class BamStats(ctypes.Structure):
+    _fields_ = [("n_rec", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_bytes", ctypes.c_int64),
+                ("len_ms", ctypes.c_float), ("write_ms", ctypes.c_float)]
+
+
+def bam_records(engine, recs, rec_first, aln, cigar, md, reads, read_off, read_len, names, quals, opt: RecOpt,
+                paired: bool, bam_cap: int | None = None):
+    """bsw_bam_records (host arrays): sam_text's arguments -> (the BAM alignment blocks as bytes, bam_off int64
+    [n_rec + 1]).  A bam_cap below what is needed raises BswError with .needed and .bam_off set."""
+    recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+    rec_first = np.ascontiguousarray(rec_first, dtype=np.int32)
+    aln = np.ascontiguousarray(aln, dtype=ALN_DTYPE)
+    cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+    md = np.ascontiguousarray(md, dtype=np.uint8)
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+    read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+    quals = None if quals is None else np.ascontiguousarray(quals, dtype=np.uint8)
+    nm, nm_off = _names_host(names)
+    n_reads = len(read_len)
+    assert len(names) == (n_reads // 2 if paired else n_reads) and (quals is None or len(quals) == len(reads))
+    cs = cigar.shape[1] if cigar.ndim == 2 else 1
+    ms = md.shape[1] if md.ndim == 2 else 1
+    if bam_cap is None:         # the text's bound holds: no field is longer in binary than printed
+        per = 256 + 160 + 2 * int(read_len.max(initial=0)) + ms + 12 * cs * 16
+        bam_cap = per * max(len(recs), 1)
+    bam = np.zeros(max(bam_cap, 1), dtype=np.uint8)
+    bam_off = np.zeros(len(recs) + 1, dtype=np.int64)
+    n_bytes = ctypes.c_int64(-1)
+    rc = hip_lib().bsw_bam_records(engine._ctx, ctypes.byref(opt), _ptr(recs), _ptr(rec_first), len(recs), _ptr(aln),
+                                   _ptr(cigar), cs, _ptr(md), ms, len(aln), _ptr(reads), _ptr(read_off), _ptr(read_len),
+                                   n_reads, _ptr(nm), _ptr(nm_off), _ptr(quals) if quals is not None else None,
+                                   int(paired), _ptr(bam), _ptr(bam_off), bam_cap, ctypes.byref(n_bytes))
+    if rc != 0:
+        try:
+            _raise_needed(rc, n_bytes)
+        except BswError as e:
+            e.bam_off = bam_off
+            raise
+    return bam[:n_bytes.value].tobytes(), bam_off
+
+
+def bam_records_resident(engine, d_recs: int, d_rec_first: int, n_rec: int, d_aln: int, d_cigar: int, cigar_stride: int,
+                         d_md: int, md_stride: int, n_aln: int, d_reads: int, d_off: int, d_len: int, n_reads: int,
+                         d_names: int, d_name_off: int, d_quals: int, paired: bool, d_bam: int, d_bam_off: int,
+                         bam_cap: int, opt: RecOpt, stream: int = 0) -> int:
+    """bsw_bam_records_resident: every array a device pointer.  Returns n_bytes."""
+    V = ctypes.c_void_p
+    n_bytes = ctypes.c_int64(-1)
+    rc = hip_lib().bsw_bam_records_resident(engine._ctx, ctypes.byref(opt), V(d_recs or None), V(d_rec_first or None),
+                                            n_rec, V(d_aln or None), V(d_cigar or None), cigar_stride, V(d_md or None),
+                                            md_stride, n_aln, V(d_reads or None), V(d_off or None), V(d_len or None),
+                                            n_reads, V(d_names or None), V(d_name_off), V(d_quals or None), int(paired),
+                                            V(d_bam or None), V(d_bam_off), bam_cap, ctypes.byref(n_bytes),
+                                            V(stream or None))
+    if rc != 0:
+        _raise_needed(rc, n_bytes)
+    return n_bytes.value
+
+
+def bam_header(engine, opt: RecOpt, sam_text: bytes = b"") -> bytes:
+    """bsw_bam_header: the uncompressed header block for the engine's contig table (or opt.rname / opt.l_pac)"""
+    n_bytes = ctypes.c_int64(-1)
+    L = hip_lib()
+    rc = L.bsw_bam_header(engine._ctx, ctypes.byref(opt), sam_text or None, len(sam_text), None, 0, ctypes.byref(n_bytes))
+    if rc != -34 or n_bytes.value <= 0:
+        _check(rc)
+    out = np.zeros(n_bytes.value, dtype=np.uint8)
+    _check(L.bsw_bam_header(engine._ctx, ctypes.byref(opt), sam_text or None, len(sam_text), _ptr(out), len(out),
+                            ctypes.byref(n_bytes)))
+    return out[:n_bytes.value].tobytes()
+
+
+def bam_last_stats(engine) -> BamStats:
+    st = BamStats()
+    _check(hip_lib().bsw_bam_last_stats(engine._ctx, ctypes.byref(st)))
     return st
 
 

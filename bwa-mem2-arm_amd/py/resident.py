@@ -1,6 +1,6 @@
 """ResidentBatch: the device arrays of one batch of reads and the resident stage chain over them,
 
-    seeds -> chain2aln -> select -> pe_stat -> matesw -> pe_pair -> reg2aln / records -> sam_text
+    seeds -> chain2aln -> select -> pe_stat -> matesw -> pe_pair -> reg2aln / records -> sam_text / bam_records
 
 Plumbing for tests and tools, like bsw.py: every stage method is one bsw.*_resident call on the buffers the
 stage before left in HBM.  Importing this module loads no library and touches no device.
@@ -17,7 +17,7 @@ import hiprt
 
 # buffer name -> (dtype, row shape: the names of the strides a row has, the count that trims it).
 # Every allocation is sized from this table; a dotted name ("all.aln") has the layout of its last part
-# and counts of its own ("all.aln").
+# and counts of its own ("all.aln").  ("bam" / "bam_off" are not here: BAM_LAYOUT below; _row reads both.)
 LAYOUT = {
     "reads": (np.uint8, (), "reads"), "quals": (np.uint8, (), "reads"),
     "off": (np.int64, (), "n_reads"), "lens": (np.int32, (), "n_reads"), "frac_rep": (np.float32, (), "n_reads"),
@@ -35,6 +35,9 @@ LAYOUT = {
     "names": (np.uint8, (), "names"), "name_off": (np.int64, (), "name_off"),
     "text": (np.uint8, (), "text"), "text_off": (np.int64, (), "text_off"),
 }
+# the BAM form of the records (bsw_bam.h), rows of the same shape in a table of their own: LAYOUT's entries and
+# their item sizes are pinned one by one (tests/test_resident.py)
+BAM_LAYOUT = {"bam": (np.uint8, (), "bam"), "bam_off": (np.int64, (), "bam_off")}
 FIXED = ("reads", "n_reads", "first")           # counts the constructor sets for good
 # (regs, read, info, first) as the extension, the selection and the rescue leave them
 LISTS = {"c": ("regs", "sr", None, None), "s": ("sreg", "sread", "sinfo", "sfirst"), "m": ("mreg", "mread", "minfo", "mfirst")}
@@ -43,9 +46,9 @@ LISTS = {"c": ("regs", "sr", None, None), "s": ("sreg", "sread", "sinfo", "sfirs
 def _row(name):
     """(dtype, stride keys, count key) of a buffer name"""
     pre, dot, base = name.rpartition(".")
-    if base not in LAYOUT:
+    if base not in LAYOUT and base not in BAM_LAYOUT:
         raise ValueError(f"no buffer named '{name}'")
-    dtype, strides, key = LAYOUT[base]
+    dtype, strides, key = LAYOUT[base] if base in LAYOUT else BAM_LAYOUT[base]
     return np.dtype(dtype), tuple(pre + dot + s for s in strides), pre + dot + key
 
 
@@ -207,24 +210,24 @@ class ResidentBatch:
             self.buf["pairs"].ptr if paired else 0, *out, ropt)
         return self.n["recs"], self.n["aln"]
 
-    def sam_text(self, ropt, names, paired, cap=None) -> int:
-        """names: a list of bytes (one per read, or per pair), uploaded; None: the names of the call before.
-        cap=None: one call with no room that says how many bytes are needed, then the call with exactly those."""
-        self._have("sam_text", "recs", "rec_first", "aln", "cigar", "md")
+    def _records_out(self, stage, fn, out, ropt, names, paired, cap):
+        """call 2 in either form: fn = bsw.sam_text_resident into "text" / "text_off", or bsw.bam_records_resident
+        into "bam" / "bam_off" """
+        self._have(stage, "recs", "rec_first", "aln", "cigar", "md")
         if names is not None:
             if len(names) != (self.n_reads // 2 if paired else self.n_reads):
-                raise ValueError(f"sam_text: {len(names)} names for {self.n_reads} reads, paired={paired}")
+                raise ValueError(f"{stage}: {len(names)} names for {self.n_reads} reads, paired={paired}")
             nm, nm_off = bsw._names_host(names)
             self.put(names=nm, name_off=nm_off)
-        self._have("sam_text", "names", "name_off")
+        self._have(stage, "names", "name_off")
         n_rec = self.n["recs"]
-        toff = self.alloc("text_off", n_rec + 1).ptr
+        toff = self.alloc(out + "_off", n_rec + 1).ptr
 
         def call(d_text, cap):
-            return bsw.sam_text_resident(self.engine, *self._p("recs", "rec_first"), n_rec, *self._p("aln", "cigar"),
-                                         self.stride["cigar"], self.buf["md"].ptr, self.stride["md"], self.n["aln"],
-                                         *self._p("reads", "off", "lens"), self.n_reads, *self._p("names", "name_off"),
-                                         self.buf["quals"].ptr if "quals" in self.buf else 0, paired, d_text, toff, cap, ropt)
+            return fn(self.engine, *self._p("recs", "rec_first"), n_rec, *self._p("aln", "cigar"),
+                      self.stride["cigar"], self.buf["md"].ptr, self.stride["md"], self.n["aln"],
+                      *self._p("reads", "off", "lens"), self.n_reads, *self._p("names", "name_off"),
+                      self.buf["quals"].ptr if "quals" in self.buf else 0, paired, d_text, toff, cap, ropt)
 
         if cap is None:
             try:
@@ -233,5 +236,15 @@ class ResidentBatch:
                 if getattr(e, "needed", -1) <= 0:
                     raise
                 cap = e.needed
-        self.n["text"], self.n["text_off"] = call(self.alloc("text", cap).ptr, cap), n_rec + 1
-        return self.n["text"]
+        self.n[out], self.n[out + "_off"] = call(self.alloc(out, cap).ptr, cap), n_rec + 1
+        return self.n[out]
+
+    def sam_text(self, ropt, names, paired, cap=None) -> int:
+        """names: a list of bytes (one per read, or per pair), uploaded; None: the names of the call before.
+        cap=None: one call with no room that says how many bytes are needed, then the call with exactly those."""
+        return self._records_out("sam_text", bsw.sam_text_resident, "text", ropt, names, paired, cap)
+
+    def bam_records(self, ropt, names, paired, cap=None) -> int:
+        """the same records as BAM alignment blocks ("bam", "bam_off"); names=None reuses the uploaded names, so
+        text and BAM of one batch come from one upload"""
+        return self._records_out("bam_records", bsw.bam_records_resident, "bam", ropt, names, paired, cap)

@@ -10,9 +10,13 @@ in one process, --reps times each:
   (c) bsw_records_resident       -- aln_ms beside (b), helper_ms beside (a)
   (d) bsw_sam_text_resident      -- its kernels' bytes/s
   (e) a device-to-device hipMemcpy of the same byte count
-Prints one JSON line (and writes it to --out).  --only-new: just (c) and (d) (for a kernel trace).
+  (f) bsw_bam_records_resident   -- the same records as BAM alignment blocks (include/bsw_bam.h): len_ms, write_ms
+  (g) a device-to-device hipMemcpy of the BAM byte count
+Prints one JSON line (and writes it to --out).  --only-new: just (c) and (d) (for a kernel trace); --only-out: just
+(d) and (f) with their copies (the lanes-per-record sweeps, BSW_HIP_LIB names the library under test; a kernel trace).
 
     python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 7 --out profiles/rec/bench.json
+    python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 7 --only-out --out profiles/bam/bench.json
 """
 
 import argparse
@@ -43,6 +47,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--w", type=int, default=100)
     ap.add_argument("--only-new", action="store_true")
+    ap.add_argument("--only-out", action="store_true")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     log = lambda m: print(f"[rec_bench] {m}", file=sys.stderr, flush=True)  # noqa: E731
@@ -96,10 +101,66 @@ def main():
         hiprt.check(hiprt.rt().hipMemcpy(ctypes.c_void_p(d_copy.ptr), ctypes.c_void_p(b.buf["text"].ptr), n_bytes, hiprt.D2D))
         hiprt.synchronize()
 
+    # (--only-new stays (c) and (d): its kernel trace holds no BAM kernel)
+    bam_bytes = 0 if args.only_new else b.bam_records(ropt, None, True)     # (the names of the text call)
+    d_copy_bam = None if args.only_new else hiprt.DeviceBuffer(bam_bytes)
+
+    def bam():
+        return b.bam_records(ropt, None, True, cap=bam_bytes)
+
+    def copy_bam():
+        hiprt.check(hiprt.rt().hipMemcpy(ctypes.c_void_p(d_copy_bam.ptr), ctypes.c_void_p(b.buf["bam"].ptr), bam_bytes,
+                                         hiprt.D2D))
+        hiprt.synchronize()
+
     all_regions()
     text()
     copy()
+    if not args.only_new:
+        bam()
+        copy_bam()
     ta, tb, tc, td, te, b_ms, c_aln, c_help, d_ms = [], [], [], [], [], [], [], [], []
+    tf, tg, f_len, f_write = [], [], [], []
+
+    def out_legs():
+        td.append(timed(text))
+        d_ms.append(bsw.rec_last_stats(eng).text_ms)
+        te.append(timed(copy))
+        tf.append(timed(bam))
+        bs = bsw.bam_last_stats(eng)
+        f_len.append(bs.len_ms)
+        f_write.append(bs.write_ms)
+        tg.append(timed(copy_bam))
+
+    def out_json():
+        n_rec = bsw.bam_last_stats(eng).n_rec
+        f_ms = [x + y for x, y in zip(f_len, f_write)]
+        return {"records": n_rec, "text_bytes": int(n_bytes), "text_bytes_per_record": round(n_bytes / max(n_rec, 1), 1),
+                "bam_bytes": int(bam_bytes), "bam_bytes_per_record": round(bam_bytes / max(n_rec, 1), 1),
+                "d_text_s": spread(td), "d_text_kernel_ms": spread(d_ms),
+                "d_text_kernels_gb_per_s": round(n_bytes / (spread(d_ms)["median"] * 1e-3) / 1e9, 1),
+                "e_memcpy_d2d_s": spread(te), "e_memcpy_d2d_gb_per_s": round(n_bytes / spread(te)["median"] / 1e9, 1),
+                "f_bam_s": spread(tf), "f_bam_len_ms": spread(f_len), "f_bam_write_ms": spread(f_write),
+                "f_bam_kernel_ms": spread(f_ms),
+                "f_bam_kernels_gb_per_s": round(bam_bytes / (spread(f_ms)["median"] * 1e-3) / 1e9, 1),
+                "f_bam_over_d_text_median": round(spread(f_ms)["median"] / spread(d_ms)["median"], 3),
+                "g_memcpy_d2d_bam_s": spread(tg), "g_memcpy_d2d_bam_gb_per_s": round(bam_bytes / spread(tg)["median"] / 1e9, 1)}
+
+    if args.only_out:
+        for _ in range(args.reps):
+            out_legs()
+        out = {"tool": "rec_bench", "legs": "out", "lib": os.path.basename(bsw.HIP_LIB), "pairs": n // 2, "reads": n,
+               "read_len": args.read_len, "ref_mb": args.ref_mb}
+        out.update(out_json())
+        line = json.dumps(out)
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        eng.close()
+        fmi.close()
+        return
     for _ in range(args.reps):
         if args.only_new:
             select()
@@ -114,10 +175,11 @@ def main():
         st = bsw.rec_last_stats(eng)
         c_aln.append(st.aln_ms)
         c_help.append(st.helper_ms)
-        td.append(timed(text))
-        d_ms.append(bsw.rec_last_stats(eng).text_ms)
-        if not args.only_new:
-            te.append(timed(copy))
+        if args.only_new:
+            td.append(timed(text))
+            d_ms.append(bsw.rec_last_stats(eng).text_ms)
+        else:
+            out_legs()
     st = bsw.rec_last_stats(eng)
     out = {"tool": "rec_bench", "pairs": n // 2, "reads": n, "read_len": args.read_len, "ref_mb": args.ref_mb,
            "regions": int(k), "records": st.n_rec, "unmapped": st.n_unmapped, "supplementary": st.n_supp, "xa_members": st.n_xa,
@@ -126,9 +188,9 @@ def main():
            "d_text_s": spread(td), "d_text_kernel_ms": spread(d_ms),
            "d_text_kernels_gb_per_s": round(n_bytes / (spread(d_ms)["median"] * 1e-3) / 1e9, 1)}
     if not args.only_new:
+        out.update(out_json())
         out.update({"a_regs_select_s": spread(ta), "b_reg2aln_all_regions_s": spread(tb),
-                    "b_reg2aln_all_regions_kernel_ms": spread(b_ms), "e_memcpy_d2d_s": spread(te),
-                    "e_memcpy_d2d_gb_per_s": round(n_bytes / spread(te)["median"] / 1e9, 1),
+                    "b_reg2aln_all_regions_kernel_ms": spread(b_ms),
                     "c_helper_over_a_median": round(spread(c_help)["median"] * 1e-3 / spread(ta)["median"], 3),
                     "c_aln_over_b_median": round(spread(c_aln)["median"] / spread(b_ms)["median"], 3)})
     line = json.dumps(out)
