@@ -2,14 +2,15 @@
 //
 //   plan_kernel   : per pair -> kernel class (lane QMAX bucket 32..160 | wide) + sort key
 //                   (class, qlen desc, tlen desc) so every wavefront gets 64 like-shaped pairs
-//   radix sort    : hipCUB DeviceRadixSort on the 27-bit key -> order[] (= sortPairsLen)
+//   radix sort    : the stable LSD radix sort of bsw_sort.hip over the bits of the 32-bit key that
+//                   vary in this batch (plan_kernel reduces them) -> order[] (= sortPairsLen)
 //   DP kernels    : one launch per non-empty class over its slice of order[]
 //   results       : written by the kernels straight into the SeqPair records
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <cstring>
 #include "bsw_engine.h"
+#include "bsw_sort.h"
 #include <emmintrin.h>
 
 namespace bsw {
@@ -21,7 +22,7 @@ constexpr int kWvClass0 = kWideClass + 1;   // wave-per-alignment kernel, 4 / 8 
 constexpr int kNumWvClasses = 3;
 constexpr int kWvCols[kNumWvClasses] = {4, 8, 16};
 constexpr int kNumClasses = kWvClass0 + kNumWvClasses;
-static_assert(kNumClasses <= kMetaCounts, "class counts");
+static_assert(kNumClasses <= kMetaKeyOr, "class counts, then the key mask's two words (bsw_sort.h)");
 static_assert(kNumLaneClasses <= kMetaRedoWords && kMetaRedo + kMetaRedoWords <= kMetaWords, "redo-list lengths");
 
 // Lifetime predictor for the sort key (scheduling only, results never depend on it): does the
@@ -102,6 +103,7 @@ __global__ void plan_kernel(const SeqPair *__restrict__ pairs, int32_t n, const 
     }
     if (c == kWideClass && wvc >= 0) c = wvc;
     if (misroute) c = 0;          // BSW_OPT_TEST_MISROUTE: the QMAX=32 lane kernel's guard must trip
+    uint32_t key = 0;
     if (valid) {
         if (c == kWideClass) atomicMax(maxq_wide, qlen);
         // (class, qlen desc, related first, tlen desc, h0 desc): like-shaped pairs share a
@@ -113,21 +115,26 @@ __global__ void plan_kernel(const SeqPair *__restrict__ pairs, int32_t n, const 
         // alike share a wavefront, so their band ends move together (C2 kernel 9.58 -> 8.60 ms vs
         // the h0-only order, BSW_SORTKEY=0)
         if (keymode == 0)
-            keys[i] = ((uint32_t)c << 28) | ((uint32_t)(255 - min(qlen, 255)) << 20) |
+            key = ((uint32_t)c << 28) | ((uint32_t)(255 - min(qlen, 255)) << 20) |
                       ((uint32_t)(1 - rel) << 19) | ((uint32_t)(2047 - min(tlen, 2047)) << 8) |
                       (uint32_t)(255 - min(max(p.h0, 0), 255));
         else
-            keys[i] = ((uint32_t)c << 28) | ((uint32_t)(255 - min(qlen, 255)) << 20) |
+            key = ((uint32_t)c << 28) | ((uint32_t)(255 - min(qlen, 255)) << 20) |
                       ((uint32_t)(1 - rel) << 19) | ((uint32_t)(63 - min(tlen >> 5, 63)) << 13) |
                       ((uint32_t)(31 - min(mt, 31)) << 8) | (uint32_t)(255 - min(max(p.h0, 0), 255));
+        keys[i] = key;
         vals[i] = i;
     }
     // class counts: wave ballots -> LDS per block -> one global add per block and class into the
     // block's slot (32 slots in separate 64-B lines; same-line atomics from every wave cost
     // ~10 ns each, 0.16-0.7 ms per 1M pairs)
+    // the key mask rides on the same two barriers: which key bits vary in this batch (bsw_sort.h)
     __shared__ int s_cnt[kNumClasses];
+    __shared__ uint32_t s_or[2];
     if (threadIdx.x < kNumClasses) s_cnt[threadIdx.x] = 0;
+    key_mask_zero(s_or);
     __syncthreads();
+    key_mask_add(key, valid, s_or);
     const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int k = 0; k < kNumClasses; ++k) {
@@ -137,6 +144,7 @@ __global__ void plan_kernel(const SeqPair *__restrict__ pairs, int32_t n, const 
     __syncthreads();
     if (threadIdx.x < kNumClasses && s_cnt[threadIdx.x])
         atomicAdd(&counts[(blockIdx.x % kMetaSpread) * kMetaCounts + threadIdx.x], s_cnt[threadIdx.x]);
+    key_mask_flush(s_or, counts);
 }
 
 void make_kparams(const bsw_params_t &p, KParams &kp)
@@ -193,20 +201,6 @@ hipError_t grow_sort(Slot &s, int32_t n)
     if ((e = s.d_keys2.reserve_exact(cap)) != hipSuccess) return e;
     if ((e = s.d_vals.reserve_exact(cap)) != hipSuccess) return e;
     return s.d_order.reserve_exact(cap);
-}
-
-// hipCUB's radix sort of the slot's (d_keys, d_vals) by the low key_bits bits -> d_order on `st`,
-// d_tmp grown to its temporary storage first; run = false: only that growth
-hipError_t sort_order(Slot &s, int32_t n, int key_bits, hipStream_t st, bool run)
-{
-    size_t tmp_bytes = 0;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, s.d_keys.p, s.d_keys2.p, s.d_vals.p,
-                                                      s.d_order.p, n, 0, key_bits, st);
-    if (e == hipSuccess) e = s.d_tmp.grow(tmp_bytes);
-    if (e == hipSuccess && run)
-        e = hipcub::DeviceRadixSort::SortPairs(s.d_tmp, tmp_bytes, s.d_keys.p, s.d_keys2.p, s.d_vals.p, s.d_order.p, n,
-                                               0, key_bits, st);
-    return e;
 }
 
 // The device pipeline on one slot's device; d_* are device pointers valid on `stream`, in two
@@ -304,7 +298,7 @@ int run_plan(const KParams &kp, Slot &s, const PlanCall &pc)
                        pc.d_pairs, n, kp, pc.w, pc_route, long_route, pc.d_ref, pc.d_qer, s.d_keys,
                        s.d_vals, d_counts, d_maxq, (int)kp.keymode, (int)kp.misroute);
     BSW_TRY(hipGetLastError());
-    BSW_TRY(sort_order(s, n, kKeyBits, stream));
+    BSW_TRY(sort_order(s, n, kKeyBits, stream, true, s.d_meta));
     BSW_TRY(hipMemcpyAsync(s.h_meta, s.d_meta, kMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     if (!s.evm) BSW_TRY(hipEventCreateWithFlags(&s.evm.p, hipEventDisableTiming));
     BSW_TRY(hipEventRecord(s.evm, stream));

@@ -2,6 +2,7 @@
 // call's Slot, the per-device slot pool and the context, plus the functions that cross the
 // engine's translation units:
 //   bsw_dispatch.hip : plan_kernel, run_plan / run_dp / run_device, finish_stats
+//   bsw_sort.hip     : sort_order, the batch-order radix sort (bsw_sort.h)
 //   bsw_pipeline.hip : staging kernels, the chunked host pipeline (host_shard), cross-call coalescing
 //   bsw_host.cpp     : contexts, recovery, mate / global / extension wrappers, options, the core C ABI
 //   bsw_stages.cpp   : the stages behind the extension (final alignments, region selection, the
@@ -384,10 +385,9 @@ static inline int with_slot(DeviceCtx &dc, F &&body)
     return rc;
 }
 
-// ---- bsw_dispatch.hip
+// ---- bsw_dispatch.hip (sort_order: bsw_sort.h)
 BSW_HIDDEN void make_kparams(const bsw_params_t &p, KParams &kp);
 BSW_HIDDEN hipError_t grow_sort(Slot &s, int32_t n);
-BSW_HIDDEN hipError_t sort_order(Slot &s, int32_t n, int key_bits, hipStream_t st, bool run = true);
 BSW_HIDDEN int ensure_pstream(Slot &s);
 BSW_HIDDEN int run_plan(const KParams &kp, Slot &s, const PlanCall &pc);
 BSW_HIDDEN int run_dp(const KParams &kp, Slot &s);

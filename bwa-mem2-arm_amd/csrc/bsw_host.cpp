@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 #include "bsw_engine.h"
+#include "bsw_sort.h"
 #include "bsw_mate_k.h"
 #include "bsw_global_k.h"
 #include "bsw_ext_k.h"

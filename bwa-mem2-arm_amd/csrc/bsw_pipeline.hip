@@ -10,6 +10,7 @@
 #include <thread>
 #include <vector>
 #include "bsw_engine.h"
+#include "bsw_sort.h"
 #include "bsw_pool.h"
 
 namespace bsw {

@@ -263,6 +263,9 @@ def hip_lib():
         L.bsw_fmi_set_contigs.argtypes = [P, i32, P]
         L.bsw_fmi_set_contigs.restype = ctypes.c_int
         L.bsw_get_scores_packed_device.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int, P, P]
+        if hasattr(L, "bsw_sort_order_device"):     # test hook, no part of the ABI (an older experiment build lacks it)
+            L.bsw_sort_order_device.argtypes = [P, P, ctypes.c_int32, ctypes.c_int, ctypes.c_int, P]
+            L.bsw_sort_order_device.restype = ctypes.c_int
         for f in ("bsw_create", "bsw_create_on", "bsw_get_scores", "bsw_get_scores_device", "bsw_last_stats",
                   "bsw_pack_batch", "bsw_get_scores_packed_device",
                   "bsw_abi_version", "bsw_extend_seeds", "bsw_ext_last_stats", "bswb_write",
@@ -353,6 +356,15 @@ class Engine:
         s = Stats()
         _check(hip_lib().bsw_last_stats(self._ctx, ctypes.byref(s)))
         return s
+
+    def sort_order(self, keys: np.ndarray, key_bits: int = 32, use_mask: bool = True) -> np.ndarray:
+        """bsw_sort_order_device (test hook, no part of the ABI): the engine's batch-order sort on its own --
+        the stable permutation that sorts `keys` by their low key_bits bits; use_mask: digits from the
+        varying bits only, as the planned path runs it."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        order = np.empty(len(keys), dtype=np.int32)
+        _check(hip_lib().bsw_sort_order_device(self._ctx, _ptr(keys), len(keys), key_bits, int(use_mask), _ptr(order)))
+        return order
 
 
 class Packed(ctypes.Structure):
