@@ -16,7 +16,7 @@ SYNTH    := $(LIBDIR)/libbsw_synth.so
 SHIMTEST := $(LIBDIR)/bsw_shim_example
 ORACLE   := oracle/liboracle.so
 
-HIP_HDRS := $(CSRC)/bsw_devcache.h $(CSRC)/bsw_pool.h $(CSRC)/bsw_kernels.h $(CSRC)/bsw_mate_k.h include/bsw_mate.h $(CSRC)/bsw_global_k.h include/bsw_global.h $(CSRC)/bsw_ext_k.h $(CSRC)/bsw_aln_k.h include/bsw_aln.h $(CSRC)/bsw_sel_k.h $(CSRC)/bsw_sel_dev.h include/bsw_sel.h $(CSRC)/bsw_pe_k.h include/bsw_pe.h $(CSRC)/bsw_matesw_k.h include/bsw_matesw.h $(CSRC)/bsw_rec_k.h include/bsw_rec.h include/bsw_bam.h $(CSRC)/bsw_wave.h $(CSRC)/bsw_formulas.h $(CSRC)/bsw_contig_seg.h include/bsw_contigs.h $(CSRC)/bsw_stage_k.h $(CSRC)/bsw_internal.h $(CSRC)/bsw_engine.h $(CSRC)/bsw_sort.h $(CSRC)/bsw_fmi_internal.h include/bsw.h include/bsw_seqpair.h include/bsw_ext.h include/bsw_batch.h include/bsw_fmi.h
+HIP_HDRS := $(CSRC)/bsw_devcache.h $(CSRC)/bsw_pool.h $(CSRC)/bsw_kernels.h $(CSRC)/bsw_mate_k.h include/bsw_mate.h $(CSRC)/bsw_global_k.h include/bsw_global.h $(CSRC)/bsw_ext_k.h $(CSRC)/bsw_aln_k.h include/bsw_aln.h $(CSRC)/bsw_sel_k.h $(CSRC)/bsw_sel_dev.h include/bsw_sel.h $(CSRC)/bsw_pe_k.h include/bsw_pe.h $(CSRC)/bsw_matesw_k.h include/bsw_matesw.h $(CSRC)/bsw_rec_k.h include/bsw_rec.h include/bsw_bam.h $(CSRC)/bsw_wave.h $(CSRC)/bsw_formulas.h $(CSRC)/bsw_contig_seg.h include/bsw_contigs.h $(CSRC)/bsw_stage_k.h $(CSRC)/bsw_internal.h $(CSRC)/bsw_stage_plan.h $(CSRC)/bsw_engine.h $(CSRC)/bsw_sort.h $(CSRC)/bsw_fmi_internal.h include/bsw.h include/bsw_seqpair.h include/bsw_ext.h include/bsw_batch.h include/bsw_fmi.h
 
 # the product's objects; the experiment libraries below are this list with one object swapped
 OBJS := $(addprefix $(LIBDIR)/,bsw_kernels.o bsw_pc.o bsw_wv.o bsw_gq.o bsw_mate.o bsw_global.o bsw_ext_dev.o bsw_aln.o bsw_sel.o bsw_pe.o bsw_matesw.o bsw_rec.o bsw_stage.o \
@@ -50,7 +50,7 @@ $(LIBDIR)/bsw_host.o $(LIBDIR)/bsw_stages.o: XHIP := -x hip
 $(LIBDIR)/bsw_ext.o: $(CSRC)/bsw_ext.cpp $(HIP_HDRS) | $(LIBDIR)
 	g++ -O3 -std=c++17 -fPIC -Wall -Iinclude -c $< -o $@
 
-$(LIBDIR)/bsw_pack.o: $(CSRC)/bsw_pack.cpp $(CSRC)/bsw_internal.h | $(LIBDIR)
+$(LIBDIR)/bsw_pack.o: $(CSRC)/bsw_pack.cpp $(CSRC)/bsw_internal.h $(CSRC)/bsw_stage_plan.h | $(LIBDIR)
 	g++ -O3 -std=c++17 -fPIC -Wall -Iinclude -c $< -o $@
 
 $(LIBDIR)/bsw_batch.o: $(CSRC)/bsw_batch.c include/bsw_batch.h include/bsw.h | $(LIBDIR)
@@ -103,7 +103,7 @@ ASAN_BIN   := $(ASAN_DIR)/asan_driver
 ASAN_C     := $(CSRC)/bsw_batch.c $(CSRC)/bsw_synth.c oracle/ksw_ext_ref.c oracle/ext_ref.c oracle/ksw_align_ref.c oracle/ksw_global_ref.c oracle/fmi_ref.c oracle/chain_ref.c
 ASAN_SSE   := oracle/bsw_sse41.c oracle/bsw_avx512.c
 ASAN_CXX   := $(ASAN_DIR)/asan_driver.cpp $(ASAN_DIR)/engine_stub.cpp $(CSRC)/bsw_ext.cpp $(CSRC)/bsw_pack.cpp
-$(ASAN_BIN): $(ASAN_C) $(ASAN_SSE) oracle/bsw_simd_batch.inc oracle/bsw_simd_common.h $(ASAN_CXX) $(CSRC)/bsw_internal.h $(CSRC)/bsw_formulas.h include/bsw_ext.h include/bsw_fmi.h
+$(ASAN_BIN): $(ASAN_C) $(ASAN_SSE) oracle/bsw_simd_batch.inc oracle/bsw_simd_common.h $(ASAN_CXX) $(CSRC)/bsw_internal.h $(CSRC)/bsw_stage_plan.h $(CSRC)/bsw_formulas.h include/bsw_ext.h include/bsw_fmi.h
 	mkdir -p $(ASAN_DIR)/obj
 	for f in $(ASAN_C); do gcc $(ASAN_FLAGS) -std=gnu11 -c $$f -o $(ASAN_DIR)/obj/$$(basename $$f).o || exit 1; done
 	for f in $(ASAN_SSE); do gcc $(ASAN_FLAGS) -std=gnu11 -msse4.1 -c $$f -o $(ASAN_DIR)/obj/$$(basename $$f).o || exit 1; done
@@ -128,4 +128,10 @@ asan-suite: $(ASAN_ORACLE) $(ASAN_SYNTH)
 	  BSW_ORACLE_LIB=$(ASAN_ORACLE) BSW_SYNTH_LIB=$(ASAN_SYNTH) \
 	  python -m pytest tests -q -m "not gpu" -p no:cacheprovider > $(ASAN_DIR)/asan_suite.log 2>&1; rc=$$?; \
 	  tail -5 $(ASAN_DIR)/asan_suite.log; exit $$rc
-.PHONY: asan asan-suite
+# ThreadSanitizer over the host pipeline's worker thread (Worker, bsw_pool.h): a stand-alone driver, no GPU
+TSAN_BIN := $(ASAN_DIR)/worker_driver
+$(TSAN_BIN): $(ASAN_DIR)/worker_driver.cpp $(CSRC)/bsw_pool.h
+	g++ -fsanitize=thread -fno-omit-frame-pointer -g -O1 -std=c++17 -o $@ $< -lpthread
+tsan: $(TSAN_BIN)
+	TSAN_OPTIONS=halt_on_error=1 ./$(TSAN_BIN) > $(ASAN_DIR)/tsan.log 2>&1; rc=$$?; cat $(ASAN_DIR)/tsan.log; exit $$rc
+.PHONY: asan asan-suite tsan

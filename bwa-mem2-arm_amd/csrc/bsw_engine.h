@@ -4,6 +4,7 @@
 //   bsw_dispatch.hip : plan_kernel, run_plan / run_dp / run_device, finish_stats
 //   bsw_sort.hip     : sort_order, the batch-order radix sort (bsw_sort.h)
 //   bsw_pipeline.hip : staging kernels, the chunked host pipeline (host_shard), cross-call coalescing
+//                      (its planning -- staging layout, chunk schedule, kStageBlk -- in bsw_stage_plan.h)
 //   bsw_host.cpp     : contexts, recovery, mate / global / extension wrappers, options, the core C ABI
 //   bsw_stages.cpp   : the stages behind the extension (final alignments, region selection, the
 //                      paired-end stage, mate rescue, SAM records), both forms of each, on shared call
@@ -34,6 +35,7 @@
 #include "bsw_contig_seg.h"
 #include "bsw_kernels.h"
 #include "bsw_internal.h"
+#include "bsw_stage_plan.h"
 
 // engine-internal names that cross translation units stay out of the library's dynamic symbols
 #define BSW_HIDDEN __attribute__((visibility("hidden")))
@@ -50,7 +52,6 @@ constexpr int kMetaRedo = kMetaCnt + 1;     // packed-column classes: redo-list 
 constexpr int kMetaRedoWords = 5;
 constexpr int kMetaWords = kMetaRedo + kMetaRedoWords;
 constexpr int kKeyBits = 32;                // 4 class + 8 qlen + 1 related + 11 tlen + 8 h0 bits
-constexpr int32_t kStageBlk = 4096;         // host pipeline: pairs per staging block (a chunk is whole blocks)
 
 static inline int hip_rc(hipError_t e)
 {

@@ -432,8 +432,7 @@ static int recover_range(bsw_ctx_t *ctx, const KParams &kp, int d0, SeqPair *pai
     how = std::max(how, 3);
     *st = a;
     st->kernel_ms += b.kernel_ms; st->stage_ms += b.stage_ms; st->host_ms += b.host_ms;
-    st->n_i16 += b.n_i16; st->n_u8 += b.n_u8; st->n_wide += b.n_wide; st->n_packed += b.n_packed;
-    st->n_launches += b.n_launches; st->n_wave += b.n_wave; st->n_group += b.n_group;
+    add_counters(*st, b);
     return BSW_OK;
 }
 
@@ -454,9 +453,7 @@ int scores_eb(bsw_ctx_t *ctx, int32_t end_bonus, SeqPair *pairs, const uint8_t *
     // before any device starts
     if (nd > 1)
         for (int32_t i = 0; i < n; ++i)
-            if (pairs[i].len1 < 0 || pairs[i].len2 < 0 || pairs[i].len1 > BSW_MAX_LEN ||
-                pairs[i].len2 > BSW_MAX_LEN || pairs[i].idr < 0 || pairs[i].idq < 0)
-                return BSW_E_RANGE;
+            if (!pair_valid(pairs[i])) return BSW_E_RANGE;
     std::vector<int> rcs(nd, BSW_OK);
     std::vector<bsw_stats_t> st(nd);
     std::vector<int> how(nd, 0);
@@ -495,9 +492,7 @@ int scores_eb(bsw_ctx_t *ctx, int32_t end_bonus, SeqPair *pairs, const uint8_t *
     for (int d = 0; d < nd; ++d) {
         if (rcs[d]) return rcs[d];
         agg.kernel_ms = std::max(agg.kernel_ms, st[d].kernel_ms);
-        agg.n_i16 += st[d].n_i16; agg.n_u8 += st[d].n_u8; agg.n_wide += st[d].n_wide; agg.n_packed += st[d].n_packed;
-        agg.n_launches += st[d].n_launches;
-        agg.n_wave += st[d].n_wave; agg.n_group += st[d].n_group;
+        add_counters(agg, st[d]);
         agg.stage_ms = std::max(agg.stage_ms, st[d].stage_ms);
         agg.host_ms = std::max(agg.host_ms, st[d].host_ms);
         agg.recovery = std::max(agg.recovery, how[d]);

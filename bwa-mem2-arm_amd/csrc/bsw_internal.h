@@ -48,13 +48,18 @@ int chain_rounds_device(bsw_ctx_t *ctx, const bsw_ext_opt_t *opt, const uint8_t 
 // outside 0..3, ascending (the staging kernels patch code bits 2-3 from them, bsw_pipeline.hip)
 void pack_nibbles(uint8_t *dst, const uint8_t *src, size_t nbytes);
 void pack_2bit(uint8_t *dst, const uint8_t *src, size_t nbytes, uint32_t pos0, std::vector<uint32_t> &exc);
-// plan_kernel's schedule key (bsw_dispatch.hip) of the packed-column class computed on the host
-// for pairs [0, n) -- (255 - qlen) << 20 | (1 - related) << 19 |
-// (63 - tlen / 32) << 13 | (31 - seed identities) << 8 | (255 - h0), identities as the device's
-// seed_matches (best of 13 shifts of query[10, 40) against target[4 + s, 34 + s))
-void fast_keys(const SeqPair *pairs, int32_t n, const uint8_t *ref, const uint8_t *qer, uint32_t *keys);
-// kv[i] = (the bits of keys[i] selected by `vary`, compacted: pext) << 32 | i, for i in [a0, a1)
-void compact_keys(const uint32_t *keys, int32_t a0, int32_t a1, uint32_t vary, uint64_t *kv);
+// a record bsw_get_scores / bsw_pack_batch accept (else BSW_E_RANGE)
+inline bool pair_valid(const SeqPair &p)
+{
+    return p.len1 >= 0 && p.len2 >= 0 && p.len1 <= BSW_MAX_LEN && p.len2 <= BSW_MAX_LEN && p.idr >= 0 && p.idq >= 0;
+}
+// a += b over the pair and launch counters of two calls' stats (the *_ms fields are the caller's:
+// summed along one device's chunks, maxed over devices)
+inline void add_counters(bsw_stats_t &a, const bsw_stats_t &b)
+{
+    a.n_i16 += b.n_i16; a.n_u8 += b.n_u8; a.n_wide += b.n_wide; a.n_packed += b.n_packed;
+    a.n_launches += b.n_launches; a.n_wave += b.n_wave; a.n_group += b.n_group;
+}
 // Layout of a staged blob (the host-array forms of the stages, bsw_stages.cpp): parts end to end
 // in the order added, each starting on a 16-byte boundary; a part of 0 bytes takes no room
 struct BlobLayout {

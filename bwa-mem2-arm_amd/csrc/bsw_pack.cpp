@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 #include "bsw_internal.h"
+#include "bsw_stage_plan.h"
 
 namespace bsw {
 
@@ -145,70 +146,6 @@ void pack_2bit(uint8_t *dst, const uint8_t *src, size_t nbytes, uint32_t pos0, s
     else pack_2bit_sse2(dst, src, nbytes, pos0, exc);
 }
 
-// seed identities (plan_kernel's seed_matches, bsw_dispatch.hip): best over shifts s = 0..12 of the
-// matches of query[10, 40) with target[4 + s, 34 + s); 31 when the pair is too short to test
-static int seed_matches_scalar(const uint8_t *q, int qlen, const uint8_t *r, int tlen)
-{
-    if (qlen < 40 || tlen < 46) return 31;
-    int best = 0;
-    for (int s = 0; s <= 12; ++s) {
-        int c = 0;
-        for (int j = 0; j < 30; ++j) c += q[10 + j] == r[4 + j + s];
-        best = c > best ? c : best;
-    }
-    return best;
-}
-
-// AVX2: the 30 query bytes in one register, each shift one unaligned load + compare + popcount.
-// Reads target bytes [4, 48): only when tlen >= 48 (the scalar form otherwise)
-__attribute__((target("avx2,popcnt"))) static int seed_matches_avx2(const uint8_t *q, int qlen, const uint8_t *r,
-                                                                    int tlen)
-{
-    if (qlen < 42 || tlen < 48) return seed_matches_scalar(q, qlen, r, tlen);
-    const __m256i qv = _mm256_loadu_si256((const __m256i *)(q + 10));
-    int best = 0;
-    for (int s = 0; s <= 12; ++s) {
-        const __m256i rv = _mm256_loadu_si256((const __m256i *)(r + 4 + s));
-        const uint32_t m = (uint32_t)_mm256_movemask_epi8(_mm256_cmpeq_epi8(qv, rv)) & 0x3fffffffu;
-        const int c = __builtin_popcount(m);
-        best = c > best ? c : best;
-    }
-    return best;
-}
-
-void fast_keys(const SeqPair *pairs, int32_t n, const uint8_t *ref, const uint8_t *qer, uint32_t *keys)
-{
-    static const bool avx2 = __builtin_cpu_supports("avx2");
-    for (int32_t i = 0; i < n; ++i) {
-        const SeqPair &p = pairs[i];
-        const int qlen = p.len2 > 0 ? p.len2 : 0, tlen = p.len1 > 0 ? p.len1 : 0;
-        const uint8_t *q = qer + (qlen > 0 ? p.idq : 0), *r = ref + (tlen > 0 ? p.idr : 0);
-        const int mt = avx2 ? seed_matches_avx2(q, qlen, r, tlen) : seed_matches_scalar(q, qlen, r, tlen);
-        const int rel = mt > 18;
-        const int h0 = p.h0 < 0 ? 0 : (p.h0 > 255 ? 255 : p.h0);
-        keys[i] = ((uint32_t)(255 - (qlen < 255 ? qlen : 255)) << 20) | ((uint32_t)(1 - rel) << 19) |
-                  ((uint32_t)(63 - ((tlen >> 5) < 63 ? (tlen >> 5) : 63)) << 13) |
-                  ((uint32_t)(31 - (mt < 31 ? mt : 31)) << 8) | (uint32_t)(255 - h0);
-    }
-}
-
-__attribute__((target("bmi2"))) static void compact_bmi2(const uint32_t *keys, int32_t a0, int32_t a1, uint32_t vary,
-                                                         uint64_t *kv)
-{
-    for (int32_t i = a0; i < a1; ++i) kv[i] = ((uint64_t)_pext_u32(keys[i], vary) << 32) | (uint32_t)i;
-}
-
-void compact_keys(const uint32_t *keys, int32_t a0, int32_t a1, uint32_t vary, uint64_t *kv)
-{
-    static const bool bmi2 = __builtin_cpu_supports("bmi2");
-    if (bmi2) { compact_bmi2(keys, a0, a1, vary, kv); return; }
-    for (int32_t i = a0; i < a1; ++i) {
-        uint32_t ck = 0;
-        for (uint32_t v = vary, o = 0; v; v &= v - 1, ++o) ck |= ((keys[i] >> __builtin_ctz(v)) & 1u) << o;
-        kv[i] = ((uint64_t)ck << 32) | (uint32_t)i;
-    }
-}
-
 }  // namespace bsw
 
 // bsw_pack_batch (bsw.h): the 2-bit wire form of a batch, host-only
@@ -219,8 +156,7 @@ extern "C" int bsw_pack_batch(const SeqPair *pairs, const uint8_t *ref, const ui
     int64_t r_lo = INT64_MAX, r_hi = 0, q_lo = INT64_MAX, q_hi = 0;
     for (int32_t i = 0; i < n; ++i) {
         const SeqPair &p = pairs[i];
-        if (p.len1 < 0 || p.len2 < 0 || p.len1 > BSW_MAX_LEN || p.len2 > BSW_MAX_LEN || p.idr < 0 || p.idq < 0)
-            return BSW_E_RANGE;
+        if (!bsw::pair_valid(p)) return BSW_E_RANGE;
         if (p.len1 > 0) { r_lo = std::min<int64_t>(r_lo, p.idr); r_hi = std::max<int64_t>(r_hi, (int64_t)p.idr + p.len1); }
         if (p.len2 > 0) { q_lo = std::min<int64_t>(q_lo, p.idq); q_hi = std::max<int64_t>(q_hi, (int64_t)p.idq + p.len2); }
     }
@@ -235,18 +171,18 @@ extern "C" int bsw_pack_batch(const SeqPair *pairs, const uint8_t *ref, const ui
         return c;
     };
     const int64_t er = count_exc(ref + r_lo, rb), eq = count_exc(qer + q_lo, qb);
-    auto a256 = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
+    const bsw::StageLayout lay = bsw::stage_layout(bsw::kStage2bit, (size_t)n, (size_t)rb, (size_t)qb, (size_t)(er + eq));
     bsw_packed_t d{};
     d.n = n;
     d.n_exc_ref = (int32_t)er;
     d.n_exc_qer = (int32_t)eq;
     d.ref_bytes = rb;
     d.qer_bytes = qb;
-    d.rec_off = 0;
-    d.ref_off = a256((int64_t)n * 20);
-    d.qer_off = a256(d.ref_off + (rb + 3) / 4 + 4);
-    d.exc_off = a256(d.qer_off + (qb + 3) / 4 + 4);
-    d.total_bytes = a256(d.exc_off + 4 * (er + eq));
+    d.rec_off = (int64_t)lay.pair_off;
+    d.ref_off = (int64_t)lay.ref_off;
+    d.qer_off = (int64_t)lay.qer_off;
+    d.exc_off = (int64_t)lay.exc_off;
+    d.total_bytes = (int64_t)lay.wire_bytes;
     *desc = d;
     if (!dst) return BSW_OK;
     if (cap < d.total_bytes) return BSW_E_INVAL;

@@ -5,27 +5,29 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
-#include <deque>
 #include <mutex>
-#include <thread>
 #include <vector>
 #include "bsw_engine.h"
 #include "bsw_sort.h"
 #include "bsw_pool.h"
+#include "bsw_stage_plan.h"
+
+// experiment builds only (make abhost AB_FLAGS=-DBSW_HP_SLOTS=5 / -DBSW_HP_FIRST_BLK=8)
+// Slots of one host_shard call; chunk k + slots stages only once chunk k's outputs are back.  4
+// since round 4: with the helper stream the fourth slot lets the next chunk stage a DP generation
+// earlier (same box, alternating: 84.7 / 87.7 vs 77.0 / 78.8 M/s per 1M-pair call; 5 slots pay
+// more first-call allocation, profiles/r04/hostpath_slots_r4w.txt)
+#ifndef BSW_HP_SLOTS
+#define BSW_HP_SLOTS 4
+#endif
+// blocks of a pipelined call's first chunk (first_chunk_blocks, bsw_stage_plan.h)
+#ifndef BSW_HP_FIRST_BLK
+#define BSW_HP_FIRST_BLK 16
+#endif
 
 namespace bsw {
 
-static void par_pack_nibbles(uint8_t *dst, const uint8_t *src, size_t nbytes)
-{
-    constexpr size_t kPiece = (size_t)2 << 20;
-    const int nt = (int)std::min<size_t>(HostPool::workers() + 1, nbytes / kPiece);
-    if (nt <= 1) { pack_nibbles(dst, src, nbytes); return; }
-    auto cut = [=](size_t t) { return t == (size_t)nt ? nbytes : (nbytes * t / nt) & ~(size_t)31; };
-    HostPool::get().parallel_for(nt, [=](int t) {
-        const size_t a = cut(t), b = cut(t + 1);
-        pack_nibbles(dst + a / 2, src + a, b - a);
-    });
-}
+static_assert(sizeof(PairIn) == kPairInBytes, "stage_layout's 2-bit record is PairIn");
 
 // bytes out[0, n) from nibbles in[0, (n + 1) / 2): 4 packed bytes -> 8 codes per thread
 __global__ void unpack_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, int64_t n)
@@ -49,45 +51,6 @@ __global__ void unpack_kernel(const uint8_t *__restrict__ in, uint8_t *__restric
                               (uint8_t)w1, (uint8_t)(w1 >> 8), (uint8_t)(w1 >> 16), (uint8_t)(w1 >> 24)};
         for (int k = 0; o + k < n; ++k) out[o + k] = b[k];
     }
-}
-
-// bytes out[0, n) from 2-bit codes in[0, (n + 3) / 4): 4 packed bytes -> 16 codes per thread
-__global__ void unpack2_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, int64_t n)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t o = t * 16;
-    if (o >= n) return;
-    uint32_t v = 0;
-    const int64_t ib = t * 4, nin = (n + 3) / 4;
-    if (ib + 4 <= nin) v = *(const uint32_t *)(in + ib);
-    else
-        for (int k = 0; k < 4 && ib + k < nin; ++k) v |= (uint32_t)in[ib + k] << (8 * k);
-    // plane p holds code 4m + p in byte m; output dword m = byte m of planes 0..3
-    const uint32_t p0 = v & 0x03030303u, p1 = (v >> 2) & 0x03030303u;
-    const uint32_t p2 = (v >> 4) & 0x03030303u, p3 = (v >> 6) & 0x03030303u;
-    const uint32_t a01 = __builtin_amdgcn_perm(p1, p0, 0x05010400u), b01 = __builtin_amdgcn_perm(p1, p0, 0x07030602u);
-    const uint32_t a23 = __builtin_amdgcn_perm(p3, p2, 0x05010400u), b23 = __builtin_amdgcn_perm(p3, p2, 0x07030602u);
-    const uint4 r = make_uint4(__builtin_amdgcn_perm(a23, a01, 0x05040100u), __builtin_amdgcn_perm(a23, a01, 0x07060302u),
-                               __builtin_amdgcn_perm(b23, b01, 0x05040100u), __builtin_amdgcn_perm(b23, b01, 0x07060302u));
-    if (o + 16 <= n) {
-        *(uint4 *)(out + o) = r;
-    } else {
-        const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-        for (int k = 0; o + k < n; ++k) out[o + k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-    }
-}
-
-// (PairIn: the kernels' input fields of a SeqPair, bsw_kernels.h)
-
-__global__ void expand_pairs_kernel(const PairIn *__restrict__ in, SeqPair *__restrict__ out, int32_t n)
-{
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const PairIn p = in[i];
-    SeqPair sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.idr = p.idr; sp.idq = p.idq; sp.len1 = p.len1; sp.len2 = p.len2; sp.h0 = p.h0;
-    out[i] = sp;
 }
 
 // The whole staged input of a coalesced batch in one launch (what unpack2 x2 + patch_codes +
@@ -234,17 +197,16 @@ __global__ __launch_bounds__(256) void stage_in_kernel(const uint8_t *__restrict
     }
 }
 
-static size_t exc_buckets(int64_t r_tot, int64_t q_tot) { return (size_t)((r_tot + 4095) / 4096 + (q_tot + 4095) / 4096 + 2); }
-
 // The whole staged input of one batch: the exceptions' bucket table (when there are exceptions),
 // then stage_in_kernel -- on `st`, the slot's d_bkt grown to the table
 int launch_stage_in(Slot &s, hipStream_t st, const uint8_t *ref2, int64_t r_tot, const uint8_t *qer2,
                            int64_t q_tot, const uint32_t *exc, int32_t n_r, int32_t ne, const PairIn *pin, int32_t n,
                            uint8_t *ref, uint8_t *qer, SeqPair *pairs, int32_t *zero2)
 {
-    const int64_t nbr = (r_tot + 4095) / 4096 + 1, nbq = (q_tot + 4095) / 4096 + 1;
+    const ExcBuckets nb = exc_buckets(r_tot, q_tot);
+    const int64_t nbr = nb.nbr, nbq = nb.nbq;
     if (ne > 0) {
-        BSW_TRY(s.d_bkt.grow(exc_buckets(r_tot, q_tot)));
+        BSW_TRY(s.d_bkt.grow(nb.total()));
         hipLaunchKernelGGL(exc_bucket_kernel, dim3((unsigned)((nbr + nbq + 255) / 256)), dim3(256), 0, st, exc, n_r,
                            ne, nbr, nbq, s.d_bkt);
         BSW_TRY(hipGetLastError());
@@ -273,13 +235,8 @@ int launch_gather_outputs(const SeqPair *d_pairs, int32_t *d_out, int32_t n, hip
 }
 
 // Pre-pass of a host-buffer call, one parallel sweep over the records: validation (the ABI's
-// BSW_E_RANGE before any device work) and per-block extents of the byte buffers, from which
-// chunks are cut and staged without another pass.
-struct BlkStat {
-    int64_t r_lo, r_hi, q_lo, q_hi, r_sum, q_sum;
-    bool bad;
-};
-
+// BSW_E_RANGE before any device work) and per-block extents of the byte buffers (BlkStat,
+// bsw_stage_plan.h).
 // blocks [b0, b1) of bs (sized for every block of the n pairs); false if any pair there is invalid
 static bool prepass_range(const SeqPair *pairs, int32_t n, std::vector<BlkStat> &bs, int32_t b0, int32_t b1)
 {
@@ -288,8 +245,7 @@ static bool prepass_range(const SeqPair *pairs, int32_t n, std::vector<BlkStat> 
         const int32_t e = std::min(n, (b + 1) * kStageBlk);
         for (int32_t i = b * kStageBlk; i < e; ++i) {
             const SeqPair &p = pairs[i];
-            t.bad |= p.len1 < 0 || p.len2 < 0 || p.len1 > BSW_MAX_LEN || p.len2 > BSW_MAX_LEN || p.idr < 0 ||
-                     p.idq < 0;
+            t.bad |= !pair_valid(p);
             if (p.len1 > 0) { t.r_lo = std::min<int64_t>(t.r_lo, p.idr); t.r_hi = std::max<int64_t>(t.r_hi, (int64_t)p.idr + p.len1); t.r_sum += p.len1; }
             if (p.len2 > 0) { t.q_lo = std::min<int64_t>(t.q_lo, p.idq); t.q_hi = std::max<int64_t>(t.q_hi, (int64_t)p.idq + p.len2); t.q_sum += p.len2; }
         }
@@ -310,25 +266,6 @@ static bool prepass_range(const SeqPair *pairs, int32_t n, std::vector<BlkStat> 
     return true;
 }
 
-// blocks [0, nb) as one: their common extents (none: [0, 0)) and byte sums
-static BlkStat merge_blocks(const BlkStat *b, int32_t nb)
-{
-    BlkStat t{INT64_MAX, 0, INT64_MAX, 0, 0, 0, false};
-    for (int32_t k = 0; k < nb; ++k) {
-        t.r_lo = std::min(t.r_lo, b[k].r_lo); t.r_hi = std::max(t.r_hi, b[k].r_hi); t.r_sum += b[k].r_sum;
-        t.q_lo = std::min(t.q_lo, b[k].q_lo); t.q_hi = std::max(t.q_hi, b[k].q_hi); t.q_sum += b[k].q_sum;
-    }
-    if (t.r_lo == INT64_MAX) t.r_lo = t.r_hi = 0;
-    if (t.q_lo == INT64_MAX) t.q_lo = t.q_hi = 0;
-    return t;
-}
-// staged in bulk (the whole extents, packed) when they hold little besides the pairs' own bytes;
-// else gathered pair by pair
-static bool bulk_extents(const BlkStat &t)
-{
-    return (t.r_hi - t.r_lo) <= t.r_sum + t.r_sum / 4 + 4096 && (t.q_hi - t.q_lo) <= t.q_sum + t.q_sum / 4 + 4096;
-}
-
 static bool prepass(const SeqPair *pairs, int32_t n, std::vector<BlkStat> &bs)
 {
     const int32_t nb = (n + kStageBlk - 1) / kStageBlk;
@@ -336,42 +273,28 @@ static bool prepass(const SeqPair *pairs, int32_t n, std::vector<BlkStat> &bs)
     return prepass_range(pairs, n, bs, 0, nb);
 }
 
-// One chunk of a host-buffer call staged in a slot's pinned buffer: [SeqPair x n | ref | qer].
-// Contiguous chunks (the upstream layout: each batch's windows concatenated in pair order) pack
-// their byte extents into 2-bit codes + exception words, with the records cut to their five
-// input fields (20 of 56 B) and only the 24 output bytes coming back -- or into nibbles with
-// whole records when the chunk holds too many non-ACGT bytes; scattered ones are
-// gathered pair by pair as bytes and the staged records' idr / idq rewritten (only outputs
+// One chunk of a host-buffer call staged in a slot's pinned buffer (StageMode and StageLayout,
+// bsw_stage_plan.h).  Gathered chunks have their staged records' idr / idq rewritten (only outputs
 // ever go back to the caller).
-enum StageMode { kStageGather = 0, kStageNibble = 1, kStage2bit = 2 };
 struct StagedChunk {
     int32_t n = 0;
     int mode = kStageGather;
-    bool packed = false;                // bulk extents (nibble or 2-bit)
-    size_t pair_off = 0, ref_off = 0, qer_off = 0, exc_off = 0, bytes = 0;
+    StageLayout lay;
     int32_t n_exr = 0, n_exq = 0;       // 2-bit: exception words for ref / qer
     size_t rb = 0, qb = 0;              // ref / qer bytes after unpacking
-    int64_t r_base = 0, q_base = 0;     // staged ref byte 0 = caller byte r_base (bulk mode)
+    int64_t r_base = 0, q_base = 0;     // staged ref byte 0 = caller byte r_base (bulk modes)
 };
 
-// blocks [b0, b1) = pairs [a, a + n)
-// 2-bit staging of a bulk chunk: [PairIn x n | ref codes | qer codes | exception words], sized
-// for at least the 24 B per pair of outputs that come back through the same buffers.  Returns 1
-// (nothing staged) when the exception words would pass 1/32 of the bytes.
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// 2-bit staging of a bulk chunk (c.rb / c.qb bytes from ref / qer).  Returns 1 (nothing staged)
+// when the exception words would pass exc_cap.
 static int stage_2bit(Slot &s, const SeqPair *pairs, const uint8_t *ref, const uint8_t *qer, int32_t n,
                       StagedChunk &c)
 {
-    const size_t rs = (c.rb + 3) / 4, qs = (c.qb + 3) / 4;
-    const size_t exc_cap = (c.rb + c.qb) / 32 + 1024;
-    c.pair_off = 0;
-    c.ref_off = align256((size_t)n * sizeof(PairIn));
-    c.qer_off = align256(c.ref_off + rs + 4);          // +4: the unpack's dword loads
-    c.exc_off = align256(c.qer_off + qs + 4);
-    c.bytes = std::max(c.exc_off + exc_cap * 4, (size_t)n * 24);
-    BSW_TRY(s.h_stage.grow(c.bytes));
+    const size_t cap = exc_cap(c.rb, c.qb);
+    const StageLayout l = stage_layout(kStage2bit, (size_t)n, c.rb, c.qb, cap);
+    BSW_TRY(s.h_stage.grow(l.bytes));
     uint8_t *h = s.h_stage;
-    PairIn *pin = (PairIn *)(h + c.pair_off);
+    PairIn *pin = (PairIn *)(h + l.pair_off);
     const int np = (int)std::max<size_t>(1, ((size_t)n * sizeof(SeqPair)) >> 21);
     const int nr = (int)std::max<size_t>(1, c.rb >> 22), nq = (int)std::max<size_t>(1, c.qb >> 22);
     auto even = [](size_t total, int k, int parts) {     // piece bounds: multiples of 64 codes
@@ -385,10 +308,10 @@ static int stage_2bit(Slot &s, const SeqPair *pairs, const uint8_t *ref, const u
                 pin[i] = PairIn{pairs[i].idr, pairs[i].idq, pairs[i].len1, pairs[i].len2, pairs[i].h0};
         } else if (t < np + nr) {
             const size_t a0 = even(c.rb, t - np, nr), a1 = even(c.rb, t - np + 1, nr);
-            pack_2bit(h + c.ref_off + a0 / 4, ref + a0, a1 - a0, (uint32_t)a0, ex[(size_t)(t - np)]);
+            pack_2bit(h + l.ref_off + a0 / 4, ref + a0, a1 - a0, (uint32_t)a0, ex[(size_t)(t - np)]);
         } else {
             const size_t a0 = even(c.qb, t - np - nr, nq), a1 = even(c.qb, t - np - nr + 1, nq);
-            pack_2bit(h + c.qer_off + a0 / 4, qer + a0, a1 - a0, (uint32_t)a0, ex[(size_t)(t - np)]);
+            pack_2bit(h + l.qer_off + a0 / 4, qer + a0, a1 - a0, (uint32_t)a0, ex[(size_t)(t - np)]);
         }
     });
     size_t tot = 0, tr = 0;
@@ -396,48 +319,39 @@ static int stage_2bit(Slot &s, const SeqPair *pairs, const uint8_t *ref, const u
         tot += ex[k].size();
         if (k < (size_t)nr) tr += ex[k].size();
     }
-    if (tot > exc_cap) return 1;
-    uint32_t *exw = (uint32_t *)(h + c.exc_off);
+    if (tot > cap) return 1;
+    uint32_t *exw = (uint32_t *)(h + l.exc_off);
     for (size_t k = 0, o = 0; k < ex.size(); o += ex[k].size(), ++k)
         if (!ex[k].empty()) memcpy(exw + o, ex[k].data(), ex[k].size() * 4);
     c.n_exr = (int32_t)tr;
     c.n_exq = (int32_t)(tot - tr);
-    c.mode = kStage2bit;
-    c.bytes = std::max(c.exc_off + tot * 4, (size_t)n * 24);
-    memset(h + c.ref_off + rs, 0, 4);
-    memset(h + c.qer_off + qs, 0, 4);
+    c.lay = stage_layout(kStage2bit, (size_t)n, c.rb, c.qb, tot);
+    memset(h + l.ref_off + l.ref_len, 0, 4);
+    memset(h + l.qer_off + l.qer_len, 0, 4);
     return BSW_OK;
 }
 
+// pairs [0, n) = blocks bs[0, nblk)
 static int stage_chunk(Slot &s, const SeqPair *pairs, const uint8_t *ref, const uint8_t *qer, int32_t n,
                        const BlkStat *bs, int32_t nblk, bool two_bit, StagedChunk &c)
 {
     const BlkStat t = merge_blocks(bs, nblk);
-    const int64_t r_lo = t.r_lo, r_hi = t.r_hi, q_lo = t.q_lo, q_hi = t.q_hi, r_sum = t.r_sum, q_sum = t.q_sum;
-    const bool bulk = bulk_extents(t);
-    c.rb = (size_t)(bulk ? r_hi - r_lo : r_sum);
-    c.qb = (size_t)(bulk ? q_hi - q_lo : q_sum);
-    c.packed = bulk;
+    const int64_t r_lo = t.r_lo, q_lo = t.q_lo;
     c.n = n;
-    if (bulk && two_bit && c.rb < ((size_t)1 << 30) && c.qb < ((size_t)1 << 30)) {
+    c.mode = stage_mode(t, two_bit, &c.rb, &c.qb);
+    const bool bulk = c.mode != kStageGather;
+    c.r_base = bulk ? r_lo : 0;
+    c.q_base = bulk ? q_lo : 0;
+    if (c.mode == kStage2bit) {
         const int r = stage_2bit(s, pairs, ref + r_lo, qer + q_lo, n, c);
-        if (r != 1) {                       // 1: too many exception bytes -> nibbles below
-            c.r_base = r_lo; c.q_base = q_lo;
-            return r;
-        }
+        if (r != 1) return r;
+        c.mode = kStageNibble;              // 1: too many exception bytes -> nibbles below
     }
-    c.mode = bulk ? kStageNibble : kStageGather;
-    const size_t rs = bulk ? (c.rb + 1) / 2 : c.rb, qs = bulk ? (c.qb + 1) / 2 : c.qb;   // staged sizes
-    c.n = n;
-    c.pair_off = 0;
-    c.ref_off = ((size_t)n * sizeof(SeqPair) + 255) & ~(size_t)255;
-    c.qer_off = (c.ref_off + rs + 4 + 255) & ~(size_t)255;     // +4: kernels' aligned dword loads
-    c.bytes = c.qer_off + qs + 4;
-    BSW_TRY(s.h_stage.grow(c.bytes));
+    const StageLayout l = c.lay = stage_layout(c.mode, (size_t)n, c.rb, c.qb, 0);
+    BSW_TRY(s.h_stage.grow(l.bytes));
     uint8_t *h = s.h_stage;
-    SeqPair *sp = (SeqPair *)(h + c.pair_off);
+    SeqPair *sp = (SeqPair *)(h + l.pair_off);
     if (bulk) {
-        c.r_base = r_lo; c.q_base = q_lo;
         // records + both packs as one pool job list (pieces of ~2 MB)
         const size_t pb = (size_t)n * sizeof(SeqPair);
         const int np = (int)std::max<size_t>(1, pb >> 21), nr = (int)std::max<size_t>(1, c.rb >> 22),
@@ -451,83 +365,63 @@ static int stage_chunk(Slot &s, const SeqPair *pairs, const uint8_t *ref, const 
                 memcpy((char *)sp + a0, (const char *)pairs + a0, a1 - a0);
             } else if (t < np + nr) {
                 const size_t a0 = even(c.rb, t - np, nr), a1 = even(c.rb, t - np + 1, nr);
-                pack_nibbles(h + c.ref_off + a0 / 2, ref + r_lo + a0, a1 - a0);
+                pack_nibbles(h + l.ref_off + a0 / 2, ref + r_lo + a0, a1 - a0);
             } else {
                 const size_t a0 = even(c.qb, t - np - nr, nq), a1 = even(c.qb, t - np - nr + 1, nq);
-                pack_nibbles(h + c.qer_off + a0 / 2, qer + q_lo + a0, a1 - a0);
+                pack_nibbles(h + l.qer_off + a0 / 2, qer + q_lo + a0, a1 - a0);
             }
         });
     } else {
         par_memcpy(sp, pairs, (size_t)n * sizeof(SeqPair));
-        c.r_base = c.q_base = 0;
         int64_t ro = 0, qo = 0;
         for (int32_t i = 0; i < n; ++i) {
             SeqPair &p = sp[i];
-            if (p.len1 > 0) { memcpy(h + c.ref_off + ro, ref + p.idr, (size_t)p.len1); p.idr = (int32_t)ro; ro += p.len1; }
+            if (p.len1 > 0) { memcpy(h + l.ref_off + ro, ref + p.idr, (size_t)p.len1); p.idr = (int32_t)ro; ro += p.len1; }
             else p.idr = 0;
-            if (p.len2 > 0) { memcpy(h + c.qer_off + qo, qer + p.idq, (size_t)p.len2); p.idq = (int32_t)qo; qo += p.len2; }
+            if (p.len2 > 0) { memcpy(h + l.qer_off + qo, qer + p.idq, (size_t)p.len2); p.idq = (int32_t)qo; qo += p.len2; }
             else p.idq = 0;
         }
     }
-    memset(h + c.ref_off + rs, 0, 4);
-    memset(h + c.qer_off + qs, 0, 4);
+    memset(h + l.ref_off + l.ref_len, 0, 4);
+    memset(h + l.qer_off + l.qer_len, 0, 4);
     return BSW_OK;
 }
 
-// outputs of a finished chunk (staged records) -> the caller's records.  Bulk-staged records
-// carry the caller's own input fields, so whole records copy back; gathered ones had their
-// offsets rewritten and copy field by field.
+// outputs of a finished chunk -> the caller's records: 24 B per pair (2-bit), whole records
+// (nibbles: they carry the caller's own input fields) or the output fields of the staged records
+// (gathered: their offsets were rewritten)
 static void unstage_outputs(const Slot &s, SeqPair *pairs, int32_t n, int mode)
 {
-    if (mode == kStage2bit) {                           // 24 B of outputs per pair
-        const int32_t *o = (const int32_t *)s.h_stage.p;
-        const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(HostPool::workers() + 1, n >> 15));
-        HostPool::get().parallel_for(nt, [&](int t) {
-            for (int32_t i = (int32_t)((int64_t)n * t / nt); i < (int32_t)((int64_t)n * (t + 1) / nt); ++i) {
-                const int32_t *q = o + 6 * (int64_t)i;
-                pairs[i].score = q[0]; pairs[i].tle = q[1]; pairs[i].gtle = q[2];
-                pairs[i].qle = q[3]; pairs[i].gscore = q[4]; pairs[i].max_off = q[5];
-            }
-        });
-        return;
-    }
-    const SeqPair *sp = (const SeqPair *)s.h_stage.p;
     if (mode == kStageNibble) {
-        par_memcpy(pairs, sp, (size_t)n * sizeof(SeqPair));
+        par_memcpy(pairs, s.h_stage.p, (size_t)n * sizeof(SeqPair));
         return;
     }
-    for (int32_t i = 0; i < n; ++i) {
-        pairs[i].score = sp[i].score; pairs[i].tle = sp[i].tle; pairs[i].gtle = sp[i].gtle;
-        pairs[i].qle = sp[i].qle; pairs[i].gscore = sp[i].gscore; pairs[i].max_off = sp[i].max_off;
+    const int32_t *o = (const int32_t *)s.h_stage.p;
+    if (mode == kStageGather) {
+        for (int32_t i = 0; i < n; ++i) put_outputs(pairs[i], o + BSW_SP_WORDS * (int64_t)i + BSW_SP_SCORE / 4);
+        return;
     }
+    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(HostPool::workers() + 1, n >> 15));
+    HostPool::get().parallel_for(nt, [&](int t) {
+        for (int32_t i = (int32_t)((int64_t)n * t / nt); i < (int32_t)((int64_t)n * (t + 1) / nt); ++i)
+            put_outputs(pairs[i], o + 6 * (int64_t)i);
+    });
 }
 
 // The largest buffers any chunk of a host-buffer call needs, in the staging form stage_chunk will
-// pick for it (2-bit for bulk extents, gathered bytes otherwise; a chunk that falls back to nibbles
-// -- more than 1/32 non-ACGT bytes -- grows its slot as before): reserve_slot grows a slot to them
-// before its first chunk.
+// pick for it first (a 2-bit chunk that falls back to nibbles -- more than 1/32 non-ACGT bytes --
+// grows its slot as before): reserve_slot grows a slot to them before its first chunk.
 struct SlotReserve {
     int32_t m = 0;                      // pairs
     size_t rb = 0, qb = 0, stage = 0;   // unpacked ref / qer bytes, pinned / device staging bytes
     void add(int32_t mc, const BlkStat *b, int32_t nb, bool two_bit)
     {
-        const BlkStat t = merge_blocks(b, nb);
-        const bool bulk = bulk_extents(t);              // (stage_chunk's choice)
-        const size_t r = (size_t)(bulk ? t.r_hi - t.r_lo : t.r_sum), q = (size_t)(bulk ? t.q_hi - t.q_lo : t.q_sum);
-        const size_t mm = (size_t)mc;
-        size_t st;
-        if (bulk && two_bit && r < ((size_t)1 << 30) && q < ((size_t)1 << 30))
-            st = std::max(align256(align256(align256(mm * sizeof(PairIn)) + (r + 3) / 4 + 4) + (q + 3) / 4 + 4) +
-                              ((r + q) / 32 + 1024) * 4,
-                          mm * 24);
-        else if (bulk)
-            st = align256(align256(mm * sizeof(SeqPair)) + (r + 1) / 2 + 4) + (q + 1) / 2 + 4;
-        else
-            st = align256(align256(mm * sizeof(SeqPair)) + r + 4) + q + 4;
+        size_t r, q;
+        const StageMode mode = stage_mode(merge_blocks(b, nb), two_bit, &r, &q);
         m = std::max(m, mc);
         rb = std::max(rb, r);
         qb = std::max(qb, q);
-        stage = std::max(stage, st);
+        stage = std::max(stage, stage_layout(mode, (size_t)mc, r, q, mode == kStage2bit ? exc_cap(r, q) : 0).bytes);
     }
 };
 
@@ -544,7 +438,7 @@ static int reserve_slot(Slot &s, const SlotReserve &r)
     BSW_TRY(s.d_ref.grow(r.rb + 16));
     BSW_TRY(s.d_qer.grow(r.qb + 16));
     BSW_TRY(s.d_pairs.grow((size_t)r.m));
-    BSW_TRY(s.d_bkt.grow(exc_buckets((int64_t)r.rb, (int64_t)r.qb)));
+    BSW_TRY(s.d_bkt.grow(exc_buckets((int64_t)r.rb, (int64_t)r.qb).total()));
     BSW_TRY(grow_sort(s, r.m));
     BSW_TRY(sort_order(s, r.m, kKeyBits, (hipStream_t)0, false));     // (d_tmp only)
     return BSW_OK;
@@ -575,340 +469,300 @@ static int prime_copies(Slot *const *slots, int ns)
     return BSW_OK;
 }
 
-// One device's share of a host-buffer call: a pipeline of chunks over the device's slots (four by default).
-// Per chunk: stage into the slot's pinned buffer (records + nibble-packed sequences, host
-// pool) -> one H2D -> unpack -> plan / sort -> DP kernels -> D2H of the records.  The calling
-// thread only stages and enqueues copies and plans; a launcher thread enqueues each chunk's DP
-// kernels and record readback as soon as that chunk's class counts are back, so the GPU never
-// waits for the host to finish staging the next chunk (round 1's single-thread loop launched
-// chunk k's kernels only after chunk k + 1 was staged: ~1.4 ms of idle GPU per chunk in the
-// rocprofv3 timeline).  Chunks ramp from ~n/32 pairs up to `chunk` so the first kernels start
-// early.  Outputs are identical to one unchunked call (pairs are independent).
+// One device's share of a host-buffer call: a pipeline of chunks over the device's slots.
+// Per chunk: stage into the slot's pinned buffer (host pool) -> one H2D -> unpack -> plan / sort
+// -> DP kernels -> D2H of the outputs.  The calling thread only stages; a launcher thread enqueues
+// each chunk's DP kernels and output readback as soon as that chunk's class counts are back, so
+// the GPU never waits for the host to finish staging the next chunk (round 1's single-thread loop
+// launched chunk k's kernels only after chunk k + 1 was staged: ~1.4 ms of idle GPU per chunk in
+// the rocprofv3 timeline).  Calls of several chunks hand each staged chunk to an enqueuer thread,
+// so the calling thread stages the next chunk at once: the enqueue of a chunk (H2D, unpack, plan,
+// sort -- ~0.9 ms of runtime calls per 256K-pair chunk in the kernel + copy trace) otherwise sat
+// between two stagings and made the next chunk's DP start after the current one had drained
+// (profiles/r04/hostpath_trace_*.txt).  One-chunk calls -- up to 128K pairs, kt_for-sized batches
+// -- run on one slot and enqueue inline (no thread hand-off).  Outputs are identical to one
+// unchunked call (pairs are independent).
+//
+// Errors: a chunk whose enqueue failed still goes to the launcher, which skips the DP of every
+// chunk once the call has an error and releases finish(k) with the first one.  The enqueuer is
+// stopped before the launcher, and each handles every queued job first.
+struct ShardCall {
+    static constexpr int kSlots = BSW_HP_SLOTS;
+    const KParams &kp;
+    DeviceCtx &dc;
+    SeqPair *pairs;
+    const uint8_t *ref, *qer;
+    int32_t n, w;
+    int cell_bits;
+    bool two_bit;
+
+    std::unique_ptr<Slot> slots[kSlots];    // taken as chunks start (a one-chunk call takes one)
+    struct Pending { int32_t at = 0, n = 0, seq = -1; int mode = kStageGather; } pend[kSlots];  // chunk in flight
+    bsw_stats_t agg{};
+    double stage_ms = 0;
+
+    // what finish(k) waits on, under mu: the call's first error and per slot the seq (chunks are
+    // numbered in order) of the last chunk the launcher is through with
+    std::mutex mu;
+    std::condition_variable cv;
+    int err = BSW_OK;
+    int32_t launched[kSlots];
+
+    struct LaunchJob { int k; int32_t seq; int mode; };
+    struct EnqJob { int k; int32_t seq; StagedChunk c; };
+    bool launcher_dev_ok = false, enqueuer_dev_ok = false;  // hipSetDevice on each thread
+    bool async = false;
+    Worker<LaunchJob> launcher;             // (the workers go first: members above outlive them)
+    Worker<EnqJob> enqueuer;
+
+    ShardCall(const KParams &kp_, DeviceCtx &dc_, SeqPair *pairs_, const uint8_t *ref_, const uint8_t *qer_,
+              int32_t n_, int32_t w_, int cell_bits_, bool two_bit_)
+        : kp(kp_), dc(dc_), pairs(pairs_), ref(ref_), qer(qer_), n(n_), w(w_), cell_bits(cell_bits_), two_bit(two_bit_)
+    {
+        std::fill(launched, launched + kSlots, -1);
+    }
+
+    // the launcher always, the enqueuer for a call of several chunks
+    void start(bool several)
+    {
+        launcher.start([this](LaunchJob &j) { launch(j); },
+                       [this] { launcher_dev_ok = hipSetDevice(dc.device) == hipSuccess; });
+        async = several;
+        if (!async) return;
+        enqueuer.start(
+            [this](EnqJob &j) {
+                if (enqueuer_dev_ok) (void)enqueue(j.k, j.seq, j.c);
+                else to_launcher(j.k, j.seq, j.c.mode, BSW_E_HIP);
+            },
+            [this] { enqueuer_dev_ok = hipSetDevice(dc.device) == hipSuccess; });
+    }
+
+    // slot k's chunk, enqueued with status r, to the launcher
+    void to_launcher(int k, int32_t seq, int mode, int r)
+    {
+        {
+            std::lock_guard<std::mutex> g(mu);
+            if (r && !err) err = r;
+        }
+        launcher.push(LaunchJob{k, seq, mode});
+    }
+
+    int take_slot(int k, const SlotReserve &res)
+    {
+        if (slots[k]) return BSW_OK;
+        int r = BSW_OK;
+        slots[k] = dc.acquire(r);
+        if (r) return r;
+        // every buffer of the slot at the call's largest chunk at once: chunks rotate over the
+        // slots, so sizing by the chunk at hand regrew a slot (hipFree waits for the device) on
+        // the first calls of a context as its chunks got larger
+        return reserve_slot(*slots[k], res);
+    }
+
+    // the context's first pipelined call: every slot it will use now, then the copy warm-up over
+    // all of them at once (prime_copies).  A failure leaves the context cold for the rerun
+    int warm_up(const SlotReserve &res, int nchunks)
+    {
+        bool cold = false;
+        if (!dc.copies_warm.compare_exchange_strong(cold, true)) return BSW_OK;
+        const int ns = std::min<int>(kSlots, nchunks);
+        Slot *sp[kSlots] = {slots[0].get()};
+        int r = BSW_OK;
+        for (int j = 1; j < ns && !r; ++j)
+            if (!(r = take_slot(j, res))) sp[j] = slots[j].get();
+        if (!r) r = prime_copies(sp, ns);
+        if (r) dc.copies_warm.store(false);
+        return r;
+    }
+
+    int stage(int k, int32_t seq, const ChunkRange &ch, const BlkStat *bs, StagedChunk &c)
+    {
+        const int32_t a = ch.b * kStageBlk, m = chunk_pairs(ch, n);
+        const auto t0 = std::chrono::steady_clock::now();
+        if (int r = stage_chunk(*slots[k], pairs + a, ref, qer, m, bs + ch.b, ch.nb, two_bit, c)) return r;
+        stage_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        pend[k] = Pending{a, m, seq, c.mode};
+        return BSW_OK;
+    }
+
+    // the device side of one staged chunk -- H2D of the slot's staging buffer, unpack kernels,
+    // plan / sort -- then its launcher job, whatever the status.  Everything but the DP kernels
+    // runs on the slot's high-priority stream: the next chunk's copies, unpack / plan / sort
+    // kernels and the outputs' readback are dispatched ahead of the queued DP workgroups
+    int enqueue(int k, int32_t seq, const StagedChunk &c)
+    {
+        const int r = enqueue_device(*slots[k], c);
+        to_launcher(k, seq, c.mode, r);
+        return r;
+    }
+    int enqueue_device(Slot &s, const StagedChunk &c)
+    {
+        if (int e = ensure_pstream(s)) return e;
+        hipStream_t hs = s.pstream;
+        const StageLayout &l = c.lay;
+        BSW_TRY(s.d_stage.grow(l.bytes));
+        BSW_TRY(hipMemcpyAsync(s.d_stage, s.h_stage, l.bytes, hipMemcpyHostToDevice, hs));
+        const uint8_t *d_r = s.d_stage + l.ref_off, *d_q = s.d_stage + l.qer_off;
+        SeqPair *d_p = (SeqPair *)(s.d_stage + l.pair_off);
+        if (c.mode == kStage2bit) {     // 2-bit codes -> bytes, exceptions patched, records expanded
+            // one launch (stage_in_kernel: both unpacks, the exception patches, the records and
+            // the pad zeroing) instead of six: a chunk's enqueue is launch-bound on the host
+            // (~60 us per launch while the pool packs the next chunk, HIP API trace
+            // profiles/r04/hostpath_api_trace.txt)
+            BSW_TRY(s.d_ref.grow(c.rb + 16));
+            BSW_TRY(s.d_qer.grow(c.qb + 16));
+            BSW_TRY(s.d_pairs.grow((size_t)c.n));
+            if (int e = launch_stage_in(s, hs, d_r, (int64_t)c.rb, d_q, (int64_t)c.qb,
+                                        (const uint32_t *)(s.d_stage + l.exc_off), c.n_exr, c.n_exr + c.n_exq,
+                                        (const PairIn *)(s.d_stage + l.pair_off), c.n, s.d_ref, s.d_qer, s.d_pairs,
+                                        nullptr))
+                return e;
+            d_r = s.d_ref;
+            d_q = s.d_qer;
+            d_p = s.d_pairs;
+        } else if (c.mode == kStageNibble) {    // nibbles -> one byte per base in the slot's buffers
+            BSW_TRY(s.d_ref.grow(c.rb + 4));
+            BSW_TRY(s.d_qer.grow(c.qb + 4));
+            BSW_TRY(hipMemsetAsync(s.d_ref + c.rb, 0, 4, hs));
+            BSW_TRY(hipMemsetAsync(s.d_qer + c.qb, 0, 4, hs));
+            const int64_t tr = ((int64_t)c.rb + 7) / 8, tq = ((int64_t)c.qb + 7) / 8;
+            if (tr > 0)
+                hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((tr + 255) / 256)), dim3(256), 0, hs, d_r, s.d_ref,
+                                   (int64_t)c.rb);
+            if (tq > 0)
+                hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((tq + 255) / 256)), dim3(256), 0, hs, d_q, s.d_qer,
+                                   (int64_t)c.qb);
+            BSW_TRY(hipGetLastError());
+            d_r = s.d_ref;
+            d_q = s.d_qer;
+        }
+        PlanCall pc;
+        pc.d_pairs = d_p;
+        // kernels index ref / qer by idr / idq: shift the bases so staged byte 0 is r_base / q_base
+        pc.d_ref = d_r - c.r_base;
+        pc.d_qer = d_q - c.q_base;
+        pc.n = c.n; pc.w = w; pc.cell_bits = cell_bits; pc.stream = hs;
+        pc.dp_stream = s.stream;
+        pc.plan_stream = hs;
+        return run_plan(kp, s, pc);
+    }
+
+    // launcher thread: a chunk's DP kernels and the readback of its outputs
+    void launch(const LaunchJob &job)
+    {
+        int r = launcher_dev_ok ? BSW_OK : BSW_E_HIP;
+        {
+            std::lock_guard<std::mutex> g(mu);
+            if (err) r = err;
+        }
+        Slot &p = *slots[job.k];
+        if (!r) r = run_dp(kp, p);
+        // the outputs' gather and readback go on the high-priority stream once the DP (and its
+        // guard readback) is done: on the DP stream they would queue behind the next chunks'
+        // DP workgroups (a 1.4 ms copy in the trace)
+        hipStream_t os = p.run_stream;
+        hipStream_t hs = p.plan.plan_stream;       // the chunk's helper stream
+        if (!r && hs && p.run_stream != hs) {
+            if (!p.evd && hipEventCreateWithFlags(&p.evd.p, hipEventDisableTiming) != hipSuccess) r = BSW_E_HIP;
+            if (!r && (hipEventRecord(p.evd, p.run_stream) != hipSuccess ||
+                       hipStreamWaitEvent(hs, p.evd, 0) != hipSuccess))
+                r = BSW_E_HIP;
+            os = hs;
+            p.run_stream = hs;                     // finish_stats waits here: after the DP's stream
+        }
+        if (!r && job.mode == kStage2bit) {        // outputs only: 24 B per pair
+            const int32_t m = p.plan.n;
+            if (launch_gather_outputs(p.plan.d_pairs, (int32_t *)p.d_stage.p, m, os) != BSW_OK ||
+                hipMemcpyAsync(p.h_stage, p.d_stage, (size_t)m * kOutBytes, hipMemcpyDeviceToHost, os) != hipSuccess)
+                r = BSW_E_HIP;
+        } else if (!r && hipMemcpyAsync(p.h_stage, p.plan.d_pairs, (size_t)p.plan.n * sizeof(SeqPair),
+                                        hipMemcpyDeviceToHost, os) != hipSuccess) {
+            r = BSW_E_HIP;
+        }
+        {
+            std::lock_guard<std::mutex> g(mu);
+            if (r && !err) err = r;
+            launched[job.k] = job.seq;
+        }
+        cv.notify_all();
+    }
+
+    // wait for slot k's chunk, outputs back in the caller's records
+    int finish(int k)
+    {
+        Pending &pd = pend[k];
+        if (pd.n == 0) return BSW_OK;
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return launched[k] == pd.seq; });
+            if (err) return err;
+        }
+        Slot &s = *slots[k];
+        if (int r = finish_stats(s)) return r;          // also BSW_E_RANGE: kernel guard tripped
+        unstage_outputs(s, pairs + pd.at, pd.n, pd.mode);
+        agg.kernel_ms += s.stats.kernel_ms;
+        add_counters(agg, s.stats);
+        pd.n = 0;
+        return BSW_OK;
+    }
+
+    // the chunk loop: chunk j on slot j % kSlots, once that slot's last chunk is finished
+    int run(const std::vector<ChunkRange> &chs, const BlkStat *bs, const SlotReserve &res)
+    {
+        BSW_TRY(hipSetDevice(dc.device));
+        if (int r = reserve_slot(*slots[0], res)) return r;     // (slot 0 was taken before the threads started)
+        if (chs.size() > 1)
+            if (int r = warm_up(res, (int)chs.size())) return r;
+        int32_t seq = 0;
+        for (const ChunkRange &ch : chs) {
+            const int k = seq % kSlots;
+            if (int r = finish(k)) return r;
+            if (int r = take_slot(k, res)) return r;
+            StagedChunk c;
+            if (int r = stage(k, seq, ch, bs, c)) return r;
+            if (async) enqueuer.push(EnqJob{k, seq, c});
+            else if (int r = enqueue(k, seq, c)) return r;
+            ++seq;
+        }
+        for (int k = 0; k < kSlots; ++k)
+            if (int r = finish(k)) return r;
+        return BSW_OK;
+    }
+};
+
 int host_shard(const KParams &kp, DeviceCtx &dc, SeqPair *pairs, const uint8_t *ref,
                       const uint8_t *qer, int32_t n, int32_t w, int cell_bits, int32_t chunk, bool two_bit,
                       bsw_stats_t *st)
 {
     if (n == 0) return BSW_OK;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    const auto t_start = now();
+    const auto t_start = std::chrono::steady_clock::now();
     // the whole prepass (validation + per-block byte extents) before chunk 0: validating only chunk
     // 0's blocks first and the rest after it started measured no faster
     std::vector<BlkStat> bs;
     if (!prepass(pairs, n, bs)) return BSW_E_RANGE;
     if (chunk <= 0) chunk = n;
-    // slots are taken as chunks start (a one-chunk call takes one); chunk k + nslots stages only
-    // once chunk k's outputs are back.  4 since round 4: with the helper stream the fourth slot
-    // lets the next chunk stage a DP generation earlier (same box, alternating: 84.7 / 87.7 vs
-    // 77.0 / 78.8 M/s per 1M-pair call; 5 slots pay more first-call allocation,
-    // profiles/r04/hostpath_slots_r4w.txt)
-#ifndef BSW_HP_SLOTS                   // experiment builds only (make abhost AB_FLAGS=-DBSW_HP_SLOTS=5)
-#define BSW_HP_SLOTS 4
-#endif
-    constexpr int nslots = BSW_HP_SLOTS;
-    int rc = BSW_OK;
-    std::unique_ptr<Slot> slots[nslots];
-    slots[0] = dc.acquire(rc);
-    if (rc) return rc;
-    int32_t pend_at[nslots] = {}, pend_n[nslots] = {};  // chunk in flight per slot
-    int32_t pend_seq[nslots];
-    std::fill(pend_seq, pend_seq + nslots, -1);
-    int pend_mode[nslots] = {};
-    bsw_stats_t agg{};
-    // Everything but the DP kernels runs on the slot's high-priority stream: the next chunk's
-    // copies, unpack / plan / sort kernels and the outputs' readback are dispatched ahead of the
-    // queued DP workgroups instead of behind them
-    // launcher thread: chunk seq numbers in order; launched[k] = last seq whose DP is enqueued
-    struct Launcher {
-        std::mutex mu;
-        std::condition_variable cv;
-        struct Job { int first; int32_t second; int mode; };
-        std::deque<Job> q;                        // (slot, seq, staging mode)
-        int32_t launched[nslots];
-        bool stop = false;
-        int rc = BSW_OK;
-    } L;
-    std::fill(L.launched, L.launched + nslots, -1);
-    std::thread launcher([&] {
-        const bool dev_ok = hipSetDevice(dc.device) == hipSuccess;
-        for (;;) {
-            Launcher::Job job;
-            {
-                std::unique_lock<std::mutex> lk(L.mu);
-                L.cv.wait(lk, [&] { return L.stop || !L.q.empty(); });
-                if (L.q.empty()) return;
-                job = L.q.front();
-                L.q.pop_front();
-            }
-            int r = dev_ok ? BSW_OK : BSW_E_HIP;
-            {
-                std::lock_guard<std::mutex> g(L.mu);
-                if (L.rc) r = L.rc;
-            }
-            Slot &p = *slots[job.first];
-            if (!r) r = run_dp(kp, p);
-            // the outputs' gather and readback go on the high-priority stream once the DP (and its
-            // guard readback) is done: on the DP stream they would queue behind the next chunks'
-            // DP workgroups (a 1.4 ms copy in the trace)
-            hipStream_t os = p.run_stream;
-            hipStream_t hs = p.plan.plan_stream;       // the chunk's helper stream
-            if (!r && hs && p.run_stream != hs) {
-                if (!p.evd && hipEventCreateWithFlags(&p.evd.p, hipEventDisableTiming) != hipSuccess) r = BSW_E_HIP;
-                if (!r && (hipEventRecord(p.evd, p.run_stream) != hipSuccess ||
-                           hipStreamWaitEvent(hs, p.evd, 0) != hipSuccess))
-                    r = BSW_E_HIP;
-                os = hs;
-                p.run_stream = hs;                     // finish_stats waits here: after the DP's stream
-            }
-            if (!r && job.mode == kStage2bit) {        // outputs only: 24 B per pair
-                const int32_t m = p.plan.n;
-                hipLaunchKernelGGL(gather_outputs_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, os,
-                                   p.plan.d_pairs, (int32_t *)p.d_stage.p, m);
-                if (hipGetLastError() != hipSuccess ||
-                    hipMemcpyAsync(p.h_stage, p.d_stage, (size_t)m * 24, hipMemcpyDeviceToHost, os) != hipSuccess)
-                    r = BSW_E_HIP;
-            } else if (!r && hipMemcpyAsync(p.h_stage, p.plan.d_pairs, (size_t)p.plan.n * sizeof(SeqPair),
-                                            hipMemcpyDeviceToHost, os) != hipSuccess) {
-                r = BSW_E_HIP;
-            }
-            {
-                std::lock_guard<std::mutex> g(L.mu);
-                if (r && !L.rc) L.rc = r;
-                L.launched[job.first] = job.second;
-            }
-            L.cv.notify_all();
-        }
-    });
-    auto stop_launcher = [&] {
-        {
-            std::lock_guard<std::mutex> g(L.mu);
-            L.stop = true;
-        }
-        L.cv.notify_all();
-        if (launcher.joinable()) launcher.join();
-    };
-    auto finish = [&](int k) -> int {                   // wait for slot k's chunk, outputs back
-        if (pend_n[k] == 0) return BSW_OK;
-        {
-            std::unique_lock<std::mutex> lk(L.mu);
-            L.cv.wait(lk, [&] { return L.launched[k] == pend_seq[k]; });
-            if (L.rc) return L.rc;
-        }
-        Slot &s = *slots[k];
-        const int r = finish_stats(s);                  // also BSW_E_RANGE: kernel guard tripped
-        if (r) return r;
-        unstage_outputs(s, pairs + pend_at[k], pend_n[k], pend_mode[k]);
-        agg.kernel_ms += s.stats.kernel_ms;
-        agg.n_i16 += s.stats.n_i16; agg.n_u8 += s.stats.n_u8; agg.n_wide += s.stats.n_wide;
-        agg.n_packed += s.stats.n_packed; agg.n_launches += s.stats.n_launches; agg.n_wave += s.stats.n_wave; agg.n_group += s.stats.n_group;
-        pend_n[k] = 0;
-        return BSW_OK;
-    };
-    // the device side of one staged chunk -- H2D of the slot's staging buffer, unpack kernels,
-    // plan / sort -- then its launcher job.  On a failure the job still goes to the launcher,
-    // which skips its DP and releases finish(k) with the error
-    auto enqueue = [&](int k, int32_t seq, const StagedChunk &c, int32_t m) -> int {
-        Slot &s = *slots[k];
-        const int r = [&]() -> int {
-            if (int e = ensure_pstream(s)) return e;
-            hipStream_t hs = s.pstream;
-            BSW_TRY(s.d_stage.grow(c.bytes));
-            BSW_TRY(hipMemcpyAsync(s.d_stage, s.h_stage, c.bytes, hipMemcpyHostToDevice, hs));
-            const uint8_t *d_r = s.d_stage + c.ref_off, *d_q = s.d_stage + c.qer_off;
-            SeqPair *d_p = (SeqPair *)(s.d_stage + c.pair_off);
-            if (c.mode == kStage2bit) {     // 2-bit codes -> bytes, exceptions patched, records expanded
-                // one launch (stage_in_kernel: both unpacks, the exception patches, the records and
-                // the pad zeroing) instead of six: a chunk's enqueue is launch-bound on the host
-                // (~60 us per launch while the pool packs the next chunk, HIP API trace
-                // profiles/r04/hostpath_api_trace.txt)
-                BSW_TRY(s.d_ref.grow(c.rb + 16));
-                BSW_TRY(s.d_qer.grow(c.qb + 16));
-                BSW_TRY(s.d_pairs.grow((size_t)m));
-                if (int e = launch_stage_in(s, hs, s.d_stage + c.ref_off, (int64_t)c.rb, s.d_stage + c.qer_off,
-                                            (int64_t)c.qb, (const uint32_t *)(s.d_stage + c.exc_off), c.n_exr,
-                                            c.n_exr + c.n_exq, (const PairIn *)(s.d_stage + c.pair_off), m, s.d_ref,
-                                            s.d_qer, s.d_pairs, nullptr))
-                    return e;
-                d_r = s.d_ref;
-                d_q = s.d_qer;
-                d_p = s.d_pairs;
-            } else if (c.packed) {          // nibbles -> one byte per base in the slot's buffers
-                BSW_TRY(s.d_ref.grow(c.rb + 4));
-                BSW_TRY(s.d_qer.grow(c.qb + 4));
-                BSW_TRY(hipMemsetAsync(s.d_ref + c.rb, 0, 4, hs));
-                BSW_TRY(hipMemsetAsync(s.d_qer + c.qb, 0, 4, hs));
-                const int64_t tr = ((int64_t)c.rb + 7) / 8, tq = ((int64_t)c.qb + 7) / 8;
-                if (tr > 0)
-                    hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((tr + 255) / 256)), dim3(256), 0, hs,
-                                       d_r, s.d_ref, (int64_t)c.rb);
-                if (tq > 0)
-                    hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((tq + 255) / 256)), dim3(256), 0, hs,
-                                       d_q, s.d_qer, (int64_t)c.qb);
-                BSW_TRY(hipGetLastError());
-                d_r = s.d_ref;
-                d_q = s.d_qer;
-            }
-            PlanCall pc;
-            pc.d_pairs = d_p;
-            // kernels index ref / qer by idr / idq: shift the bases so staged byte 0 is r_base / q_base
-            pc.d_ref = d_r - c.r_base;
-            pc.d_qer = d_q - c.q_base;
-            pc.n = m; pc.w = w; pc.cell_bits = cell_bits; pc.stream = hs;
-            pc.dp_stream = s.stream;
-            pc.plan_stream = hs;
-            return run_plan(kp, s, pc);
-        }();
-        {
-            std::lock_guard<std::mutex> g(L.mu);
-            if (r && !L.rc) L.rc = r;
-            L.q.push_back(Launcher::Job{k, seq, c.mode});
-        }
-        L.cv.notify_all();
-        return r;
-    };
-    // Calls of several chunks hand each staged chunk to an enqueuer thread, so the calling thread
-    // stages the next chunk at once: the enqueue of a chunk (H2D, unpack, plan, sort -- ~0.9 ms
-    // of runtime calls per 256K-pair chunk in the kernel + copy trace) otherwise sat between two
-    // stagings and made the next chunk's DP start after the current one had drained
-    // (profiles/r04/hostpath_trace_*.txt).  One-chunk calls enqueue inline (no thread hand-off).
-    struct EnqJob { int k; int32_t seq; StagedChunk c; int32_t m; };
-    struct Enqueuer {
-        std::mutex mu;
-        std::condition_variable cv;
-        std::deque<EnqJob> q;
-        bool stop = false;
-    } E;
-    const int32_t nblk0 = (int32_t)bs.size();
-    // the first chunk: 16 blocks (64K pairs) or 1/32 of the call.  The same size decides whether
-    // the call runs as several chunks (enqueuer thread) and cuts the chunks below
-#ifndef BSW_HP_FIRST_BLK               // experiment builds only (make abhost AB_FLAGS=-DBSW_HP_FIRST_BLK=8)
-#define BSW_HP_FIRST_BLK 16
-#endif
-    const int32_t first_blk = std::min(std::max<int32_t>(1, chunk / kStageBlk),
-                                       nblk0 <= 32 ? nblk0 : std::max<int32_t>(BSW_HP_FIRST_BLK, nblk0 / 32));
-    const bool async = nblk0 > first_blk;
-    std::thread enqueuer;
-    if (async)
-        enqueuer = std::thread([&] {
-            const bool dev_ok = hipSetDevice(dc.device) == hipSuccess;
-            for (;;) {
-                EnqJob job;
-                {
-                    std::unique_lock<std::mutex> lk(E.mu);
-                    E.cv.wait(lk, [&] { return E.stop || !E.q.empty(); });
-                    if (E.q.empty()) return;
-                    job = E.q.front();
-                    E.q.pop_front();
-                }
-                if (!dev_ok) {
-                    std::lock_guard<std::mutex> g(L.mu);
-                    if (!L.rc) L.rc = BSW_E_HIP;
-                    L.q.push_back(Launcher::Job{job.k, job.seq, job.c.mode});
-                    L.cv.notify_all();
-                    continue;
-                }
-                (void)enqueue(job.k, job.seq, job.c, job.m);
-            }
-        });
-    auto stop_enqueuer = [&] {
-        {
-            std::lock_guard<std::mutex> g(E.mu);
-            E.stop = true;
-        }
-        E.cv.notify_all();
-        if (enqueuer.joinable()) enqueuer.join();
-    };
-    double stage_ms = 0;
-    // the chunk schedule (block ranges): `cur` blocks, doubling from first_blk up to `chunk` pairs,
-    // fewer when their sequence bytes pass ~512 MB (staged offsets stay int32).  (A small remainder
-    // stays its own chunk: folded into the last full chunk it added a third, nearly empty generation
-    // of waves to that launch -- 262144 pairs are exactly two generations at two waves per SIMD --
-    // and the call got ~1 ms slower; as its own launch it runs beside the last chunk on another
-    // queue.  Measured)  Calls of up to 128K pairs -- kt_for-sized batches -- run as
-    // one chunk on one slot.
-    std::vector<std::pair<int32_t, int32_t>> chs;
+    const int32_t nblk = (int32_t)bs.size(), first_blk = first_chunk_blocks(nblk, chunk, BSW_HP_FIRST_BLK);
+    const std::vector<ChunkRange> chs = chunk_schedule(bs, chunk, first_blk);
     SlotReserve res{};
-    {
-        const int32_t nblk = (int32_t)bs.size();
-        const int32_t cap_blk = std::max<int32_t>(1, chunk / kStageBlk);
-        for (int32_t b = 0, nb = 0, cur = first_blk; b < nblk; b += nb, cur = std::min(cap_blk, cur * 2)) {
-            int64_t bytes = 0;
-            for (nb = 0; nb < cur && b + nb < nblk; ++nb) {
-                const int64_t x = bs[b + nb].r_sum + bs[b + nb].q_sum;
-                if (nb > 0 && bytes + x > ((int64_t)1 << 29)) break;
-                bytes += x;
-            }
-            chs.emplace_back(b, nb);
-            res.add(std::min(n, (b + nb) * kStageBlk) - b * kStageBlk, bs.data() + b, nb, two_bit);
-        }
-    }
+    for (const ChunkRange &ch : chs) res.add(chunk_pairs(ch, n), bs.data() + ch.b, ch.nb, two_bit);
 
-    rc = [&]() -> int {
-        BSW_TRY(hipSetDevice(dc.device));
-        if (int r = reserve_slot(*slots[0], res)) return r;     // (slot 0 was taken before the schedule)
-        if (chs.size() > 1 && !dc.copies_warm.exchange(true)) {
-            // the context's first pipelined call: every slot it will use now, then the copy
-            // warm-up over all of them at once (prime_copies)
-            const int ns = std::min<int>(nslots, (int)chs.size());
-            Slot *sp[nslots] = {slots[0].get()};
-            for (int j = 1; j < ns; ++j) {
-                int r = BSW_OK;
-                slots[j] = dc.acquire(r);
-                if (r) return r;
-                if ((r = reserve_slot(*slots[j], res))) return r;
-                sp[j] = slots[j].get();
-            }
-            if (int r = prime_copies(sp, ns)) return r;
-        }
-        int k = 0;
-        int32_t seq = 0;
-        for (const auto &ch : chs) {
-            const int32_t b = ch.first, nb = ch.second;
-            const int32_t a = b * kStageBlk, m = std::min(n, (b + nb) * kStageBlk) - a;
-            int r = finish(k);                          // slot k's last chunk
-            if (r) return r;
-            if (!slots[k]) {
-                slots[k] = dc.acquire(r);
-                if (r) return r;
-                // every buffer of the slot at the call's largest chunk at once: chunks rotate over
-                // the slots, so sizing by the chunk at hand regrew a slot (hipFree waits for the
-                // device) on the first calls of a context as its chunks got larger
-                if ((r = reserve_slot(*slots[k], res))) return r;
-            }
-            Slot &s = *slots[k];
-            StagedChunk c;
-            const auto t0 = now();
-            if ((r = stage_chunk(s, pairs + a, ref, qer, m, bs.data() + b, nb, two_bit, c))) return r;
-            stage_ms += std::chrono::duration<double, std::milli>(now() - t0).count();
-            pend_at[k] = a; pend_n[k] = m; pend_mode[k] = c.mode; pend_seq[k] = seq;
-            if (async) {
-                {
-                    std::lock_guard<std::mutex> g(E.mu);
-                    E.q.push_back(EnqJob{k, seq, c, m});
-                }
-                E.cv.notify_all();
-            } else if ((r = enqueue(k, seq, c, m))) {
-                return r;
-            }
-            k = (k + 1) % nslots;
-            ++seq;
-        }
-        for (int j = 0; j < nslots; ++j) {
-            const int r = finish(j);
-            if (r) return r;
-        }
-        return BSW_OK;
-    }();
-    stop_enqueuer();                                    // drains its queue first (every job reaches the launcher)
-    stop_launcher();                                    // drains the queue first (it exits only when empty)
-    agg.stage_ms = (float)stage_ms;
-    agg.host_ms = (float)std::chrono::duration<double, std::milli>(now() - t_start).count();
+    ShardCall call(kp, dc, pairs, ref, qer, n, w, cell_bits, two_bit);
+    int rc = BSW_OK;
+    call.slots[0] = dc.acquire(rc);
+    if (rc) return rc;
+    call.start(nblk > first_blk);
+    rc = call.run(chs, bs.data(), res);
+    call.enqueuer.stop();                               // handles its queue first (every job reaches the launcher)
+    call.launcher.stop();
+    call.agg.stage_ms = (float)call.stage_ms;
+    call.agg.host_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     // give_back(slot, rc) drains a failed call's slots: their stream and pstream, which may hold
     // queued chunks, and also run_stream and the side streams -- idle by now, since the launcher
     // has been joined and run_dp joins its fork before it returns, so the wider drain waits on
     // nothing more
-    for (int k = 0; k < nslots; ++k)
-        if (slots[k]) dc.give_back(std::move(slots[k]), rc);
-    if (rc == BSW_OK && st) *st = agg;
+    for (auto &s : call.slots)
+        if (s) dc.give_back(std::move(s), rc);
+    if (rc == BSW_OK && st) *st = call.agg;
     return rc;
 }
 
@@ -948,16 +802,14 @@ static int run_group_staged(const KParams &kp, DeviceCtx &dc, std::vector<AggSeg
                             int64_t q_tot, int32_t w, int cell_bits, bsw_stats_t &st)
 {
     return with_slot(dc, [&](Slot &s) -> int {
-        const size_t rs = (size_t)(r_tot + 3) / 4, qs = (size_t)(q_tot + 3) / 4;
-        const size_t exc_cap = (size_t)(r_tot + q_tot) / 32 + 1024;
-        const size_t pair_off = 0, ref_off = align256((size_t)N * sizeof(PairIn));
-        const size_t qer_off = align256(ref_off + rs + 4), exc_off = align256(qer_off + qs + 4);
-        const size_t bytes = std::max(exc_off + exc_cap * 4, (size_t)N * 24);
-        BSW_TRY(s.h_stage.grow(bytes));
+        const size_t cap = exc_cap((size_t)r_tot, (size_t)q_tot);
+        const StageLayout l = stage_layout(kStage2bit, (size_t)N, (size_t)r_tot, (size_t)q_tot, cap);
+        const size_t pair_off = l.pair_off, ref_off = l.ref_off, qer_off = l.qer_off, exc_off = l.exc_off;
+        BSW_TRY(s.h_stage.grow(l.bytes));
         const auto tg0 = std::chrono::steady_clock::now();
         uint8_t *h = s.h_stage;
-        memset(h + ref_off, 0, rs + 4);                 // the padding between calls' extents
-        memset(h + qer_off, 0, qs + 4);
+        memset(h + ref_off, 0, l.ref_len + 4);          // the padding between calls' extents
+        memset(h + qer_off, 0, l.qer_len + 4);
         // tasks: per call its records, and its ref / qer extents in pieces of <= 1 MB cut at
         // multiples of 64 codes (every call's extent starts 64-aligned in the code space)
         struct Task { int seg, kind; int64_t a, b; };
@@ -1000,7 +852,7 @@ static int run_group_staged(const KParams &kp, DeviceCtx &dc, std::vector<AggSeg
         });
         size_t n_r = 0, n_q = 0;
         for (size_t t = 0; t < tasks.size(); ++t) (tasks[t].kind == 1 ? n_r : n_q) += ex[t].size();
-        if (n_r + n_q > exc_cap) return 1;              // too many non-ACGT bytes: caller splits
+        if (n_r + n_q > cap) return 1;                  // too many non-ACGT bytes: caller splits
         uint32_t *exw = (uint32_t *)(h + exc_off);
         size_t o_r = 0, o_q = n_r;
         for (size_t t = 0; t < tasks.size(); ++t) {
@@ -1011,7 +863,7 @@ static int run_group_staged(const KParams &kp, DeviceCtx &dc, std::vector<AggSeg
         }
         const size_t up = exc_off + (n_r + n_q) * 4;
         const auto tg1 = std::chrono::steady_clock::now();
-        BSW_TRY(s.d_stage.grow(std::max(up, (size_t)N * 24)));
+        BSW_TRY(s.d_stage.grow(stage_layout(kStage2bit, (size_t)N, (size_t)r_tot, (size_t)q_tot, n_r + n_q).bytes));
         BSW_TRY(hipMemcpyAsync(s.d_stage, s.h_stage, up, hipMemcpyHostToDevice, s.stream));
         BSW_TRY(s.d_ref.grow((size_t)r_tot + 4));
         BSW_TRY(s.d_qer.grow((size_t)q_tot + 4));
@@ -1044,7 +896,7 @@ static int run_group_staged(const KParams &kp, DeviceCtx &dc, std::vector<AggSeg
         }
         if (!(s.fast == 2 && s.plan.d_out24))
             if (int e = launch_gather_outputs(s.d_pairs, (int32_t *)s.d_stage.p, N, s.stream)) return e;
-        BSW_TRY(hipMemcpyAsync(s.h_stage, s.d_stage, (size_t)N * 24, hipMemcpyDeviceToHost, s.stream));
+        BSW_TRY(hipMemcpyAsync(s.h_stage, s.d_stage, (size_t)N * kOutBytes, hipMemcpyDeviceToHost, s.stream));
         // the leader polls its batch (~0.3 ms) instead of the runtime's blocking wait: 8 callers x 1K
         // coalesced 11.4 / 12.4 -> 14.1 / 13.5 M/s (same box, alternating; profiles/r05/slot_ownq_percall.txt)
         if ((r = finish_stats(s, true))) return r;
@@ -1052,10 +904,7 @@ static int run_group_staged(const KParams &kp, DeviceCtx &dc, std::vector<AggSeg
         auto scatter = [&](int g) {
             SeqPair *p = segs[g].r->pairs;
             const int32_t *q = out + 6 * (int64_t)segs[g].p_off;
-            for (int32_t i = 0; i < segs[g].r->n; ++i, q += 6) {
-                p[i].score = q[0]; p[i].tle = q[1]; p[i].gtle = q[2];
-                p[i].qle = q[3]; p[i].gscore = q[4]; p[i].max_off = q[5];
-            }
+            for (int32_t i = 0; i < segs[g].r->n; ++i, q += 6) put_outputs(p[i], q);
         };
         // a few thousand records: on this thread (waking the host pool costs more than the copy)
         if (N <= 16384)

@@ -1,4 +1,5 @@
-// bsw_pool.h -- the engine's host worker pool (host-buffer staging, packing, scans).
+// bsw_pool.h -- the engine's host worker pool (host-buffer staging, packing, scans) and the
+// one-thread job queue of the host pipeline (Worker, below).  Host-only: no HIP header.
 //
 // One process-wide pool of workers() threads, created on first use (the process's CPU share
 // minus the caller: the cgroup CPU quota when one is set, else the affinity set; 2..32 lanes).  parallel_for(n, fn) runs
@@ -115,6 +116,60 @@ private:
     std::deque<std::function<void()>> q_;
     std::vector<std::thread> th_;
     bool stop_ = false;
+};
+
+// One thread with a FIFO of jobs (the host pipeline's launcher and enqueuer, bsw_pipeline.hip):
+// start(handler, on_start) runs on_start() once on the new thread, then handler(job) for every
+// pushed job in order, outside the lock.  stop() lets the queue drain -- every job pushed before it
+// is handled -- and then joins; on a worker never started, or twice, it does nothing.
+template <class Job>
+class Worker {
+public:
+    Worker() = default;
+    Worker(const Worker &) = delete;
+    Worker &operator=(const Worker &) = delete;
+    ~Worker() { stop(); }
+    void start(std::function<void(Job &)> handler, std::function<void()> on_start = nullptr)
+    {
+        th_ = std::thread([this, handler, on_start] {
+            if (on_start) on_start();
+            for (;;) {
+                Job job;
+                {
+                    std::unique_lock<std::mutex> lk(mu_);
+                    cv_.wait(lk, [this] { return stop_ || !q_.empty(); });
+                    if (q_.empty()) return;
+                    job = std::move(q_.front());
+                    q_.pop_front();
+                }
+                handler(job);
+            }
+        });
+    }
+    void push(Job job)
+    {
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            q_.push_back(std::move(job));
+        }
+        cv_.notify_one();
+    }
+    void stop()
+    {
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            stop_ = true;
+        }
+        cv_.notify_one();
+        if (th_.joinable()) th_.join();
+    }
+
+private:
+    std::mutex mu_;
+    std::condition_variable cv_;
+    std::deque<Job> q_;
+    bool stop_ = false;
+    std::thread th_;
 };
 
 // memcpy split over the pool when large (staging into / out of pinned memory)

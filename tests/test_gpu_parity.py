@@ -296,7 +296,7 @@ def test_host_pipeline_chunks(chunk):
 
 @pytest.mark.parametrize("chunk", [4096, 65536, 262144])
 def test_host_pipeline_chunks_equal_oracle(chunk, c2_full):
-    """The host pipeline (bsw_host.cpp host_shard: 2-bit staging, H2D, device unpack / plan / sort,
+    """The host pipeline (bsw_pipeline.hip host_shard: 2-bit staging, H2D, device unpack / plan / sort,
     DP, 24-B outputs back) over contiguous C2 batches with extra N bases, empty sequences and the
     8-bit regime's edge h0 values, in 1 to ~75 chunks (chunks of <= 32K pairs take the row-group
     kernel); outputs equal the oracle and only the six output fields change."""

@@ -7,6 +7,10 @@
 //                    at the 2^30-byte bound, cap < total_bytes and bad records rejected
 //   bsw_internal.h   BlobLayout (the staged blob of the stages' host-array forms): offsets aligned,
 //                    parts disjoint, total and offsets as the recurrence they replace
+//   bsw_stage_plan.h stage_layout (every staging mode; offsets aligned, parts disjoint with their pad
+//                    bytes, the reserve covers every exception count, offsets and totals as the formulas
+//                    they replace in the pipeline and in bsw_pack_batch), the exception bucket count,
+//                    first_chunk_blocks and chunk_schedule == the loop they replace
 //   bsw_batch.c      .bswb write / read round trip, truncated and corrupted files rejected
 //   bsw_synth.c      every generator
 //   bsw_ext.cpp      bsw_extend_seeds (chunked) and bsw_chain2aln through an oracle-backed engine
@@ -25,6 +29,7 @@
 #include "../../include/bsw_ext.h"
 #include "../../include/bsw_fmi.h"
 #include "../../bwa-mem2-arm_amd/csrc/bsw_internal.h"
+#include "../../bwa-mem2-arm_amd/csrc/bsw_stage_plan.h"
 
 extern "C" {
 bsw_ctx_t *stub_ctx_create(const bsw_params_t *p);
@@ -78,8 +83,10 @@ int64_t oracle_mem_chain(const bsw_chain_opt_t *opt, const int64_t *sa, int64_t 
 }
 
 static int g_fail = 0;
+static long g_checks = 0;
 #define CHECK(c, ...)                                                    \
     do {                                                                 \
+        ++g_checks;                                                      \
         if (!(c)) {                                                      \
             fprintf(stderr, "CHECK failed %s:%d: ", __FILE__, __LINE__); \
             fprintf(stderr, __VA_ARGS__);                                \
@@ -301,6 +308,145 @@ static void test_blob_layout()
     }
 }
 
+// stage_layout against the formulas it replaced (kept here as literals): stage_2bit / stage_chunk /
+// SlotReserve::add / run_group_staged of the host pipeline and bsw_pack_batch's wire form
+static void test_stage_layout()
+{
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t ns[] = {0, 1, 63, 64, 4096, 4097, 196608};
+    // (252, 253, 506, 1012: the codes + 4 pad bytes end at and just past a 256-byte boundary in some mode)
+    const size_t bytes[] = {0, 1, 3, 4, 5, 252, 253, 255, 256, 257, 506, 1012, ((size_t)1 << 20) + 1, ((size_t)1 << 30) - 1};
+    const int modes[] = {bsw::kStageGather, bsw::kStageNibble, bsw::kStage2bit};
+    for (int mode : modes)
+        for (size_t n : ns)
+            for (size_t rb : bytes)
+                for (size_t qb : bytes) {
+                    const size_t cap = (rb + qb) / 32 + 1024;
+                    CHECK(bsw::exc_cap(rb, qb) == cap, "exc_cap(%zu, %zu)", rb, qb);
+                    const bsw::ExcBuckets nb = bsw::exc_buckets((int64_t)rb, (int64_t)qb);
+                    CHECK(nb.nbr == (int64_t)((rb + 4095) / 4096 + 1) && nb.nbq == (int64_t)((qb + 4095) / 4096 + 1) &&
+                          nb.total() == (rb + 4095) / 4096 + (qb + 4095) / 4096 + 2, "exc_buckets(%zu, %zu)", rb, qb);
+                    const size_t per = mode == bsw::kStage2bit ? 4 : mode == bsw::kStageNibble ? 2 : 1;
+                    const size_t rec = mode == bsw::kStage2bit ? 20 : 56;
+                    const size_t rs = (rb + per - 1) / per, qs = (qb + per - 1) / per;
+                    const size_t reserve = bsw::stage_layout(mode, n, rb, qb, mode == bsw::kStage2bit ? cap : 0).bytes;
+                    const size_t old_reserve =
+                        mode == bsw::kStage2bit
+                            ? std::max(al(al(al(n * 20) + (rb + 3) / 4 + 4) + (qb + 3) / 4 + 4) + ((rb + qb) / 32 + 1024) * 4, n * 24)
+                            : mode == bsw::kStageNibble ? al(al(n * 56) + (rb + 1) / 2 + 4) + (qb + 1) / 2 + 4
+                                                        : al(al(n * 56) + rb + 4) + qb + 4;
+                    CHECK(reserve == old_reserve, "mode %d n %zu rb %zu qb %zu: reserve %zu, was %zu", mode, n, rb, qb,
+                          reserve, old_reserve);
+                    const size_t excs[] = {0, 1, cap};
+                    for (size_t e : excs) {
+                        if (mode != bsw::kStage2bit && e != 0) continue;        // only the 2-bit form has exceptions
+                        const bsw::StageLayout l = bsw::stage_layout(mode, n, rb, qb, e);
+                        CHECK(l.pair_off % 256 == 0 && l.ref_off % 256 == 0 && l.qer_off % 256 == 0 && l.exc_off % 256 == 0,
+                              "mode %d n %zu rb %zu qb %zu: an offset is not 256-aligned", mode, n, rb, qb);
+                        CHECK(l.ref_len == rs && l.qer_len == qs && l.ref_len * per >= rb && l.qer_len * per >= qb,
+                              "mode %d rb %zu qb %zu: staged code bytes", mode, rb, qb);
+                        CHECK(l.pair_off == 0 && l.pair_off + n * rec <= l.ref_off && l.ref_off + rs + 4 <= l.qer_off &&
+                              l.qer_off + qs + 4 <= l.exc_off, "mode %d n %zu rb %zu qb %zu: parts overlap", mode, n, rb, qb);
+                        CHECK(l.ref_off == al(n * rec) && l.qer_off == al(l.ref_off + rs + 4), "mode %d n %zu: offsets", mode, n);
+                        CHECK(reserve >= l.bytes, "mode %d n %zu rb %zu qb %zu e %zu: staging %zu > reserve %zu", mode, n, rb,
+                              qb, e, l.bytes, reserve);
+                        if (mode == bsw::kStage2bit) {
+                            CHECK(l.bytes >= 24 * n && l.bytes >= l.exc_off + 4 * e && l.bytes == std::max(l.exc_off + 4 * e, n * 24),
+                                  "2-bit n %zu rb %zu qb %zu e %zu: staging bytes %zu", n, rb, qb, e, l.bytes);
+                            // the wire form (bsw_pack_batch) as it was written there, in int64
+                            auto a64 = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
+                            const int64_t w_ref = a64((int64_t)n * 20), w_qer = a64(w_ref + ((int64_t)rb + 3) / 4 + 4);
+                            const int64_t w_exc = a64(w_qer + ((int64_t)qb + 3) / 4 + 4), w_tot = a64(w_exc + 4 * (int64_t)e);
+                            CHECK((int64_t)l.ref_off == w_ref && (int64_t)l.qer_off == w_qer && (int64_t)l.exc_off == w_exc &&
+                                  (int64_t)l.wire_bytes == w_tot, "wire form n %zu rb %zu qb %zu e %zu", n, rb, qb, e);
+                        } else {
+                            CHECK(l.bytes == l.qer_off + qs + 4, "mode %d: staging ends after the qer pad", mode);
+                        }
+                    }
+                }
+    // bsw_pack_batch itself still reports those offsets
+    SeqPair p[2];
+    memset(p, 0, sizeof(p));
+    p[0].len1 = 300; p[0].len2 = 151; p[1].idr = 300; p[1].idq = 151; p[1].len1 = 257; p[1].len2 = 5;
+    std::vector<uint8_t> r(557, 1), q(156, 2);
+    r[5] = 4; q[7] = 4; q[9] = 4;
+    bsw_packed_t d;
+    CHECK(bsw_pack_batch(p, r.data(), q.data(), 2, nullptr, 0, &d) == BSW_OK, "pack_batch sizes");
+    CHECK(d.rec_off == 0 && d.ref_off == 256 && d.qer_off == 512 && d.exc_off == 768 && d.total_bytes == 1024 &&
+          d.n_exc_ref == 1 && d.n_exc_qer == 2, "pack_batch offsets %lld %lld %lld %lld", (long long)d.ref_off,
+          (long long)d.qer_off, (long long)d.exc_off, (long long)d.total_bytes);
+}
+
+// chunk_schedule / first_chunk_blocks against the loop they replaced in host_shard (kept here)
+static void test_chunk_schedule()
+{
+    const int32_t blocks[] = {1, 2, 16, 17, 32, 33, 48, 245, 733};
+    const int32_t chunks[] = {1, 4096, 8192, 65536, 196608, 262144, 1 << 20};
+    // bytes per block: 1.8 MB; 96 MB; 1.8 MB with one block of 600 MB; 128 MB (four are exactly 2^29)
+    for (int pat = 0; pat < 4; ++pat)
+        for (int32_t nblk : blocks)
+            for (int32_t chunk : chunks) {
+                std::vector<bsw::BlkStat> bs((size_t)nblk, bsw::BlkStat{0, 0, 0, 0, 1200000, 600000, false});
+                if (pat == 1)
+                    for (auto &b : bs) { b.r_sum = (int64_t)64 << 20; b.q_sum = (int64_t)32 << 20; }
+                if (pat == 2) bs[(size_t)nblk / 2].r_sum = (int64_t)600 << 20;
+                if (pat == 3)
+                    for (auto &b : bs) b.r_sum = b.q_sum = (int64_t)1 << 26;
+                const int32_t cap_blk = std::max<int32_t>(1, chunk / 4096);
+                const int32_t first = bsw::first_chunk_blocks(nblk, chunk, 16);
+                CHECK(first == std::min(cap_blk, nblk <= 32 ? nblk : std::max<int32_t>(16, nblk / 32)) && first >= 1,
+                      "first_chunk_blocks(%d, %d) = %d", nblk, chunk, first);
+                const std::vector<bsw::ChunkRange> chs = bsw::chunk_schedule(bs, chunk, first);
+                std::vector<std::pair<int32_t, int32_t>> old;
+                for (int32_t b = 0, nb = 0, cur = first; b < nblk; b += nb, cur = std::min(cap_blk, cur * 2)) {
+                    int64_t bytes = 0;
+                    for (nb = 0; nb < cur && b + nb < nblk; ++nb) {
+                        const int64_t x = bs[(size_t)(b + nb)].r_sum + bs[(size_t)(b + nb)].q_sum;
+                        if (nb > 0 && bytes + x > ((int64_t)1 << 29)) break;
+                        bytes += x;
+                    }
+                    old.emplace_back(b, nb);
+                }
+                bool same = old.size() == chs.size();
+                for (size_t k = 0; same && k < chs.size(); ++k) same = chs[k].b == old[k].first && chs[k].nb == old[k].second;
+                CHECK(same, "pattern %d, %d blocks, chunk %d: not the old loop's list", pat, nblk, chunk);
+                int32_t at = 0, want = first;
+                for (size_t k = 0; k < chs.size(); ++k, want = std::min(cap_blk, want * 2)) {
+                    const bsw::ChunkRange &c = chs[k];
+                    CHECK(c.b == at && c.nb >= 1 && c.nb <= cap_blk, "pattern %d, %d blocks, chunk %d: chunk %zu = (%d, %d)",
+                          pat, nblk, chunk, k, c.b, c.nb);
+                    int64_t bytes = 0;
+                    for (int32_t j = 0; j < c.nb; ++j) bytes += bs[(size_t)(c.b + j)].r_sum + bs[(size_t)(c.b + j)].q_sum;
+                    CHECK(c.nb == 1 || bytes <= ((int64_t)1 << 29), "pattern %d, %d blocks, chunk %d: chunk %zu holds %lld bytes",
+                          pat, nblk, chunk, k, (long long)bytes);
+                    // sizes start at first_blk and double to the cap: exactly so where the byte cut never
+                    // binds (the last chunk takes what is left), never more anywhere
+                    CHECK(c.nb <= want && (pat != 0 || c.nb == std::min(want, nblk - at)),
+                          "pattern %d, %d blocks, chunk %d: chunk %zu has %d blocks, the ramp gives %d", pat, nblk, chunk, k,
+                          c.nb, want);
+                    if (pat == 1) CHECK(c.nb <= 5, "96 MB blocks: %d in one chunk", c.nb);
+                    if (pat == 3 && want >= 4 && nblk - at >= 4) CHECK(c.nb == 4, "128 MB blocks: %d in one chunk", c.nb);
+                    at += c.nb;
+                    if (c.nb < 1) break;
+                }
+                CHECK(at == nblk, "pattern %d, %d blocks, chunk %d: the chunks cover %d blocks", pat, nblk, chunk, at);
+                // every chunk's pairs for a call whose last block is partial
+                const int32_t n = nblk * 4096 - 4095;
+                int32_t tot = 0;
+                for (const bsw::ChunkRange &c : chs) tot += bsw::chunk_pairs(c, n);
+                CHECK(tot == n, "chunk_pairs sum %d != %d", tot, n);
+            }
+    // stage_mode: bulk extents go 2-bit below 2^30 bytes, nibbles at it or with 2-bit off; scattered ones gather
+    size_t rb, qb;
+    const int64_t lim = (int64_t)1 << 30;
+    CHECK(bsw::stage_mode(bsw::BlkStat{0, lim - 1, 0, 100, lim - 1, 100, false}, true, &rb, &qb) == bsw::kStage2bit &&
+          rb == (size_t)lim - 1 && qb == 100, "2-bit below 2^30");
+    CHECK(bsw::stage_mode(bsw::BlkStat{0, lim, 0, 100, lim, 100, false}, true, &rb, &qb) == bsw::kStageNibble, "nibbles at 2^30");
+    CHECK(bsw::stage_mode(bsw::BlkStat{0, 1000, 0, 100, 1000, 100, false}, false, &rb, &qb) == bsw::kStageNibble, "2-bit off");
+    CHECK(bsw::stage_mode(bsw::BlkStat{0, 100000, 0, 100, 1000, 100, false}, true, &rb, &qb) == bsw::kStageGather &&
+          rb == 1000 && qb == 100, "scattered extents gather their sums");
+}
+
 static void test_batch_file()
 {
     bsw_params_t p;
@@ -465,8 +611,11 @@ int main()
     test_pack();
     test_pack_batch();
     test_blob_layout();
+    test_stage_layout();
+    test_chunk_schedule();
     test_batch_file();
     test_extension_and_synth();
+    printf("asan_driver: %ld checks\n", g_checks);
     printf("asan_driver: %s (%d failed checks)\n", g_fail ? "FAIL" : "ok", g_fail);
     return g_fail ? 1 : 0;
 }

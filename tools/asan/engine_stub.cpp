@@ -47,6 +47,12 @@ int scores_eb(bsw_ctx_t *ctx, int32_t end_bonus, SeqPair *pairs, const uint8_t *
 void ctx_params(const bsw_ctx_t *ctx, bsw_params_t *out) { *out = ctx->params; }
 int ctx_device(const bsw_ctx_t *) { return 0; }
 int64_t ctx_refres_len(bsw_ctx_t *) { return -1; }
+int ctx_contigs(bsw_ctx_t *, int64_t l_pac, int64_t, ContigView *dev, std::vector<int64_t> *host_off)   // no table
+{
+    if (dev) *dev = ContigView{nullptr, nullptr, nullptr, 0, l_pac};
+    if (host_off) host_off->clear();
+    return BSW_OK;
+}
 void *pinned_acquire(bsw_ctx_t *, int, size_t) { return nullptr; }     // builder falls back to heap
 void pinned_release(bsw_ctx_t *, int) {}
 void set_ext_stats(bsw_ctx_t *ctx, const bsw_ext_stats_t &s) { std::lock_guard<std::mutex> g(ctx->mu); ctx->ext = s; }

@@ -106,17 +106,17 @@ for step in "$@"; do
             done
         done ;;
     hptrace)
-        # the drop-in host path's timeline: per-chunk host times (BSW_DEBUG_HP) and a kernel +
+        # the drop-in host path's timeline: a kernel +
         # copy trace of a few 1M-pair bsw_get_scores calls (tools/host_path_once.py [chunk] [calls])
         rm -rf "$O/hptrace"
-        BSW_DEBUG_HP=1 timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv \
+        timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv \
             -d "$O/hptrace" -- python3 tools/host_path_once.py ${arg:-262144} 4 > "$O/hptrace.log" 2>&1 \
             || fail "$step" $? "$O/hptrace.log"
         grep '^call' "$O/hptrace.log" ;;
     hpapi)
         # hptrace plus the HIP runtime API trace (per-thread host timeline of every runtime call)
         rm -rf "$O/hpapi"
-        BSW_DEBUG_HP=1 timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --hip-runtime-trace --output-format csv \
+        timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --hip-runtime-trace --output-format csv \
             -d "$O/hpapi" -- python3 tools/host_path_once.py ${arg:-262144} 4 > "$O/hpapi.log" 2>&1 \
             || fail "$step" $? "$O/hpapi.log"
         grep '^call' "$O/hpapi.log" ;;
