@@ -133,6 +133,59 @@ def pairs_from_shapes(shapes, seed, p_unrelated=0.2):
     return assemble(items)
 
 
+def gap_pairs(w, n_per_cell, seed, flank, after, h0, kinds=("del", "ins"), p_sub=0.0):
+    """Band-edge pairs: one gap of g bases between two matching flanks, g = w - 1, w, w + 1, so
+    the best path runs on cells with |j - i| = g -- inside the band, on its edge, one past it.
+    "del": target a + x + b + tail, query a + b; "ins": target a + b + tail, query a + x + b;
+    |a| = flank, |x| = g, |b| = g + after (long enough to pay for the gap), |tail| = 40, random
+    bases; p_sub substitutes query bases.  n_per_cell pairs per (g, kind), all at `h0`.
+    Returns (pairs, ref, qer, meta) with meta[k] = (g, kind)."""
+    rng = np.random.default_rng(seed)
+    items, meta = [], []
+    for g in (w - 1, w, w + 1):
+        for kind in kinds:
+            for _ in range(n_per_cell):
+                a = rng.integers(0, 4, flank).astype(np.uint8)
+                x = rng.integers(0, 4, g).astype(np.uint8)
+                b = rng.integers(0, 4, g + after).astype(np.uint8)
+                tail = rng.integers(0, 4, 40).astype(np.uint8)
+                if kind == "del":
+                    r, q = np.concatenate([a, x, b, tail]), np.concatenate([a, b])
+                elif kind == "ins":
+                    r, q = np.concatenate([a, b, tail]), np.concatenate([a, x, b])
+                else:
+                    raise ValueError(kind)
+                if p_sub:
+                    hit = rng.random(len(q)) < p_sub
+                    q[hit] = (q[hit] + rng.integers(1, 4, int(hit.sum())).astype(np.uint8)) & 3
+                items.append((r, q, int(h0)))
+                meta.append((g, kind))
+    return assemble(items) + (meta,)
+
+
+def late_front_pairs(w, win, n, seed, extra=60):
+    """Pairs whose band end grows back, two columns a row and below the band edge, over columns
+    >= win that no earlier row wrote and whose first-row value is still positive (default
+    scoring with zdrop = 0; needs w >= 0.4 win).  The target opens with J bases the query does not
+    hold (base 0 against a query over 1..3): every path loses at least 2 a row, the right band
+    edge dies at row k0 ~ (h0 - w - 12) / 2 having written slots up to k0 + w + 1 ~ win, and
+    the end falls back a column a row.  Then the target follows the query along a diagonal 20
+    columns left of the end: the score there rises 1 a row, its insertion tail reaches 2 columns
+    further a row and walks over the unwritten slots.  qlen = win + extra puts column qlen inside
+    that stretch, so gscore is made of first-row values.  Returns (pairs, ref, qer)."""
+    rng = np.random.default_rng(seed)
+    items = []
+    for _ in range(n):
+        k0 = win - w + int(rng.integers(0, 8))
+        h0 = 2 * k0 + w + 12
+        J = k0 + (2 * w) // 5
+        s = h0 - 32 - 2 * J                      # the diagonal j = i + s starts at score ~20
+        q = rng.integers(1, 4, win + extra).astype(np.uint8)
+        r = np.concatenate([np.zeros(J, np.uint8), q[J + s:], rng.integers(1, 4, 40).astype(np.uint8)])
+        items.append((r, q, h0))
+    return assemble(items)
+
+
 def repeat_pairs(n, seed, L=(20, 160), h0=(1, 120)):
     """Tandem repeats (period 1..6 motifs, microsatellites) with light mutation: equal-score
     paths everywhere, so the last-index tie rules (row max mj, gscore's max_ie) decide."""
