@@ -7,8 +7,8 @@
 //                      (its planning -- staging layout, chunk schedule, kStageBlk -- in bsw_stage_plan.h)
 //   bsw_host.cpp     : contexts, recovery, mate / global / extension wrappers, options, the core C ABI
 //   bsw_stages.cpp   : the stages behind the extension (final alignments, region selection, the
-//                      paired-end stage, mate rescue, SAM records), both forms of each, on shared call
-//                      helpers
+//                      paired-end stage, mate rescue, SAM records, BGZF), both forms of each, on shared
+//                      call helpers
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -31,6 +31,7 @@
 #include "../../include/bsw_matesw.h"
 #include "../../include/bsw_rec.h"
 #include "../../include/bsw_bam.h"
+#include "../../include/bsw_bgzf.h"
 #include "../../include/bsw_contigs.h"
 #include "bsw_contig_seg.h"
 #include "bsw_kernels.h"
@@ -238,6 +239,11 @@ struct BSW_HIDDEN Slot {
     DevBuf<int32_t> d_rread;            // their reads
     DevBuf<int64_t> d_rlen;             // text: the lines' lengths, n_rec + 1
     DevBuf<int32_t> d_rmeta;            // kRecMetaWords
+    // BGZF (bsw_bgzf.h); its scan uses d_tmp, its host form stages in d_aio, its kernels are timed with evw0 / evw1
+    DevBuf<uint8_t> d_bstage;           // the blocks as compressed, 64 KB each
+    DevBuf<uint16_t> d_btok;            // the deflate kernel's tokens, per workgroup
+    DevBuf<int64_t> d_bsize;            // the blocks' sizes, n_blocks + 1
+    DevBuf<int32_t> d_bmeta;            // kBgzfMetaWords
     bool timed = false;
     hipStream_t run_stream = nullptr;   // stream of the last run_device (finish_stats waits on it)
     bsw_stats_t stats{};
@@ -435,6 +441,7 @@ struct bsw_ctx {
     bsw_matesw_stats_t matesw_last{};
     bsw_rec_stats_t rec_last{};
     bsw_bam_stats_t bam_last{};
+    bsw_bgzf_stats_t bgzf_last{};
     struct Pinned { std::mutex mu; bsw::PinnedBuf<uint8_t> b; } pin[2];
     int glob_band = 0;                  // BSW_OPT_GLOB_BAND
     int64_t ext_chunk = 0;              // BSW_OPT_EXT_CHUNK (0: the int32-offset bound)

@@ -1,8 +1,8 @@
 // bsw_stages.cpp -- the stages behind the extension, each in a device-resident form and a
 // host-array form behind the C ABI: final alignments (bsw_aln.h), region selection (bsw_sel.h),
-// the paired-end stage (bsw_pe.h), mate rescue (bsw_matesw.h) and SAM records (bsw_rec.h).  Their
-// kernels are in bsw_aln.hip, bsw_sel.hip, bsw_pe.hip, bsw_matesw.hip and bsw_rec.hip; what the calls
-// share is below.
+// the paired-end stage (bsw_pe.h), mate rescue (bsw_matesw.h), SAM records (bsw_rec.h) and BGZF
+// (bsw_bgzf.h).  Their kernels are in bsw_aln.hip, bsw_sel.hip, bsw_pe.hip, bsw_matesw.hip, bsw_rec.hip and
+// bsw_bgzf.hip; what the calls share is below.
 // (Layout of the engine: bsw_engine.h.)
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -18,6 +18,7 @@
 #include "bsw_pe_k.h"
 #include "bsw_matesw_k.h"
 #include "bsw_rec_k.h"
+#include "bsw_bgzf_k.h"
 #include "bsw_stage_k.h"
 
 // ---------------------------------------------------------------- shared by the stages
@@ -1294,6 +1295,65 @@ static void put_out_stats(RecForm form, bsw_ctx_t *ctx, int32_t n_rec, int64_t n
     }
 }
 
+// ---------------------------------------------------------------- BGZF (bsw_bgzf.h)
+static int bgzf_check_args(const bsw_bgzf_opt_t *opt, int64_t n_in, int32_t n_rec, int64_t out_cap, int32_t blk_cap)
+{
+    if (!opt || n_in < 0 || n_rec < 0 || out_cap < 0 || blk_cap < 0) return BSW_E_INVAL;
+    if (opt->level < 0 || opt->level > 1 || (opt->flags & ~BSW_BGZF_EOF)) return BSW_E_INVAL;
+    if (opt->block_bytes < 1 || opt->block_bytes > BSW_BGZF_MAX_BLOCK) return BSW_E_INVAL;
+    return (n_in + opt->block_bytes - 1) / opt->block_bytes > INT32_MAX - 1 ? BSW_E_RANGE : BSW_OK;
+}
+
+// clear the staging -> deflate -> sizes scanned into blk_off -> virtual offsets -> one readback (total, error
+// word, form counts) -> compaction into out.  bs.n_blocks and bs.n_in are set by the caller
+static int bgzf_device(Slot &s, hipStream_t st, const bsw_bgzf_opt_t &opt, const uint8_t *d_in, const int64_t *d_rec_off,
+                       int32_t n_rec, uint8_t *d_out, int64_t out_cap, int64_t *d_blk_off, int64_t *d_voff,
+                       int64_t *n_bytes, bsw_bgzf_stats_t &bs)
+{
+    const int32_t nb = bs.n_blocks;
+    const bool eof = (opt.flags & BSW_BGZF_EOF) != 0;
+    const int32_t grid = std::min<int32_t>(nb, kBgzfGrid);
+    *n_bytes = 0;
+    size_t scan_bytes = 0;
+    BSW_TRY(launch_scan64(nullptr, &scan_bytes, nullptr, nullptr, nb, st));
+    BSW_TRY(s.d_tmp.grow(std::max<size_t>(scan_bytes, 16)));
+    BSW_TRY(s.d_bsize.grow((size_t)nb + 1));
+    BSW_TRY(s.d_bmeta.grow(kBgzfMetaWords));
+    BSW_TRY(s.d_bstage.grow(std::max<size_t>((size_t)nb, 1) * bgzf::kStageStride));
+    BSW_TRY(s.d_btok.grow(std::max<size_t>((size_t)grid, 1) * bgzf::kTokPerBlock));
+    HelperTimer tm;
+    BSW_TRY(tm.init(s.evw0, s.evw1, st));
+    static_assert(kBgzfMetaWords + 2 <= kMetaWords, "the slot's pinned mirror holds the meta words and the total");
+    int64_t *h_tot = (int64_t *)(s.h_meta + kBgzfMetaWords);
+    BSW_TRY(hipMemsetAsync(s.d_bmeta, 0, kBgzfMetaWords * sizeof(int32_t), st));
+    BSW_TRY(tm.begin());
+    if (nb > 0) BSW_TRY(hipMemsetAsync(s.d_bstage, 0, (size_t)nb * bgzf::kStageStride, st));
+    BSW_TRY(launch_bgzf_deflate(d_in, bs.n_in, opt.block_bytes, nb, opt.level, s.d_bstage, s.d_btok, grid, s.d_bsize,
+                                s.d_bmeta, st));
+    if (nb == 0) BSW_TRY(hipMemsetAsync(s.d_bsize, 0, sizeof(int64_t), st));
+    BSW_TRY(launch_scan64(s.d_tmp, &scan_bytes, s.d_bsize, d_blk_off, nb, st));
+    BSW_TRY(launch_bgzf_voff(d_rec_off, n_rec, bs.n_in, opt.block_bytes, d_blk_off, opt.base_coffset, d_voff, s.d_bmeta, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipMemcpyAsync(s.h_meta, s.d_bmeta, kBgzfMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_tot, d_blk_off + nb, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(bs.deflate_ms));
+    if (s.h_meta[kBgzfErr]) return BSW_E_RANGE;
+    bs.n_stored = s.h_meta[kBgzfStored + bgzf::kStored];
+    bs.n_fixed = s.h_meta[kBgzfStored + bgzf::kFixed];
+    bs.n_dynamic = s.h_meta[kBgzfStored + bgzf::kDynamic];
+    *n_bytes = bs.n_out = *h_tot + (eof ? bgzf::kEofBytes : 0);
+    if (*n_bytes > out_cap) return BSW_E_RANGE;
+    if (nb > 0 || eof) {
+        BSW_TRY(tm.begin());
+        BSW_TRY(launch_bgzf_pack(s.d_bstage, d_blk_off, nb, eof, d_out, st));
+        BSW_TRY(tm.end());
+        BSW_TRY(hipStreamSynchronize(st));
+        BSW_TRY(tm.add(bs.pack_ms));
+    }
+    return BSW_OK;
+}
+
 }  // namespace bsw
 
 extern "C" {
@@ -1608,5 +1668,81 @@ int bsw_bam_header(bsw_ctx_t *ctx, const bsw_rec_opt_t *opt, const char *sam_tex
 }
 
 int bsw_bam_last_stats(bsw_ctx_t *ctx, bsw_bam_stats_t *out) { return bsw::get_stats(ctx, &bsw_ctx::bam_last, out); }
+
+// ---------------------------------------------------------------- BGZF (include/bsw_bgzf.h)
+void bsw_bgzf_opt_default(bsw_bgzf_opt_t *opt)
+{
+    if (!opt) return;
+    memset(opt, 0, sizeof(*opt));
+    opt->level = 1;
+    opt->block_bytes = BSW_BGZF_MAX_BLOCK;
+}
+
+int bsw_bgzf_resident(bsw_ctx_t *ctx, const bsw_bgzf_opt_t *opt, const uint8_t *d_in, int64_t n_in,
+                      const int64_t *d_rec_off, int32_t n_rec, uint8_t *d_out, int64_t out_cap, int64_t *d_blk_off,
+                      int32_t blk_cap, int64_t *d_voff, int32_t *n_blocks, int64_t *n_bytes, void *stream)
+{
+    if (const int rc = bsw::bgzf_check_args(opt, n_in, n_rec, out_cap, blk_cap)) return rc;
+    if (!ctx || !n_blocks || !n_bytes || !d_blk_off || (n_in > 0 && !d_in) || (out_cap > 0 && !d_out) ||
+        (n_rec > 0 && (!d_rec_off || !d_voff)) || ((uintptr_t)d_out & 3))
+        return BSW_E_INVAL;
+    bsw_bgzf_stats_t bs{};
+    bs.n_in = n_in;
+    *n_blocks = bs.n_blocks = (int32_t)((n_in + opt->block_bytes - 1) / opt->block_bytes);
+    *n_bytes = 0;
+    if (blk_cap < bs.n_blocks + 1) return BSW_E_RANGE;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::bgzf_device(s, st, *opt, d_in, d_rec_off, n_rec, d_out, out_cap, d_blk_off, d_voff, n_bytes, bs);
+    });
+    if (rc) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::bgzf_last, bs);
+    return BSW_OK;
+}
+
+int bsw_bgzf(bsw_ctx_t *ctx, const bsw_bgzf_opt_t *opt, const uint8_t *in, int64_t n_in, const int64_t *rec_off,
+             int32_t n_rec, uint8_t *out, int64_t out_cap, int64_t *blk_off, int32_t blk_cap, int64_t *voff,
+             int32_t *n_blocks, int64_t *n_bytes)
+{
+    if (const int rc = bsw::bgzf_check_args(opt, n_in, n_rec, out_cap, blk_cap)) return rc;
+    if (!ctx || !n_blocks || !n_bytes || !blk_off || (n_in > 0 && !in) || (out_cap > 0 && !out) ||
+        (n_rec > 0 && (!rec_off || !voff)))
+        return BSW_E_INVAL;
+    bsw_bgzf_stats_t bs{};
+    bs.n_in = n_in;
+    *n_blocks = bs.n_blocks = (int32_t)((n_in + opt->block_bytes - 1) / opt->block_bytes);
+    *n_bytes = 0;
+    if (blk_cap < bs.n_blocks + 1) return BSW_E_RANGE;
+    const size_t nb1 = (size_t)bs.n_blocks + 1, nr = (size_t)n_rec;
+    bsw::StagedIo io;
+    const auto d_in = io.in(in, (size_t)n_in);
+    const auto d_rec_off = io.in(rec_off, nr ? nr + 1 : 0);
+    const auto d_out = io.out(out, (size_t)out_cap);
+    const auto d_blk_off = io.out(blk_off, nb1);
+    const auto d_voff = io.out(voff, nr);
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(io.stage(s));
+        const int r = bsw::bgzf_device(s, s.stream, *opt, d_in, d_rec_off, n_rec, d_out, out_cap, d_blk_off, d_voff, n_bytes,
+                                       bs);
+        if (r == BSW_E_RANGE && *n_bytes > out_cap) {       // (the block starts and the offsets are still written)
+            BSW_TRY(io.back(d_blk_off));
+            BSW_TRY(io.back(d_voff));
+            BSW_TRY(hipStreamSynchronize(s.stream));
+        }
+        if (r) return r;
+        BSW_TRY(io.back(d_out, (size_t)*n_bytes));
+        BSW_TRY(io.back(d_blk_off));
+        BSW_TRY(io.back(d_voff));
+        BSW_TRY(hipStreamSynchronize(s.stream));
+        return BSW_OK;
+    });
+    if (rc) return rc;
+    bsw::put_stats(ctx, &bsw_ctx::bgzf_last, bs);
+    return BSW_OK;
+}
+
+int bsw_bgzf_last_stats(bsw_ctx_t *ctx, bsw_bgzf_stats_t *out) { return bsw::get_stats(ctx, &bsw_ctx::bgzf_last, out); }
 
 }  // extern "C"

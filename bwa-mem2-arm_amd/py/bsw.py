@@ -55,6 +55,9 @@ REC_SYMBOLS = ("bsw_rec_opt_default", "bsw_records", "bsw_records_resident", "bs
 CONTIGS_SYMBOLS = ("bsw_set_contigs", "bsw_fmi_set_contigs")
 # include/bsw_bam.h (additive likewise)
 BAM_SYMBOLS = ("bsw_bam_records", "bsw_bam_records_resident", "bsw_bam_header", "bsw_bam_last_stats")
+# include/bsw_bgzf.h (additive likewise: BSW_BGZF_API)
+BGZF_SYMBOLS = ("bsw_bgzf_opt_default", "bsw_bgzf", "bsw_bgzf_resident", "bsw_bgzf_last_stats")
+BGZF_MAX_BLOCK, BGZF_EOF = 0xff00, 1
 CONTIG_MAX_NAME = 63
 
 # include/bsw.h engine options (bsw_set_option)
@@ -257,6 +260,13 @@ def hip_lib():
         L.bsw_bam_header.argtypes = [P, P, P, i32, P, i64, P]
         L.bsw_bam_last_stats.argtypes = [P, P]
         for f in BAM_SYMBOLS:
+            getattr(L, f).restype = ctypes.c_int
+        L.bsw_bgzf_opt_default.argtypes = [P]
+        L.bsw_bgzf_opt_default.restype = None
+        L.bsw_bgzf.argtypes = [P, P, P, i64, P, i32, P, i64, P, i32, P, P, P]
+        L.bsw_bgzf_resident.argtypes = L.bsw_bgzf.argtypes + [P]
+        L.bsw_bgzf_last_stats.argtypes = [P, P]
+        for f in BGZF_SYMBOLS[1:]:
             getattr(L, f).restype = ctypes.c_int
         L.bsw_set_contigs.argtypes = [P, i32, P, ctypes.POINTER(ctypes.c_char_p)]
         L.bsw_set_contigs.restype = ctypes.c_int
@@ -1299,6 +1309,89 @@ def bam_header(engine, opt: RecOpt, sam_text: bytes = b"") -> bytes:
 def bam_last_stats(engine) -> BamStats:
     st = BamStats()
     _check(hip_lib().bsw_bam_last_stats(engine._ctx, ctypes.byref(st)))
+    return st
+
+
+# ---------------------------------------------------------------- BGZF (bsw_bgzf.h)
+class BgzfOpt(ctypes.Structure):
+    _fields_ = [("level", ctypes.c_int32), ("block_bytes", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_int32), ("base_coffset", ctypes.c_int64)]
+
+
+class BgzfStats(ctypes.Structure):
+    _fields_ = [("n_blocks", ctypes.c_int32), ("n_stored", ctypes.c_int32), ("n_fixed", ctypes.c_int32),
+                ("n_dynamic", ctypes.c_int32), ("n_in", ctypes.c_int64), ("n_out", ctypes.c_int64),
+                ("deflate_ms", ctypes.c_float), ("pack_ms", ctypes.c_float)]
+
+
+def bgzf_opt(**kw) -> BgzfOpt:
+    """bsw_bgzf_opt_default, then the given fields (level, block_bytes, flags, base_coffset)"""
+    o = BgzfOpt()
+    hip_lib().bsw_bgzf_opt_default(ctypes.byref(o))
+    for k, v in kw.items():
+        if k not in ("level", "block_bytes", "flags", "base_coffset"):
+            raise TypeError(f"bgzf_opt: no field '{k}'")
+        setattr(o, k, v)
+    return o
+
+
+def bgzf_blocks(n_in: int, opt: BgzfOpt) -> int:
+    return -(-n_in // opt.block_bytes)
+
+
+def bgzf_bound(n_in: int, opt: BgzfOpt) -> int:
+    """bytes that hold any input of n_in bytes: every block stored, the EOF marker"""
+    return n_in + 31 * bgzf_blocks(n_in, opt) + 28
+
+
+def bgzf(engine, data, opt: BgzfOpt | None = None, rec_off=None, out_cap: int | None = None, blk_cap: int | None = None):
+    """bsw_bgzf (host arrays): bytes -> (the BGZF blocks as bytes, blk_off int64 [n_blocks + 1], voff int64 [n_rec] or
+    None).  rec_off: n_rec + 1 offsets into data.  An out_cap below what is needed raises BswError with .needed,
+    .blk_off and .voff set; a blk_cap below n_blocks + 1 with .n_blocks set."""
+    opt = bgzf_opt() if opt is None else opt
+    data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data,
+                                dtype=np.uint8)
+    n_rec = 0 if rec_off is None else len(rec_off) - 1
+    rec_off = None if rec_off is None else np.ascontiguousarray(rec_off, dtype=np.int64)
+    nb = bgzf_blocks(len(data), opt)
+    out_cap = bgzf_bound(len(data), opt) if out_cap is None else out_cap
+    blk_cap = nb + 1 if blk_cap is None else blk_cap
+    out = np.zeros(max(out_cap, 1), dtype=np.uint8)
+    blk_off = np.zeros(max(blk_cap, 1), dtype=np.int64)
+    voff = np.zeros(max(n_rec, 1), dtype=np.int64)
+    n_blocks, n_bytes = ctypes.c_int32(-1), ctypes.c_int64(-1)
+    rc = hip_lib().bsw_bgzf(engine._ctx, ctypes.byref(opt), _ptr(data), len(data), None if rec_off is None else _ptr(rec_off),
+                            n_rec, _ptr(out), out_cap, _ptr(blk_off), blk_cap, _ptr(voff), ctypes.byref(n_blocks),
+                            ctypes.byref(n_bytes))
+    if rc != 0:
+        try:
+            _raise_needed(rc, n_bytes)
+        except BswError as e:
+            e.n_blocks, e.blk_off, e.voff = n_blocks.value, blk_off, voff[:n_rec]
+            raise
+    return out[:n_bytes.value].tobytes(), blk_off[:n_blocks.value + 1], (voff[:n_rec] if rec_off is not None else None)
+
+
+def bgzf_resident(engine, d_in: int, n_in: int, d_rec_off: int, n_rec: int, d_out: int, out_cap: int, d_blk_off: int,
+                  blk_cap: int, d_voff: int, opt: BgzfOpt, stream: int = 0):
+    """bsw_bgzf_resident: every array a device pointer.  Returns (n_blocks, n_bytes)."""
+    V = ctypes.c_void_p
+    n_blocks, n_bytes = ctypes.c_int32(-1), ctypes.c_int64(-1)
+    rc = hip_lib().bsw_bgzf_resident(engine._ctx, ctypes.byref(opt), V(d_in or None), n_in, V(d_rec_off or None), n_rec,
+                                     V(d_out or None), out_cap, V(d_blk_off or None), blk_cap, V(d_voff or None),
+                                     ctypes.byref(n_blocks), ctypes.byref(n_bytes), V(stream or None))
+    if rc != 0:
+        try:
+            _raise_needed(rc, n_bytes)
+        except BswError as e:
+            e.n_blocks = n_blocks.value
+            raise
+    return n_blocks.value, n_bytes.value
+
+
+def bgzf_last_stats(engine) -> BgzfStats:
+    st = BgzfStats()
+    _check(hip_lib().bsw_bgzf_last_stats(engine._ctx, ctypes.byref(st)))
     return st
 
 

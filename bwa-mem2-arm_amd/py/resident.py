@@ -1,6 +1,6 @@
 """ResidentBatch: the device arrays of one batch of reads and the resident stage chain over them,
 
-    seeds -> chain2aln -> select -> pe_stat -> matesw -> pe_pair -> reg2aln / records -> sam_text / bam_records
+    seeds -> chain2aln -> select -> pe_stat -> matesw -> pe_pair -> reg2aln / records -> sam_text / bam_records -> bgzf
 
 Plumbing for tests and tools, like bsw.py: every stage method is one bsw.*_resident call on the buffers the
 stage before left in HBM.  Importing this module loads no library and touches no device.
@@ -38,6 +38,8 @@ LAYOUT = {
 # the BAM form of the records (bsw_bam.h), rows of the same shape in a table of their own: LAYOUT's entries and
 # their item sizes are pinned one by one (tests/test_resident.py)
 BAM_LAYOUT = {"bam": (np.uint8, (), "bam"), "bam_off": (np.int64, (), "bam_off")}
+# the BGZF form of the BAM blocks (bsw_bgzf.h), in a table of its own likewise
+BGZF_LAYOUT = {"bgzf": (np.uint8, (), "bgzf"), "bgzf_blk": (np.int64, (), "bgzf_blk"), "bgzf_voff": (np.int64, (), "bgzf_voff")}
 FIXED = ("reads", "n_reads", "first")           # counts the constructor sets for good
 # (regs, read, info, first) as the extension, the selection and the rescue leave them
 LISTS = {"c": ("regs", "sr", None, None), "s": ("sreg", "sread", "sinfo", "sfirst"), "m": ("mreg", "mread", "minfo", "mfirst")}
@@ -46,9 +48,10 @@ LISTS = {"c": ("regs", "sr", None, None), "s": ("sreg", "sread", "sinfo", "sfirs
 def _row(name):
     """(dtype, stride keys, count key) of a buffer name"""
     pre, dot, base = name.rpartition(".")
-    if base not in LAYOUT and base not in BAM_LAYOUT:
+    table = next((t for t in (LAYOUT, BAM_LAYOUT, BGZF_LAYOUT) if base in t), None)
+    if table is None:
         raise ValueError(f"no buffer named '{name}'")
-    dtype, strides, key = LAYOUT[base] if base in LAYOUT else BAM_LAYOUT[base]
+    dtype, strides, key = table[base]
     return np.dtype(dtype), tuple(pre + dot + s for s in strides), pre + dot + key
 
 
@@ -248,3 +251,16 @@ class ResidentBatch:
         """the same records as BAM alignment blocks ("bam", "bam_off"); names=None reuses the uploaded names, so
         text and BAM of one batch come from one upload"""
         return self._records_out("bam_records", bsw.bam_records_resident, "bam", ropt, names, paired, cap)
+
+    def bgzf(self, bopt, cap=None):
+        """the BAM blocks ("bam", "bam_off") as BGZF blocks: "bgzf", the block starts "bgzf_blk" and the records'
+        virtual offsets "bgzf_voff".  cap=None: room for every block stored.  Returns (n_blocks, n_bytes)."""
+        self._have("bgzf", "bam", "bam_off")
+        n_in, n_rec = self.n["bam"], self.n["bam_off"] - 1
+        nb = bsw.bgzf_blocks(n_in, bopt)
+        cap = bsw.bgzf_bound(n_in, bopt) if cap is None else cap
+        out, blk, voff = self.alloc("bgzf", cap).ptr, self.alloc("bgzf_blk", nb + 1).ptr, self.alloc("bgzf_voff", n_rec).ptr
+        nb, n_bytes = bsw.bgzf_resident(self.engine, self.buf["bam"].ptr, n_in, self.buf["bam_off"].ptr, n_rec, out, cap,
+                                        blk, nb + 1, voff, bopt)
+        self.n["bgzf"], self.n["bgzf_blk"], self.n["bgzf_voff"] = n_bytes, nb + 1, n_rec
+        return nb, n_bytes

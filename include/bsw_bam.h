@@ -6,9 +6,9 @@
  * the specification; tests/bam_py.py pins it, and ties it to the text of bsw_rec.h by decoding the
  * blocks back into SAM lines.
  *
- * SCOPE as bsw_rec.h: no ALT contigs, no -a, no RG tag, no comment.  BGZF compression, file I/O and
- * the command line are the caller's: the header block (bsw_bam_header) followed by the records of
- * any number of calls is an uncompressed BAM stream, which the caller cuts into BGZF blocks.
+ * SCOPE as bsw_rec.h: no ALT contigs, no -a, no RG tag, no comment.  File I/O and the command line are
+ * the caller's: the header block (bsw_bam_header) followed by the records of any number of calls is an
+ * uncompressed BAM stream; bsw_bgzf* (bsw_bgzf.h) cuts and compresses it into BGZF blocks on the device.
  *
  * THE RECORD.  p = recs[i]; "at" a global position = its contig, the contig's rid and offset
  *   (bsw_contigs.h); with no table rid 0, offset 0.  Every number is little-endian.

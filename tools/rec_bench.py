@@ -14,9 +14,16 @@ in one process, --reps times each:
   (g) a device-to-device hipMemcpy of the BAM byte count
 Prints one JSON line (and writes it to --out).  --only-new: just (c) and (d) (for a kernel trace); --only-out: just
 (d) and (f) with their copies (the lanes-per-record sweeps, BSW_HIP_LIB names the library under test; a kernel trace).
+--bgzf: the BGZF legs (include/bsw_bgzf.h) over the BAM bytes of (f), alternating:
+  (f) (g) as above, the yardsticks of the same process
+  (h) bsw_bgzf_resident at block_bytes 0xff00 and (i) at 32,640: deflate_ms, pack_ms, bytes out, blocks per form
+  (j) hipMemcpy device -> pinned host of the BAM bytes; (k) of (h)'s compressed bytes
+and, on the host, Python's zlib at levels 1 and 6 over --zlib-chunks chunks of 0xff00 bytes spread over the BAM bytes,
+beside this encoder's blocks of the same chunks.
 
     python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 7 --out profiles/rec/bench.json
     python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 7 --only-out --out profiles/bam/bench.json
+    python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 5 --bgzf --out profiles/bgzf/bench.json
 """
 
 import argparse
@@ -25,6 +32,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -39,6 +47,74 @@ from bench import pe_reads  # noqa: E402
 from reg2aln_bench import spread, timed  # noqa: E402
 
 
+def bgzf_legs(args, eng, b, bam_bytes, bam, copy_bam, log):
+    """the --bgzf legs over b's BAM bytes; returns the JSON fields"""
+    rt = hiprt.rt()
+    big, half = bsw.bgzf_opt(), bsw.bgzf_opt(block_bytes=32640)
+    cap = bsw.bgzf_bound(bam_bytes, half)
+    nb_big, z_big = b.bgzf(big, cap=cap)                         # warm-up; the sizes
+    st_big = bsw.bgzf_last_stats(eng)
+    blk_big = b.get("bgzf_blk")
+    nb_half, z_half = b.bgzf(half, cap=cap)
+    st_half = bsw.bgzf_last_stats(eng)
+    pinned = ctypes.c_void_p()
+    hiprt.check(rt.hipHostMalloc(ctypes.byref(pinned), ctypes.c_size_t(bam_bytes), ctypes.c_uint(0)))
+
+    def d2h(name, nbytes):
+        def run():
+            hiprt.check(rt.hipMemcpy(pinned, ctypes.c_void_p(b.buf[name].ptr), nbytes, hiprt.D2H))
+        return run
+
+    d2h("bam", bam_bytes)()
+    tf, f_write, tg, th, ti, tj, tk = [], [], [], [], [], [], []
+    h_def, h_pack, i_def, i_pack = [], [], [], []
+    for _ in range(args.reps):
+        tf.append(timed(bam))
+        f_write.append(bsw.bam_last_stats(eng).write_ms)
+        tg.append(timed(copy_bam))
+        ti.append(timed(lambda: b.bgzf(half, cap=cap)))
+        st = bsw.bgzf_last_stats(eng)
+        i_def.append(st.deflate_ms)
+        i_pack.append(st.pack_ms)
+        th.append(timed(lambda: b.bgzf(big, cap=cap)))           # (last: (k) copies its bytes)
+        st = bsw.bgzf_last_stats(eng)
+        h_def.append(st.deflate_ms)
+        h_pack.append(st.pack_ms)
+        tj.append(timed(d2h("bam", bam_bytes)))
+        tk.append(timed(d2h("bgzf", z_big)))
+    hiprt.check(rt.hipHostFree(pinned))
+    # the yardstick: zlib per chunk on the host, and this encoder's blocks of the same chunks
+    data = b.get("bam")
+    pick = np.unique(np.linspace(0, nb_big - 1, min(args.zlib_chunks, nb_big)).astype(np.int64))
+    raw = z1 = z6 = ours = 0
+    for k in pick:
+        chunk = data[k * 0xff00:(k + 1) * 0xff00].tobytes()
+        raw += len(chunk)
+        z1 += len(zlib.compress(chunk, 1)) - 6 + 26              # (the zlib wrapper's 6 bytes for a block's 26)
+        z6 += len(zlib.compress(chunk, 6)) - 6 + 26
+        ours += int(blk_big[k + 1] - blk_big[k])
+    log(f"bgzf: {bam_bytes} -> {z_big} bytes at 0xff00, {z_half} at 32640; sample of {len(pick)} chunks: zlib-1 {z1}, zlib-6 {z6}, ours {ours}")
+
+    def forms(st):
+        return {"blocks": st.n_blocks, "stored": st.n_stored, "fixed": st.n_fixed, "dynamic": st.n_dynamic}
+
+    med = lambda v: spread(v)["median"]  # noqa: E731
+    return {"bam_bytes": int(bam_bytes),
+            "f_bam_s": spread(tf), "f_bam_write_ms": spread(f_write), "g_memcpy_d2d_bam_s": spread(tg),
+            "h_bgzf_ff00_bytes": int(z_big), "h_bgzf_ff00_ratio": round(z_big / bam_bytes, 4), "h_bgzf_ff00_forms": forms(st_big),
+            "h_bgzf_ff00_s": spread(th), "h_bgzf_ff00_deflate_ms": spread(h_def), "h_bgzf_ff00_pack_ms": spread(h_pack),
+            "h_bgzf_ff00_deflate_gb_per_s": round(bam_bytes / (med(h_def) * 1e-3) / 1e9, 1),
+            "i_bgzf_32640_bytes": int(z_half), "i_bgzf_32640_ratio": round(z_half / bam_bytes, 4),
+            "i_bgzf_32640_forms": forms(st_half), "i_bgzf_32640_s": spread(ti), "i_bgzf_32640_deflate_ms": spread(i_def),
+            "i_bgzf_32640_pack_ms": spread(i_pack),
+            "j_d2h_pinned_bam_s": spread(tj), "j_d2h_pinned_bam_gb_per_s": round(bam_bytes / med(tj) / 1e9, 1),
+            "k_d2h_pinned_bgzf_s": spread(tk),
+            "compress_plus_copy_s": round(med(th) + med(tk), 6), "copy_uncompressed_s": round(med(tj), 6),
+            "zlib_sample": {"chunks": int(len(pick)), "raw_bytes": int(raw), "zlib1_bytes": int(z1), "zlib6_bytes": int(z6),
+                            "bgzf_bytes": int(ours), "zlib1_ratio": round(z1 / raw, 4), "zlib6_ratio": round(z6 / raw, 4),
+                            "bgzf_ratio": round(ours / raw, 4), "bgzf_over_zlib1": round(ours / z1, 3)}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=1_000_000)
@@ -48,6 +124,8 @@ def main():
     ap.add_argument("--w", type=int, default=100)
     ap.add_argument("--only-new", action="store_true")
     ap.add_argument("--only-out", action="store_true")
+    ap.add_argument("--bgzf", action="store_true")
+    ap.add_argument("--zlib-chunks", type=int, default=256)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     log = lambda m: print(f"[rec_bench] {m}", file=sys.stderr, flush=True)  # noqa: E731
@@ -146,6 +224,19 @@ def main():
                 "f_bam_over_d_text_median": round(spread(f_ms)["median"] / spread(d_ms)["median"], 3),
                 "g_memcpy_d2d_bam_s": spread(tg), "g_memcpy_d2d_bam_gb_per_s": round(bam_bytes / spread(tg)["median"] / 1e9, 1)}
 
+    if args.bgzf:
+        out = {"tool": "rec_bench", "legs": "bgzf", "lib": os.path.basename(bsw.HIP_LIB), "pairs": n // 2, "reads": n,
+               "read_len": args.read_len, "ref_mb": args.ref_mb}
+        out.update(bgzf_legs(args, eng, b, bam_bytes, bam, copy_bam, log))
+        line = json.dumps(out)
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        eng.close()
+        fmi.close()
+        return
     if args.only_out:
         for _ in range(args.reps):
             out_legs()
