@@ -7,7 +7,7 @@
 //                      (its planning -- staging layout, chunk schedule, kStageBlk -- in bsw_stage_plan.h)
 //   bsw_host.cpp     : contexts, recovery, mate / global / extension wrappers, options, the core C ABI
 //   bsw_stages.cpp   : the stages behind the extension (final alignments, region selection, the
-//                      paired-end stage, mate rescue, SAM records, BGZF), both forms of each, on shared
+//                      paired-end stage, mate rescue, SAM records, BGZF, BAM sort and index), both forms of each, on shared
 //                      call helpers
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +32,7 @@
 #include "../../include/bsw_rec.h"
 #include "../../include/bsw_bam.h"
 #include "../../include/bsw_bgzf.h"
+#include "../../include/bsw_bamsort.h"
 #include "../../include/bsw_contigs.h"
 #include "bsw_contig_seg.h"
 #include "bsw_kernels.h"
@@ -244,6 +245,15 @@ struct BSW_HIDDEN Slot {
     DevBuf<uint16_t> d_btok;            // the deflate kernel's tokens, per workgroup
     DevBuf<int64_t> d_bsize;            // the blocks' sizes, n_blocks + 1
     DevBuf<int32_t> d_bmeta;            // kBgzfMetaWords
+    // BAM sort and index (bsw_bamsort.h); the sorted lengths are d_rlen, scans and radix sorts use d_tmp, the host
+    // forms stage in d_aio, the kernels are timed with evw0 / evw1
+    DevBuf<uint64_t> d_qkey;            // keys in and out of the radix sort, 2 n_rec
+    DevBuf<int32_t> d_qval;             // values likewise (the sort's output values are the caller's d_perm)
+    DevBuf<int32_t> d_qints;            // sort: the output tiles' first records; index: kBiIntArrays arrays of n_rec + 1
+    DevBuf<uint32_t> d_qref;            // index: kBiRefWords per reference
+    DevBuf<uint32_t> d_qlin;            // index: the flat linear index, sum((ref_len + 16383) >> 14) entries
+    DevBuf<int64_t> d_qref64;           // index: win_off, ref_size, ref_off (n_ref + 1 each), then ref_len
+    DevBuf<int32_t> d_qmeta;            // kBsMetaWords / kBiMetaWords
     bool timed = false;
     hipStream_t run_stream = nullptr;   // stream of the last run_device (finish_stats waits on it)
     bsw_stats_t stats{};
@@ -442,6 +452,7 @@ struct bsw_ctx {
     bsw_rec_stats_t rec_last{};
     bsw_bam_stats_t bam_last{};
     bsw_bgzf_stats_t bgzf_last{};
+    bsw_bamsort_stats_t bamsort_last{};
     struct Pinned { std::mutex mu; bsw::PinnedBuf<uint8_t> b; } pin[2];
     int glob_band = 0;                  // BSW_OPT_GLOB_BAND
     int64_t ext_chunk = 0;              // BSW_OPT_EXT_CHUNK (0: the int32-offset bound)

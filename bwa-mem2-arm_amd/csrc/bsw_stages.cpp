@@ -1,8 +1,8 @@
 // bsw_stages.cpp -- the stages behind the extension, each in a device-resident form and a
 // host-array form behind the C ABI: final alignments (bsw_aln.h), region selection (bsw_sel.h),
-// the paired-end stage (bsw_pe.h), mate rescue (bsw_matesw.h), SAM records (bsw_rec.h) and BGZF
-// (bsw_bgzf.h).  Their kernels are in bsw_aln.hip, bsw_sel.hip, bsw_pe.hip, bsw_matesw.hip, bsw_rec.hip and
-// bsw_bgzf.hip; what the calls share is below.
+// the paired-end stage (bsw_pe.h), mate rescue (bsw_matesw.h), SAM records (bsw_rec.h), BGZF
+// (bsw_bgzf.h) and the BAM sort and index (bsw_bamsort.h).  Their kernels are in bsw_aln.hip, bsw_sel.hip,
+// bsw_pe.hip, bsw_matesw.hip, bsw_rec.hip, bsw_bgzf.hip and bsw_bamsort.hip; what the calls share is below.
 // (Layout of the engine: bsw_engine.h.)
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -19,6 +19,7 @@
 #include "bsw_matesw_k.h"
 #include "bsw_rec_k.h"
 #include "bsw_bgzf_k.h"
+#include "bsw_bamsort_k.h"
 #include "bsw_stage_k.h"
 
 // ---------------------------------------------------------------- shared by the stages
@@ -1354,6 +1355,158 @@ static int bgzf_device(Slot &s, hipStream_t st, const bsw_bgzf_opt_t &opt, const
     return BSW_OK;
 }
 
+// ---------------------------------------------------------------- BAM sort and index (bsw_bamsort.h)
+static int bamsort_check_opt(const bsw_bamsort_opt_t *opt)
+{
+    return !opt || opt->n_ref <= 0 || opt->flags ? BSW_E_INVAL : BSW_OK;
+}
+
+static bool ranges_overlap(const uint8_t *a, int64_t na, const uint8_t *b, int64_t nb)
+{
+    return na > 0 && nb > 0 && (uintptr_t)a < (uintptr_t)b + (uint64_t)nb && (uintptr_t)b < (uintptr_t)a + (uint64_t)na;
+}
+
+// keys and checks -> one readback (error word, the keys' OR / NOR, n_bytes) -> radix sort over the bits that vary
+// (none: the input order) -> sorted lengths scanned into out_off -> the permute kernel
+static int bam_sort_device(Slot &s, hipStream_t st, const bsw_bamsort_opt_t &opt, const uint8_t *d_bam,
+                           const int64_t *d_bam_off, int32_t n_rec, uint8_t *d_out, int64_t out_cap, int64_t *d_out_off,
+                           int32_t *d_perm, bsw_bamsort_stats_t &qs)
+{
+    const size_t n = (size_t)n_rec;
+    size_t scan_bytes = 0, sort_bytes = 0;
+    BSW_TRY(launch_scan64(nullptr, &scan_bytes, nullptr, nullptr, n_rec, st));
+    BSW_TRY(launch_bamsort_pairs(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, n_rec, 0, 64, st));
+    const size_t tmp_bytes = std::max<size_t>(std::max(scan_bytes, sort_bytes), 16);
+    BSW_TRY(s.d_tmp.grow(tmp_bytes));
+    BSW_TRY(s.d_qkey.grow(2 * n));
+    BSW_TRY(s.d_qval.grow(n));
+    BSW_TRY(s.d_rlen.grow(n + 1));
+    BSW_TRY(s.d_qmeta.grow(kBsMetaWords));
+    HelperTimer tm;
+    BSW_TRY(tm.init(s.evw0, s.evw1, st));
+    static_assert(kBsMetaWords + 2 <= kMetaWords, "the slot's pinned mirror holds the meta words and the total");
+    int64_t *h_tot = (int64_t *)(s.h_meta + kBsMetaWords);
+    BSW_TRY(hipMemsetAsync(s.d_qmeta, 0, kBsMetaWords * sizeof(int32_t), st));
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_bamsort_keys(d_bam, d_bam_off, n_rec, opt.n_ref, s.d_qkey, s.d_qval, s.d_qmeta, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipMemcpyAsync(s.h_meta, s.d_qmeta, kBsMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_tot, d_bam_off + n_rec, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(qs.key_ms));
+    if (s.h_meta[kBsErr] || *h_tot < 0) return BSW_E_RANGE;
+    qs.n_bytes = *h_tot;
+    if (qs.n_bytes > out_cap) return BSW_E_RANGE;
+    if (ranges_overlap(d_bam, qs.n_bytes, d_out, qs.n_bytes)) return BSW_E_INVAL;
+    if (bamsort_tiles(qs.n_bytes) > INT32_MAX) return BSW_E_RANGE;
+    BSW_TRY(s.d_qints.grow((size_t)bamsort_tiles(qs.n_bytes) + 1));      // the output tiles' first records
+    uint64_t or_, nor_;
+    memcpy(&or_, s.h_meta + kBsOr, sizeof or_);
+    memcpy(&nor_, s.h_meta + kBsNor, sizeof nor_);
+    int lo, hi;
+    bamsort::key_span(or_, nor_, &lo, &hi);
+    qs.key_bits = hi - lo;
+    BSW_TRY(tm.begin());
+    if (hi > lo) {
+        size_t tb = tmp_bytes;
+        BSW_TRY(launch_bamsort_pairs(s.d_tmp, &tb, s.d_qkey, s.d_qkey + n, s.d_qval, d_perm, n_rec, lo, hi, st));
+    } else {
+        BSW_TRY(hipMemcpyAsync(d_perm, s.d_qval, n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    }
+    BSW_TRY(tm.end());
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(qs.sort_ms));
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_bamsort_lens(d_bam_off, d_perm, n_rec, s.d_rlen, st));
+    BSW_TRY(launch_scan64(s.d_tmp, &scan_bytes, s.d_rlen, d_out_off, n_rec, st));
+    BSW_TRY(launch_bamsort_permute(d_bam, d_bam_off, d_perm, d_out_off, s.d_qints, n_rec, qs.n_bytes, d_out, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(qs.copy_ms));
+    return BSW_OK;
+}
+
+// the index's host-side plan: the references' first windows in the flat linear index
+static int bai_windows(const bsw_bamsort_opt_t &opt, const int32_t *ref_len, std::vector<int64_t> &h64)
+{
+    const size_t r1 = (size_t)opt.n_ref + 1;
+    h64.assign(r1 + (r1 + 1) / 2, 0);               // win_off, then ref_len as int32
+    int32_t *h_len = (int32_t *)(h64.data() + r1);
+    for (int32_t r = 0; r < opt.n_ref; ++r) {
+        if (ref_len[r] < 0 || ref_len[r] > BSW_BAI_MAX_REF_LEN) return BSW_E_RANGE;
+        h64[r + 1] = h64[r] + (((int64_t)ref_len[r] + 16383) >> bamsort::kLinShift);
+        h_len[r] = ref_len[r];
+    }
+    return BSW_OK;
+}
+
+// plan (extents, windows, bins, chunks, sizes) -> one readback (meta, the references' bytes) -> the file
+static int bam_index_device(Slot &s, hipStream_t st, const bsw_bamsort_opt_t &opt, const std::vector<int64_t> &h64,
+                            const uint8_t *d_bam, const int64_t *d_bam_off, int32_t n_rec, const int64_t *d_voff,
+                            int64_t end_voff, uint8_t *d_bai, int64_t bai_cap, int64_t *n_bytes, bsw_bamsort_stats_t &qs)
+{
+    const size_t n = (size_t)n_rec, r1 = (size_t)opt.n_ref + 1;
+    BaiArgs a{};
+    a.n_win = h64[opt.n_ref];
+    BSW_TRY(bai_tmp_bytes(n_rec, opt.n_ref, &a.tmp_bytes));
+    BSW_TRY(s.d_tmp.grow(a.tmp_bytes));
+    BSW_TRY(s.d_qkey.grow(std::max<size_t>(2 * n, 1)));
+    BSW_TRY(s.d_qval.grow(std::max<size_t>(2 * n, 1)));
+    BSW_TRY(s.d_qints.grow((size_t)kBiIntArrays * (n + 1)));
+    BSW_TRY(s.d_qref.grow((size_t)opt.n_ref * kBiRefWords));
+    BSW_TRY(s.d_qlin.grow(std::max<size_t>((size_t)a.n_win, 1)));
+    BSW_TRY(s.d_qref64.grow(2 * r1 + h64.size()));
+    BSW_TRY(s.d_qmeta.grow(kBiMetaWords));
+    a.bam = d_bam; a.off = d_bam_off; a.voff = d_voff; a.end_voff = end_voff;
+    a.n_rec = n_rec; a.n_ref = opt.n_ref;
+    a.ref_size = s.d_qref64; a.ref_off = s.d_qref64 + r1;
+    a.win_off = s.d_qref64 + 2 * r1;
+    a.ref_len = (const int32_t *)(s.d_qref64 + 3 * r1);
+    a.lin = s.d_qlin; a.ref = s.d_qref;
+    a.key = s.d_qkey; a.key2 = s.d_qkey + n; a.val = s.d_qval; a.val2 = s.d_qval + n;
+    a.ints = s.d_qints; a.meta = s.d_qmeta; a.tmp = s.d_tmp; a.bai = d_bai;
+    HelperTimer tm;
+    BSW_TRY(tm.init(s.evw0, s.evw1, st));
+    static_assert(kBiMetaWords + 2 <= kMetaWords, "the slot's pinned mirror holds the meta words and the total");
+    int64_t *h_tot = (int64_t *)(s.h_meta + kBiMetaWords);
+    BSW_TRY(hipMemsetAsync(s.d_qmeta, 0, kBiMetaWords * sizeof(int32_t), st));
+    BSW_TRY(hipMemcpyAsync(s.d_qref64 + 2 * r1, h64.data(), h64.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_bai_plan(a, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipMemcpyAsync(s.h_meta, s.d_qmeta, kBiMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(h_tot, a.ref_off + opt.n_ref, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(qs.index_ms));
+    if (s.h_meta[kBiErr]) return BSW_E_RANGE;
+    qs.n_bins = s.h_meta[kBiBins];
+    qs.n_chunks = s.h_meta[kBiChunks];
+    qs.n_no_coor = s.h_meta[kBiNoCoor];
+    memcpy(&qs.n_intv, s.h_meta + kBiIntv, sizeof qs.n_intv);
+    *n_bytes = qs.bai_bytes = bamsort::kBaiHead + *h_tot + 8;
+    if (*n_bytes > bai_cap) return BSW_E_RANGE;
+    BSW_TRY(tm.begin());
+    BSW_TRY(launch_bai_write(a, st));
+    BSW_TRY(tm.end());
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(tm.add(qs.index_ms));
+    return BSW_OK;
+}
+
+// the sort's fields and the index's fields of the last stats are those of the last call of each
+static void put_bamsort_stats(bsw_ctx_t *ctx, const bsw_bamsort_stats_t &qs, bool index)
+{
+    std::lock_guard<std::mutex> g(ctx->stats_mu);
+    bsw_bamsort_stats_t &d = ctx->bamsort_last;
+    if (index) {
+        d.index_ms = qs.index_ms; d.n_bins = qs.n_bins; d.n_chunks = qs.n_chunks; d.n_intv = qs.n_intv;
+        d.n_no_coor = qs.n_no_coor; d.bai_bytes = qs.bai_bytes;
+    } else {
+        d.n_rec = qs.n_rec; d.key_bits = qs.key_bits; d.n_bytes = qs.n_bytes;
+        d.key_ms = qs.key_ms; d.sort_ms = qs.sort_ms; d.copy_ms = qs.copy_ms;
+    }
+}
+
 }  // namespace bsw
 
 extern "C" {
@@ -1744,5 +1897,137 @@ int bsw_bgzf(bsw_ctx_t *ctx, const bsw_bgzf_opt_t *opt, const uint8_t *in, int64
 }
 
 int bsw_bgzf_last_stats(bsw_ctx_t *ctx, bsw_bgzf_stats_t *out) { return bsw::get_stats(ctx, &bsw_ctx::bgzf_last, out); }
+
+// ---------------------------------------------------------------- BAM sort and index (include/bsw_bamsort.h)
+int bsw_bam_sort_resident(bsw_ctx_t *ctx, const bsw_bamsort_opt_t *opt, const uint8_t *d_bam,
+                          const int64_t *d_bam_off, int32_t n_rec, uint8_t *d_out, int64_t out_cap,
+                          int64_t *d_out_off, int32_t *d_perm, void *stream)
+{
+    if (const int rc = bsw::bamsort_check_opt(opt)) return rc;
+    if (!ctx || n_rec < 0 || out_cap < 0 || (out_cap > 0 && !d_out) || ((uintptr_t)d_out & 3) ||
+        (n_rec > 0 && (!d_bam || !d_bam_off || !d_out_off || !d_perm)))
+        return BSW_E_INVAL;
+    if (n_rec > 0 && bsw::ranges_overlap(d_bam, 1, d_out, out_cap)) return BSW_E_INVAL;
+    bsw_bamsort_stats_t qs{};
+    qs.n_rec = n_rec;
+    if (n_rec > 0) {
+        bsw::DeviceCtx &dc = *ctx->devs[0];
+        const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+            hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+            return bsw::bam_sort_device(s, st, *opt, d_bam, d_bam_off, n_rec, d_out, out_cap, d_out_off, d_perm, qs);
+        });
+        if (rc) return rc;
+    }
+    bsw::put_bamsort_stats(ctx, qs, false);
+    return BSW_OK;
+}
+
+int bsw_bam_sort(bsw_ctx_t *ctx, const bsw_bamsort_opt_t *opt, const uint8_t *bam, const int64_t *bam_off,
+                 int32_t n_rec, uint8_t *out, int64_t out_cap, int64_t *out_off, int32_t *perm)
+{
+    if (const int rc = bsw::bamsort_check_opt(opt)) return rc;
+    if (!ctx || n_rec < 0 || out_cap < 0 || (out_cap > 0 && !out) ||
+        (n_rec > 0 && (!bam || !bam_off || !out_off || !perm)))
+        return BSW_E_INVAL;
+    bsw_bamsort_stats_t qs{};
+    qs.n_rec = n_rec;
+    if (n_rec > 0) {
+        const int64_t n_bytes = bam_off[n_rec];
+        if (n_bytes < 0 || n_bytes > out_cap) return BSW_E_RANGE;
+        if (bsw::ranges_overlap(bam, n_bytes, out, n_bytes)) return BSW_E_INVAL;
+        const size_t nr = (size_t)n_rec;
+        bsw::StagedIo io;
+        const auto d_bam = io.in(bam, (size_t)n_bytes);
+        const auto d_bam_off = io.in(bam_off, nr + 1);
+        const auto d_out = io.out(out, (size_t)n_bytes);
+        const auto d_out_off = io.out(out_off, nr + 1);
+        const auto d_perm = io.out(perm, nr);
+        bsw::DeviceCtx &dc = *ctx->devs[0];
+        const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+            BSW_TRY(io.stage(s));
+            if (const int r = bsw::bam_sort_device(s, s.stream, *opt, d_bam, d_bam_off, n_rec, d_out, n_bytes, d_out_off,
+                                                   d_perm, qs))
+                return r;
+            BSW_TRY(io.back(d_out));
+            BSW_TRY(io.back(d_out_off));
+            BSW_TRY(io.back(d_perm));
+            BSW_TRY(hipStreamSynchronize(s.stream));
+            return BSW_OK;
+        });
+        if (rc) return rc;
+    }
+    bsw::put_bamsort_stats(ctx, qs, false);
+    return BSW_OK;
+}
+
+static int bam_index_check(bsw_ctx_t *ctx, const bsw_bamsort_opt_t *opt, const int32_t *ref_len, const void *bam,
+                           const void *bam_off, int32_t n_rec, const void *voff, int64_t end_voff, const void *bai,
+                           int64_t bai_cap, const int64_t *n_bytes)
+{
+    if (const int rc = bsw::bamsort_check_opt(opt)) return rc;
+    if (!ctx || !ref_len || !n_bytes || n_rec < 0 || bai_cap < 0 || end_voff < 0 || (bai_cap > 0 && !bai) ||
+        (n_rec > 0 && (!bam || !bam_off || !voff)))
+        return BSW_E_INVAL;
+    return BSW_OK;
+}
+
+int bsw_bam_index_resident(bsw_ctx_t *ctx, const bsw_bamsort_opt_t *opt, const int32_t *ref_len, const uint8_t *d_bam,
+                           const int64_t *d_bam_off, int32_t n_rec, const int64_t *d_voff, int64_t end_voff,
+                           uint8_t *d_bai, int64_t bai_cap, int64_t *n_bytes, void *stream)
+{
+    if (const int rc = bam_index_check(ctx, opt, ref_len, d_bam, d_bam_off, n_rec, d_voff, end_voff, d_bai, bai_cap, n_bytes))
+        return rc;
+    if ((uintptr_t)d_bai & 3) return BSW_E_INVAL;
+    *n_bytes = 0;
+    std::vector<int64_t> h64;
+    if (const int rc = bsw::bai_windows(*opt, ref_len, h64)) return rc;
+    bsw_bamsort_stats_t qs{};
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+        return bsw::bam_index_device(s, st, *opt, h64, d_bam, d_bam_off, n_rec, d_voff, end_voff, d_bai, bai_cap, n_bytes, qs);
+    });
+    if (rc) return rc;
+    bsw::put_bamsort_stats(ctx, qs, true);
+    return BSW_OK;
+}
+
+int bsw_bam_index(bsw_ctx_t *ctx, const bsw_bamsort_opt_t *opt, const int32_t *ref_len, const uint8_t *bam,
+                  const int64_t *bam_off, int32_t n_rec, const int64_t *voff, int64_t end_voff, uint8_t *bai,
+                  int64_t bai_cap, int64_t *n_bytes)
+{
+    if (const int rc = bam_index_check(ctx, opt, ref_len, bam, bam_off, n_rec, voff, end_voff, bai, bai_cap, n_bytes))
+        return rc;
+    *n_bytes = 0;
+    std::vector<int64_t> h64;
+    if (const int rc = bsw::bai_windows(*opt, ref_len, h64)) return rc;
+    const int64_t bam_bytes = n_rec > 0 ? bam_off[n_rec] : 0;
+    if (bam_bytes < 0) return BSW_E_RANGE;
+    const size_t nr = (size_t)n_rec;
+    bsw::StagedIo io;
+    const auto d_bam = io.in(bam, (size_t)bam_bytes);
+    const auto d_bam_off = io.in(bam_off, nr ? nr + 1 : 0);
+    const auto d_voff = io.in(voff, nr);
+    const auto d_bai = io.out(bai, (size_t)bai_cap);
+    bsw_bamsort_stats_t qs{};
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+        BSW_TRY(io.stage(s));
+        if (const int r = bsw::bam_index_device(s, s.stream, *opt, h64, d_bam, d_bam_off, n_rec, d_voff, end_voff, d_bai,
+                                                bai_cap, n_bytes, qs))
+            return r;
+        BSW_TRY(io.back(d_bai, (size_t)*n_bytes));
+        BSW_TRY(hipStreamSynchronize(s.stream));
+        return BSW_OK;
+    });
+    if (rc) return rc;
+    bsw::put_bamsort_stats(ctx, qs, true);
+    return BSW_OK;
+}
+
+int bsw_bamsort_last_stats(bsw_ctx_t *ctx, bsw_bamsort_stats_t *out)
+{
+    return bsw::get_stats(ctx, &bsw_ctx::bamsort_last, out);
+}
 
 }  // extern "C"

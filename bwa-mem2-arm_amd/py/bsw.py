@@ -58,6 +58,11 @@ BAM_SYMBOLS = ("bsw_bam_records", "bsw_bam_records_resident", "bsw_bam_header", 
 # include/bsw_bgzf.h (additive likewise: BSW_BGZF_API)
 BGZF_SYMBOLS = ("bsw_bgzf_opt_default", "bsw_bgzf", "bsw_bgzf_resident", "bsw_bgzf_last_stats")
 BGZF_MAX_BLOCK, BGZF_EOF = 0xff00, 1
+# include/bsw_bamsort.h (additive likewise: BSW_BAMSORT_API)
+BAMSORT_SYMBOLS = ("bsw_bam_sort", "bsw_bam_sort_resident", "bsw_bam_index", "bsw_bam_index_resident",
+                   "bsw_bamsort_last_stats")
+BAMSORT_PERM_TILE = 8192            # bytes of output per workgroup of the permute kernel (bsw_bamsort_k.h: kPermTile), for tests
+BAMSORT_SORT_TILE = 4096            # a size above which the radix sort runs over more than one of its tiles, for tests
 CONTIG_MAX_NAME = 63
 
 # include/bsw.h engine options (bsw_set_option)
@@ -267,6 +272,13 @@ def hip_lib():
         L.bsw_bgzf_resident.argtypes = L.bsw_bgzf.argtypes + [P]
         L.bsw_bgzf_last_stats.argtypes = [P, P]
         for f in BGZF_SYMBOLS[1:]:
+            getattr(L, f).restype = ctypes.c_int
+        L.bsw_bam_sort.argtypes = [P, P, P, P, i32, P, i64, P, P]
+        L.bsw_bam_sort_resident.argtypes = L.bsw_bam_sort.argtypes + [P]
+        L.bsw_bam_index.argtypes = [P, P, P, P, P, i32, P, i64, P, i64, P]
+        L.bsw_bam_index_resident.argtypes = L.bsw_bam_index.argtypes + [P]
+        L.bsw_bamsort_last_stats.argtypes = [P, P]
+        for f in BAMSORT_SYMBOLS:
             getattr(L, f).restype = ctypes.c_int
         L.bsw_set_contigs.argtypes = [P, i32, P, ctypes.POINTER(ctypes.c_char_p)]
         L.bsw_set_contigs.restype = ctypes.c_int
@@ -1392,6 +1404,98 @@ def bgzf_resident(engine, d_in: int, n_in: int, d_rec_off: int, n_rec: int, d_ou
 def bgzf_last_stats(engine) -> BgzfStats:
     st = BgzfStats()
     _check(hip_lib().bsw_bgzf_last_stats(engine._ctx, ctypes.byref(st)))
+    return st
+
+
+# ---------------------------------------------------------------- BAM sort and index (bsw_bamsort.h)
+class BamsortOpt(ctypes.Structure):
+    _fields_ = [("n_ref", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class BamsortStats(ctypes.Structure):
+    _fields_ = [("n_rec", ctypes.c_int32), ("key_bits", ctypes.c_int32), ("n_bytes", ctypes.c_int64),
+                ("key_ms", ctypes.c_float), ("sort_ms", ctypes.c_float), ("copy_ms", ctypes.c_float),
+                ("index_ms", ctypes.c_float), ("n_bins", ctypes.c_int32), ("n_chunks", ctypes.c_int32),
+                ("n_intv", ctypes.c_int64), ("n_no_coor", ctypes.c_int64), ("bai_bytes", ctypes.c_int64)]
+
+
+def bamsort_opt(n_ref: int, flags: int = 0) -> BamsortOpt:
+    return BamsortOpt(n_ref, flags)
+
+
+def bam_sort(engine, bam, bam_off, n_ref: int, out_cap: int | None = None):
+    """bsw_bam_sort (host arrays): BAM alignment blocks and their offsets [n_rec + 1] -> (the blocks in coordinate
+    order as bytes, out_off int64 [n_rec + 1], perm int32 [n_rec]: the input index of output record i)"""
+    bam = np.ascontiguousarray(np.frombuffer(bam, dtype=np.uint8) if isinstance(bam, (bytes, bytearray)) else bam, dtype=np.uint8)
+    bam_off = np.ascontiguousarray(bam_off, dtype=np.int64)
+    n_rec = len(bam_off) - 1
+    out_cap = len(bam) if out_cap is None else out_cap
+    out = np.zeros(max(out_cap, 1), dtype=np.uint8)
+    out_off, perm = np.zeros(n_rec + 1, dtype=np.int64), np.zeros(max(n_rec, 1), dtype=np.int32)
+    opt = bamsort_opt(n_ref)
+    _check(hip_lib().bsw_bam_sort(engine._ctx, ctypes.byref(opt), _ptr(bam), _ptr(bam_off), n_rec, _ptr(out), out_cap,
+                                  _ptr(out_off), _ptr(perm)))
+    return out[:int(bam_off[n_rec])].tobytes(), out_off, perm[:n_rec]
+
+
+def bam_sort_resident(engine, d_bam: int, d_bam_off: int, n_rec: int, d_out: int, out_cap: int, d_out_off: int, d_perm: int,
+                      opt: BamsortOpt, stream: int = 0) -> None:
+    """bsw_bam_sort_resident: every array a device pointer"""
+    V = ctypes.c_void_p
+    _check(hip_lib().bsw_bam_sort_resident(engine._ctx, ctypes.byref(opt), V(d_bam or None), V(d_bam_off or None), n_rec,
+                                           V(d_out or None), out_cap, V(d_out_off or None), V(d_perm or None),
+                                           V(stream or None)))
+
+
+def bam_index(engine, bam, bam_off, voff, end_voff: int, ref_len, bai_cap: int | None = None) -> bytes:
+    """bsw_bam_index (host arrays): the sorted blocks, their offsets and virtual offsets -> the .bai file's bytes.
+    bai_cap=None: one call with no room that says how many bytes are needed, then the call with exactly those.  A
+    bai_cap below what is needed raises BswError with .needed set."""
+    bam = np.ascontiguousarray(np.frombuffer(bam, dtype=np.uint8) if isinstance(bam, (bytes, bytearray)) else bam, dtype=np.uint8)
+    bam_off = np.ascontiguousarray(bam_off, dtype=np.int64)
+    voff = np.ascontiguousarray(voff, dtype=np.int64)
+    ref_len = np.ascontiguousarray(ref_len, dtype=np.int32)
+    n_rec = len(bam_off) - 1
+    opt = bamsort_opt(len(ref_len))
+    n_bytes = ctypes.c_int64(-1)
+
+    def call(cap):
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        rc = hip_lib().bsw_bam_index(engine._ctx, ctypes.byref(opt), _ptr(ref_len), _ptr(bam), _ptr(bam_off), n_rec,
+                                     _ptr(voff), end_voff, _ptr(out), cap, ctypes.byref(n_bytes))
+        if rc != 0:
+            _raise_needed(rc, n_bytes)
+        return out[:n_bytes.value].tobytes()
+
+    if bai_cap is None:
+        try:
+            return call(0)          # (no index is 0 bytes long)
+        except BswError as e:
+            if getattr(e, "needed", -1) <= 0:
+                raise
+            bai_cap = e.needed
+    return call(bai_cap)
+
+
+def bam_index_resident(engine, ref_len, d_bam: int, d_bam_off: int, n_rec: int, d_voff: int, end_voff: int, d_bai: int,
+                       bai_cap: int, stream: int = 0) -> int:
+    """bsw_bam_index_resident: every array but ref_len a device pointer.  Returns n_bytes; a short bai_cap raises
+    BswError with .needed set."""
+    V = ctypes.c_void_p
+    ref_len = np.ascontiguousarray(ref_len, dtype=np.int32)
+    opt = bamsort_opt(len(ref_len))
+    n_bytes = ctypes.c_int64(-1)
+    rc = hip_lib().bsw_bam_index_resident(engine._ctx, ctypes.byref(opt), _ptr(ref_len), V(d_bam or None), V(d_bam_off or None),
+                                          n_rec, V(d_voff or None), end_voff, V(d_bai or None), bai_cap, ctypes.byref(n_bytes),
+                                          V(stream or None))
+    if rc != 0:
+        _raise_needed(rc, n_bytes)
+    return n_bytes.value
+
+
+def bamsort_last_stats(engine) -> BamsortStats:
+    st = BamsortStats()
+    _check(hip_lib().bsw_bamsort_last_stats(engine._ctx, ctypes.byref(st)))
     return st
 
 

@@ -1,6 +1,7 @@
 """ResidentBatch: the device arrays of one batch of reads and the resident stage chain over them,
 
     seeds -> chain2aln -> select -> pe_stat -> matesw -> pe_pair -> reg2aln / records -> sam_text / bam_records -> bgzf
+    (coordinate-sorted and indexed: bam_records -> bam_sort -> bgzf(src="sbam") -> bam_index)
 
 Plumbing for tests and tools, like bsw.py: every stage method is one bsw.*_resident call on the buffers the
 stage before left in HBM.  Importing this module loads no library and touches no device.
@@ -40,6 +41,9 @@ LAYOUT = {
 BAM_LAYOUT = {"bam": (np.uint8, (), "bam"), "bam_off": (np.int64, (), "bam_off")}
 # the BGZF form of the BAM blocks (bsw_bgzf.h), in a table of its own likewise
 BGZF_LAYOUT = {"bgzf": (np.uint8, (), "bgzf"), "bgzf_blk": (np.int64, (), "bgzf_blk"), "bgzf_voff": (np.int64, (), "bgzf_voff")}
+# the coordinate-sorted blocks and their index (bsw_bamsort.h), in a table of its own likewise
+SORT_LAYOUT = {"sbam": (np.uint8, (), "sbam"), "sbam_off": (np.int64, (), "sbam_off"), "bam_perm": (np.int32, (), "bam_perm"),
+               "bai": (np.uint8, (), "bai")}
 FIXED = ("reads", "n_reads", "first")           # counts the constructor sets for good
 # (regs, read, info, first) as the extension, the selection and the rescue leave them
 LISTS = {"c": ("regs", "sr", None, None), "s": ("sreg", "sread", "sinfo", "sfirst"), "m": ("mreg", "mread", "minfo", "mfirst")}
@@ -48,7 +52,7 @@ LISTS = {"c": ("regs", "sr", None, None), "s": ("sreg", "sread", "sinfo", "sfirs
 def _row(name):
     """(dtype, stride keys, count key) of a buffer name"""
     pre, dot, base = name.rpartition(".")
-    table = next((t for t in (LAYOUT, BAM_LAYOUT, BGZF_LAYOUT) if base in t), None)
+    table = next((t for t in (LAYOUT, BAM_LAYOUT, BGZF_LAYOUT, SORT_LAYOUT) if base in t), None)
     if table is None:
         raise ValueError(f"no buffer named '{name}'")
     dtype, strides, key = table[base]
@@ -252,15 +256,50 @@ class ResidentBatch:
         text and BAM of one batch come from one upload"""
         return self._records_out("bam_records", bsw.bam_records_resident, "bam", ropt, names, paired, cap)
 
-    def bgzf(self, bopt, cap=None):
-        """the BAM blocks ("bam", "bam_off") as BGZF blocks: "bgzf", the block starts "bgzf_blk" and the records'
-        virtual offsets "bgzf_voff".  cap=None: room for every block stored.  Returns (n_blocks, n_bytes)."""
-        self._have("bgzf", "bam", "bam_off")
+    def bam_sort(self, n_ref) -> int:
+        """the BAM blocks ("bam", "bam_off") in coordinate order: "sbam", "sbam_off" and "bam_perm", the input index of
+        every output record.  Returns the bytes."""
+        self._have("bam_sort", "bam", "bam_off")
         n_in, n_rec = self.n["bam"], self.n["bam_off"] - 1
+        out, off, perm = self.alloc("sbam", n_in).ptr, self.alloc("sbam_off", n_rec + 1).ptr, self.alloc("bam_perm", n_rec).ptr
+        bsw.bam_sort_resident(self.engine, self.buf["bam"].ptr, self.buf["bam_off"].ptr, n_rec, out, n_in, off, perm,
+                              bsw.bamsort_opt(n_ref))
+        self.n["sbam"], self.n["sbam_off"], self.n["bam_perm"] = n_in, n_rec + 1, n_rec
+        return n_in
+
+    def bgzf(self, bopt, cap=None, src="bam"):
+        """the BAM blocks (src: "bam" with "bam_off", or the sorted "sbam" with "sbam_off") as BGZF blocks: "bgzf", the
+        block starts "bgzf_blk" and the records' virtual offsets "bgzf_voff".  cap=None: room for every block stored.
+        Returns (n_blocks, n_bytes)."""
+        if src not in ("bam", "sbam"):
+            raise ValueError(f"bgzf: src='{src}' is neither 'bam' nor 'sbam'")
+        self._have("bgzf", src, src + "_off")
+        n_in, n_rec = self.n[src], self.n[src + "_off"] - 1
         nb = bsw.bgzf_blocks(n_in, bopt)
         cap = bsw.bgzf_bound(n_in, bopt) if cap is None else cap
         out, blk, voff = self.alloc("bgzf", cap).ptr, self.alloc("bgzf_blk", nb + 1).ptr, self.alloc("bgzf_voff", n_rec).ptr
-        nb, n_bytes = bsw.bgzf_resident(self.engine, self.buf["bam"].ptr, n_in, self.buf["bam_off"].ptr, n_rec, out, cap,
+        nb, n_bytes = bsw.bgzf_resident(self.engine, self.buf[src].ptr, n_in, self.buf[src + "_off"].ptr, n_rec, out, cap,
                                         blk, nb + 1, voff, bopt)
         self.n["bgzf"], self.n["bgzf_blk"], self.n["bgzf_voff"] = n_bytes, nb + 1, n_rec
         return nb, n_bytes
+
+    def bam_index(self, ref_len, base_coffset=0) -> int:
+        """the .bai ("bai") of the sorted blocks behind bgzf(bopt, src="sbam"); base_coffset: that call's.  Reads the
+        one entry of "bgzf_blk" that end_voff needs.  Returns the bytes."""
+        self._have("bam_index", "sbam", "sbam_off", "bgzf_blk", "bgzf_voff")
+        n_rec, nb1 = self.n["sbam_off"] - 1, self.n["bgzf_blk"]
+        if self.n["bgzf_voff"] != n_rec:
+            raise ValueError("bam_index: the virtual offsets are not those of the sorted blocks: run bgzf(bopt, src='sbam')")
+        last = np.zeros(1, np.int64)
+        hiprt.check(hiprt.rt().hipMemcpy(ctypes.c_void_p(last.ctypes.data), ctypes.c_void_p(self.buf["bgzf_blk"].ptr + 8 * (nb1 - 1)),
+                                         8, hiprt.D2H))
+        end_voff = (base_coffset + int(last[0])) << 16
+        args = (self.engine, ref_len, self.buf["sbam"].ptr, self.buf["sbam_off"].ptr, n_rec, self.buf["bgzf_voff"].ptr, end_voff)
+        try:
+            cap = bsw.bam_index_resident(*args, 0, 0)
+        except bsw.BswError as e:
+            if getattr(e, "needed", -1) <= 0:
+                raise
+            cap = e.needed
+        self.n["bai"] = bsw.bam_index_resident(*args, self.alloc("bai", cap).ptr, cap)
+        return self.n["bai"]

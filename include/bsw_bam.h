@@ -8,7 +8,8 @@
  *
  * SCOPE as bsw_rec.h: no ALT contigs, no -a, no RG tag, no comment.  File I/O and the command line are
  * the caller's: the header block (bsw_bam_header) followed by the records of any number of calls is an
- * uncompressed BAM stream; bsw_bgzf* (bsw_bgzf.h) cuts and compresses it into BGZF blocks on the device.
+ * uncompressed BAM stream; bsw_bgzf* (bsw_bgzf.h) cuts and compresses it into BGZF blocks on the device, and
+ * bsw_bam_sort* / bsw_bam_index* (bsw_bamsort.h) put the blocks in coordinate order and build the .bai.
  *
  * THE RECORD.  p = recs[i]; "at" a global position = its contig, the contig's rid and offset
  *   (bsw_contigs.h); with no table rid 0, offset 0.  Every number is little-endian.

@@ -7,7 +7,8 @@
  * This text is the specification; tests/bgzf_py.py pins it with Python's zlib and gzip as the
  * independent decoders.
  *
- * SCOPE.  File I/O, the index file (.bai / .csi) and the command line are the caller's.  Blocks are cut
+ * SCOPE.  File I/O, the .csi index and the command line are the caller's; the .bai of coordinate-sorted blocks is
+ * bsw_bam_index* (bsw_bamsort.h), which reads the d_voff of this call.  Blocks are cut
  * at byte counts, not at record boundaries; one deflate block per BGZF block; one compression level;
  * no decompression.
  *

@@ -21,9 +21,17 @@ Prints one JSON line (and writes it to --out).  --only-new: just (c) and (d) (fo
 and, on the host, Python's zlib at levels 1 and 6 over --zlib-chunks chunks of 0xff00 bytes spread over the BAM bytes,
 beside this encoder's blocks of the same chunks.
 
+--sort: the coordinate sort and the index (include/bsw_bamsort.h) over the same BAM bytes, alternating:
+  (f) (g) as above: the write kernel that builds these bytes from scratch, and the device copy that is the floor
+  (s) bsw_bam_sort_resident: key_ms, sort_ms, copy_ms (lengths, scan, the permute kernel)
+  (t) bsw_bgzf_resident on the sorted blocks and (u) on the unsorted ones: time and bytes
+  (x) bsw_bam_index_resident: index_ms, the index's size
+and, as context on the host, numpy's stable argsort over the same keys (its order has to be the device's).
+
     python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 7 --out profiles/rec/bench.json
     python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 7 --only-out --out profiles/bam/bench.json
     python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 5 --bgzf --out profiles/bgzf/bench.json
+    python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 5 --sort --out profiles/bamsort/bench.json
 """
 
 import argparse
@@ -115,6 +123,69 @@ def bgzf_legs(args, eng, b, bam_bytes, bam, copy_bam, log):
                             "bgzf_ratio": round(ours / raw, 4), "bgzf_over_zlib1": round(ours / z1, 3)}}
 
 
+def sort_legs(args, eng, b, bam_bytes, bam, copy_bam, l_pac, log):
+    """the --sort legs over b's BAM bytes (one reference of l_pac bases); returns the JSON fields"""
+    big = bsw.bgzf_opt(flags=bsw.BGZF_EOF)
+    cap = bsw.bgzf_bound(bam_bytes, big)
+    ref_len = [l_pac]
+    b.bam_sort(1)                                                # warm-up; the sizes
+    n_rec = b.n["bam_perm"]
+    nb, z_sorted = b.bgzf(big, cap=cap, src="sbam")
+    bai_bytes = b.bam_index(ref_len)
+    st_x = bsw.bamsort_last_stats(eng)
+    end_voff = int(b.get("bgzf_blk")[nb]) << 16
+    _, z_unsorted = b.bgzf(big, cap=cap, src="bam")
+
+    def index():
+        # (the virtual offsets are those of the last bgzf call: the sorted blocks')
+        bsw.bam_index_resident(eng, ref_len, b.buf["sbam"].ptr, b.buf["sbam_off"].ptr, n_rec, b.buf["bgzf_voff"].ptr, end_voff,
+                               b.buf["bai"].ptr, bai_bytes)
+
+    tf, f_write, tg, ts, tt, tu, tx = [], [], [], [], [], [], []
+    key_ms, sort_ms, copy_ms, index_ms, t_def, u_def = [], [], [], [], [], []
+    for _ in range(args.reps):
+        tf.append(timed(bam))
+        f_write.append(bsw.bam_last_stats(eng).write_ms)
+        tg.append(timed(copy_bam))
+        ts.append(timed(lambda: b.bam_sort(1)))
+        st = bsw.bamsort_last_stats(eng)
+        key_ms.append(st.key_ms)
+        sort_ms.append(st.sort_ms)
+        copy_ms.append(st.copy_ms)
+        tu.append(timed(lambda: b.bgzf(big, cap=cap, src="bam")))
+        u_def.append(bsw.bgzf_last_stats(eng).deflate_ms)
+        tt.append(timed(lambda: b.bgzf(big, cap=cap, src="sbam")))
+        t_def.append(bsw.bgzf_last_stats(eng).deflate_ms)
+        tx.append(timed(index))
+        index_ms.append(bsw.bamsort_last_stats(eng).index_ms)
+    # the host's context: numpy's stable argsort over the same keys; its order is the device's
+    data, boff = b.get("bam"), b.get("bam_off")
+    at = boff[:-1, None] + np.arange(4)[None, :]
+    rid = data[at + 4].copy().view("<i4")[:, 0].astype(np.int64)
+    pos = data[at + 8].copy().view("<i4")[:, 0].astype(np.int64)
+    rev = (data[boff[:-1] + 18] >> 4 & 1).astype(np.int64)
+    key = np.where(rid < 0, 1, rid) << 33 | (pos + 1) << 1 | rev
+    t0 = time.perf_counter()
+    order = np.argsort(key, kind="stable")
+    t_np = time.perf_counter() - t0
+    if not np.array_equal(order.astype(np.int32), b.get("bam_perm")):
+        raise SystemExit("the device's permutation is not numpy's stable argsort over the same keys")
+    log(f"sort: {n_rec} records, {bam_bytes} bytes; bgzf {z_unsorted} unsorted, {z_sorted} sorted; .bai {bai_bytes} bytes")
+    med = lambda v: spread(v)["median"]  # noqa: E731
+    return {"bam_bytes": int(bam_bytes), "records": int(n_rec), "key_bits": int(st_x.key_bits),
+            "f_bam_s": spread(tf), "f_bam_write_ms": spread(f_write),
+            "g_memcpy_d2d_bam_s": spread(tg), "g_memcpy_d2d_bam_ms_median": round(med(tg) * 1e3, 3),
+            "s_bam_sort_s": spread(ts), "s_key_ms": spread(key_ms), "s_sort_ms": spread(sort_ms), "s_copy_ms": spread(copy_ms),
+            "s_copy_gb_per_s": round(bam_bytes / (med(copy_ms) * 1e-3) / 1e9, 1),
+            "s_copy_over_f_write_median": round(med(copy_ms) / med(f_write), 3),
+            "s_copy_over_g_memcpy_median": round(med(copy_ms) * 1e-3 / med(tg), 3),
+            "t_bgzf_sorted_s": spread(tt), "t_bgzf_sorted_deflate_ms": spread(t_def), "t_bgzf_sorted_bytes": int(z_sorted),
+            "u_bgzf_unsorted_s": spread(tu), "u_bgzf_unsorted_deflate_ms": spread(u_def), "u_bgzf_unsorted_bytes": int(z_unsorted),
+            "x_bam_index_s": spread(tx), "x_index_ms": spread(index_ms), "x_bai_bytes": int(bai_bytes),
+            "x_bins": int(st_x.n_bins), "x_chunks": int(st_x.n_chunks), "x_intv": int(st_x.n_intv),
+            "host_numpy_stable_argsort_s": round(t_np, 4)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=1_000_000)
@@ -125,6 +196,7 @@ def main():
     ap.add_argument("--only-new", action="store_true")
     ap.add_argument("--only-out", action="store_true")
     ap.add_argument("--bgzf", action="store_true")
+    ap.add_argument("--sort", action="store_true")
     ap.add_argument("--zlib-chunks", type=int, default=256)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -224,10 +296,11 @@ def main():
                 "f_bam_over_d_text_median": round(spread(f_ms)["median"] / spread(d_ms)["median"], 3),
                 "g_memcpy_d2d_bam_s": spread(tg), "g_memcpy_d2d_bam_gb_per_s": round(bam_bytes / spread(tg)["median"] / 1e9, 1)}
 
-    if args.bgzf:
-        out = {"tool": "rec_bench", "legs": "bgzf", "lib": os.path.basename(bsw.HIP_LIB), "pairs": n // 2, "reads": n,
-               "read_len": args.read_len, "ref_mb": args.ref_mb}
-        out.update(bgzf_legs(args, eng, b, bam_bytes, bam, copy_bam, log))
+    if args.bgzf or args.sort:
+        out = {"tool": "rec_bench", "legs": "bgzf" if args.bgzf else "sort", "lib": os.path.basename(bsw.HIP_LIB), "pairs": n // 2,
+               "reads": n, "read_len": args.read_len, "ref_mb": args.ref_mb}
+        out.update(bgzf_legs(args, eng, b, bam_bytes, bam, copy_bam, log) if args.bgzf else
+                   sort_legs(args, eng, b, bam_bytes, bam, copy_bam, l_pac, log))
         line = json.dumps(out)
         print(line, flush=True)
         if args.out:
