@@ -32,6 +32,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/bsw_fmi.h"
+#include "../../include/bsw_fmi_launch.h"
 #include "bsw_fmi_internal.h"
 
 namespace {
@@ -963,6 +964,7 @@ struct bsw_fmi {
     int64_t dev_bytes = 0;
     int64_t tie_groups = 0;
     float build_s = 0, kernel_ms = 0;
+    int32_t last_launches = 0, last_entry_bytes = 0;   // the last seeding call (bsw_fmi_last_launch)
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void *d_scratch = nullptr;
@@ -1031,9 +1033,14 @@ int launch_collect(bsw_fmi_t *f, const FmiDevT<U> &dv, const MemOpt &mo, const u
     }
     const size_t esz = packed ? sizeof(EntP) : sizeof(EntT<U>);
     // chunk so the two scratch vectors stay within 16 GB (of 288 GB: one launch for up to ~3M
-    // 151-bp reads with 16-byte entries)
+    // 151-bp reads with 16-byte entries); BSW_SMEM_SCRATCH_MB=<MiB> overrides the budget (tests:
+    // chunked launches at small sizes), values below 1 count as 1
+    size_t budget_mb = 16384;
+    if (const char *e = getenv("BSW_SMEM_SCRATCH_MB")) budget_mb = (size_t)std::max(1, atoi(e));
     const size_t per_read = (size_t)2 * scap * esz;
-    const int32_t chunk = (int32_t)std::max<size_t>(64, std::min<size_t>((size_t)n, ((size_t)16 << 30) / per_read));
+    const int32_t chunk = (int32_t)std::max<size_t>(64, std::min<size_t>((size_t)n, (budget_mb << 20) / per_read));
+    f->last_launches = 0;
+    f->last_entry_bytes = (int32_t)esz;
     const size_t need = per_read * (size_t)std::min(chunk, n);
     if (need > f->scratch_bytes) {
         if (f->d_scratch) (void)hipFree(f->d_scratch);
@@ -1059,6 +1066,7 @@ int launch_collect(bsw_fmi_t *f, const FmiDevT<U> &dv, const MemOpt &mo, const u
                                m, (EntT<U> *)f->d_scratch, scap, d_mems, cap, d_cnt, f->d_err);
         }
         if (hipGetLastError() != hipSuccess) return BSW_E_HIP;
+        ++f->last_launches;
     }
     (void)hipEventRecord(f->ev1, s);
     int32_t herr = 0;
@@ -1507,6 +1515,14 @@ int bsw_fmi_last_kernel_ms(const bsw_fmi_t *f, float *ms)
 {
     if (!f || !ms) return BSW_E_INVAL;
     *ms = f->kernel_ms;
+    return BSW_OK;
+}
+
+int bsw_fmi_last_launch(const bsw_fmi_t *f, int32_t *launches, int32_t *entry_bytes)
+{
+    if (!f || !launches || !entry_bytes) return BSW_E_INVAL;
+    *launches = f->last_launches;
+    *entry_bytes = f->last_entry_bytes;
     return BSW_OK;
 }
 

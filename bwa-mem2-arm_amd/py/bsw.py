@@ -61,7 +61,9 @@ BGZF_MAX_BLOCK, BGZF_EOF = 0xff00, 1
 # include/bsw_bamsort.h (additive likewise: BSW_BAMSORT_API)
 BAMSORT_SYMBOLS = ("bsw_bam_sort", "bsw_bam_sort_resident", "bsw_bam_index", "bsw_bam_index_resident",
                    "bsw_bamsort_last_stats")
-BAMSORT_PERM_TILE = 8192            # bytes of output per workgroup of the permute kernel (bsw_bamsort_k.h: kPermTile), for tests
+# include/bsw_fmi_launch.h (additive likewise: BSW_FMI_LAUNCH_API)
+FMI_LAUNCH_SYMBOLS = ("bsw_fmi_last_launch",)
+BAMSORT_PERM_TILE = 8192           # bytes of output per workgroup of the permute kernel (bsw_bamsort_k.h: kPermTile), for tests
 BAMSORT_SORT_TILE = 4096            # a size above which the radix sort runs over more than one of its tiles, for tests
 CONTIG_MAX_NAME = 63
 
@@ -284,6 +286,8 @@ def hip_lib():
         L.bsw_set_contigs.restype = ctypes.c_int
         L.bsw_fmi_set_contigs.argtypes = [P, i32, P]
         L.bsw_fmi_set_contigs.restype = ctypes.c_int
+        L.bsw_fmi_last_launch.argtypes = [P, P, P]
+        L.bsw_fmi_last_launch.restype = ctypes.c_int
         L.bsw_get_scores_packed_device.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int, P, P]
         if hasattr(L, "bsw_sort_order_device"):     # test hook, no part of the ABI (an older experiment build lacks it)
             L.bsw_sort_order_device.argtypes = [P, P, ctypes.c_int32, ctypes.c_int, ctypes.c_int, P]
@@ -1658,6 +1662,12 @@ class Fmi:
         v = ctypes.c_float()
         _check(hip_lib().bsw_fmi_last_kernel_ms(self._f, ctypes.byref(v)))
         return v.value
+
+    def last_launch(self) -> tuple:
+        """bsw_fmi_last_launch: (SMEM kernel launches, scratch entry bytes) of the last seeding call"""
+        n, e = ctypes.c_int32(), ctypes.c_int32()
+        _check(hip_lib().bsw_fmi_last_launch(self._f, ctypes.byref(n), ctypes.byref(e)))
+        return n.value, e.value
 
     def mem_chain_device(self, d_len: int, n: int, d_mems: int, cap: int, d_cnt: int, d_seeds: int, d_sr: int,
                          d_sc: int, seed_cap: int, opt: "ChainOpt | None" = None, stream: int = 0):

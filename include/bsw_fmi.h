@@ -132,7 +132,8 @@ int  bsw_fmi_sa_device(bsw_fmi_t *fmi, const uint64_t *d_k, int64_t n, int64_t *
  * ~1 s for a 3 Gb genome.  BSW_E_NODEV for a host-only index. */
 int  bsw_fmi_check(bsw_fmi_t *fmi, int64_t *bad);
 
-/* The last seeding call's SMEM kernel time (HIP events). */
+/* The last seeding call's SMEM kernel time (HIP events).  (Its number of launches and scratch
+ * entry size: bsw_fmi_launch.h.) */
 int  bsw_fmi_last_kernel_ms(const bsw_fmi_t *fmi, float *ms);
 
 /* ---------------------------------------------------------------- seeds -> chains
