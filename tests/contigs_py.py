@@ -174,6 +174,7 @@ def mem_chain_read(tab, opt, sa, l_pac, read_len, mems, tr):
     mc.introsort(a, lambda x, y: x["w"] > y["w"])
     beg = lambda c: c["seeds"][0][1]                           # noqa: E731
     end = lambda c: c["seeds"][-1][1] + c["seeds"][-1][2]      # noqa: E731
+    ml, dr = mc._f32(opt["mask_level"]), mc._f32(opt["drop_ratio"])   # C: int * float is a float product
     a[0]["kept"] = 3
     kept = [0]
     for i in range(1, len(a)):
@@ -183,11 +184,11 @@ def mem_chain_read(tab, opt, sa, l_pac, read_len, mems, tr):
             b_max, e_min = max(beg(a[j]), beg(a[i])), min(end(a[j]), end(a[i]))
             if e_min > b_max:
                 min_l = min(end(a[i]) - beg(a[i]), end(a[j]) - beg(a[j]))
-                if e_min - b_max >= min_l * opt["mask_level"] and min_l < opt["max_chain_gap"]:
+                if mc._f32(e_min - b_max) >= mc._f32(min_l) * ml and min_l < opt["max_chain_gap"]:
                     large = True
                     if a[j]["first"] < 0:
                         a[j]["first"] = i
-                    if a[i]["w"] < a[j]["w"] * opt["drop_ratio"] and a[j]["w"] - a[i]["w"] >= opt["min_seed_len"] << 1:
+                    if mc._f32(a[i]["w"]) < mc._f32(a[j]["w"]) * dr and a[j]["w"] - a[i]["w"] >= opt["min_seed_len"] << 1:
                         broke = True
                         break
         if not broke:

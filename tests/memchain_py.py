@@ -3,7 +3,15 @@ ks_introsort for the weight sort) -- the checker of oracle/chain_ref.c on small 
 
 Written against the same upstream semantics as the C oracle but with Python structures: chains
 as dicts in a list kept sorted by start (kbtree stand-in with the same duplicate rule), the
-introsort over a Python list by indices.  Slow; for a few hundred reads."""
+introsort over a Python list by indices.  mem_chain_flt's two float comparisons (mask_level,
+drop_ratio) are done in numpy.float32: C multiplies int * float in float.  Slow; for a few
+thousand small reads."""
+
+import numpy as np
+
+
+def _f32(x):
+    return np.float32(x)
 
 
 def _test_and_merge(opt, l_pac, c, p):
@@ -159,6 +167,7 @@ def mem_chain_read(opt, sa, l_pac, read_len, mems):
     introsort(a, lambda x, y: x["w"] > y["w"])
     beg = lambda c: c["seeds"][0][1]                           # noqa: E731
     end = lambda c: c["seeds"][-1][1] + c["seeds"][-1][2]      # noqa: E731
+    ml, dr = _f32(opt["mask_level"]), _f32(opt["drop_ratio"])   # C: int * float is a float product
     a[0]["kept"] = 3
     kept = [0]
     for i in range(1, len(a)):
@@ -168,11 +177,11 @@ def mem_chain_read(opt, sa, l_pac, read_len, mems):
             b_max, e_min = max(beg(a[j]), beg(a[i])), min(end(a[j]), end(a[i]))
             if e_min > b_max:
                 min_l = min(end(a[i]) - beg(a[i]), end(a[j]) - beg(a[j]))
-                if e_min - b_max >= min_l * opt["mask_level"] and min_l < opt["max_chain_gap"]:
+                if _f32(e_min - b_max) >= _f32(min_l) * ml and min_l < opt["max_chain_gap"]:
                     large = True
                     if a[j]["first"] < 0:
                         a[j]["first"] = i
-                    if a[i]["w"] < a[j]["w"] * opt["drop_ratio"] and a[j]["w"] - a[i]["w"] >= opt["min_seed_len"] << 1:
+                    if _f32(a[i]["w"]) < _f32(a[j]["w"]) * dr and a[j]["w"] - a[i]["w"] >= opt["min_seed_len"] << 1:
                         broke = True
                         break
         if not broke:
