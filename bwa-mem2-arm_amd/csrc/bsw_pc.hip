@@ -46,7 +46,7 @@ constexpr int kPcChunkDw = 17;           // dwords per lane per 64-row target ch
 #define BSW_PC_EXP_HALFHEAD 0
 #endif
 #ifdef BSW_PC_STATS
-__device__ unsigned long long g_pc_stats[13];
+__device__ unsigned long long g_pc_stats[19];
 // per-wave schedule record (tools/pc_times.py): start / end (s_memrealtime, 100 MHz), XCC id and
 // HW_ID (CU / SIMD / SE), rows run -- the launch's occupancy over time, ramp-up and tail
 constexpr int kPcTimesMax = 1 << 16;
@@ -713,6 +713,61 @@ template <int QMAX, bool BY> constexpr bool pc_left_prune()
 constexpr int kPcPruned = 1 << 8;         // the wave's pruned mark, a spare bit of gz's register
 template <bool PRUNE> __device__ __forceinline__ int pc_gz_of(int gz) { return PRUNE ? (gz & (kPcPruned - 1)) : gz; }
 
+// Right prune: a wave-uniform right cap.  Past the first rows the insertion tail of
+// the diagonal is positive out to the query's end, so every row runs FAST groups to qlen although most of
+// those cells can no longer reach the lane's current best.  cap4 (a slot index, a multiple of 4; 4 NG = no
+// cap) clamps every lane's band end at the row head: the groups above it leave the entered set through the
+// band-end reduction and group cap4 / 4 runs as the row's right-edge group.  At the refresh the cap walks
+// down over groups whose every slot, in every staying lane, has UB + SLACK < T = best - MARGIN (pc_rp_group);
+// every row of a marked wave checks what leaves the computed columns -- it all goes through h1 -- against
+// T, and a lane is final only with gsc >= P, the largest threshold ever applied to it: the others are computed
+// again by the redo pass.  The rule speculates on the lane's final gscore alone.
+//   MARGIN, SLACK, SLACK2, K, ROW0: T = best - MARGIN; the zeroing test's and the soft retreat's distance from T;
+//   the rows since a staying lane's last new best and the first row the precheck allows (profiles/right_prune/ab.txt)
+//   BSW_PC_RIGHT_PRUNE 0 : off (make ab AB_FLAGS=-DBSW_PC_RIGHT_PRUNE=0); the classes of BSW_PC_PRUNE_QMIN
+#ifndef BSW_PC_RIGHT_PRUNE
+#define BSW_PC_RIGHT_PRUNE 1
+#endif
+#ifndef BSW_PC_RP_MARGIN
+#define BSW_PC_RP_MARGIN 20
+#endif
+#ifndef BSW_PC_RP_SLACK
+#define BSW_PC_RP_SLACK 12
+#endif
+#ifndef BSW_PC_RP_SLACK2
+#define BSW_PC_RP_SLACK2 11
+#endif
+#ifndef BSW_PC_RP_K
+#define BSW_PC_RP_K 16
+#endif
+#ifndef BSW_PC_RP_WALK_MASK        // a marked wave walks on refresh rows with (i & MASK) == (BSW_PC_SKIP_ROW & MASK)
+#define BSW_PC_RP_WALK_MASK 15
+#endif
+#ifndef BSW_PC_RP_RWIN             // the retreat looks at lanes whose band end is within RWIN slots of the cap
+#define BSW_PC_RP_RWIN 4
+#endif
+#ifndef BSW_PC_RP_ROW0
+#define BSW_PC_RP_ROW0 25
+#endif
+template <int QMAX, bool BY> constexpr bool pc_right_prune() { return BSW_PC_RIGHT_PRUNE && pc_left_prune<QMAX, BY>(); }
+// per-lane state of the rule, in bits of the pair pointer's high half that no address uses (bits 53 .. 63): the
+// lane's P as max(T, 0) + 1 in the top ten bits (0: no threshold was ever applied; H <= 255 in this kernel's
+// regime, so T < 256), where a plain unsigned max of the high dword updates it, and the clipped mark under it
+constexpr int kPcPShift = 54;                          // P field: bits 54 .. 63
+constexpr uintptr_t kPcClipped = (uintptr_t)1 << 53;   // the lane's band end has sat at the cap: it takes the
+                                                       // row's crossing certificate from then on
+constexpr uint32_t kPcClipHi = (uint32_t)(kPcClipped >> 32), kPcLowHi = (1u << (kPcPShift - 32)) - 1u;
+__device__ __forceinline__ uint32_t pc_sp_hi(const SeqPair *sp) { return (uint32_t)((uintptr_t)sp >> 32); }
+__device__ __forceinline__ SeqPair *pc_sp_set(const SeqPair *sp, uint32_t hi, bool rd)
+{
+    return (SeqPair *)(((uintptr_t)hi << 32) | (uintptr_t)(uint32_t)(uintptr_t)sp | (uintptr_t)rd);
+}
+// the pointer's high dword `hi` with its P field raised to max(t, 0) + 1
+__device__ __forceinline__ uint32_t pc_rp_raise(uint32_t hi, int t)
+{
+    return max(hi, ((uint32_t)(max(t, 0) + 1) << (kPcPShift - 32)) | (hi & kPcLowHi));
+}
+
 // one plane register of the prune bound (slots 2K, 2K+1): c = v + gain where v > 0 (gw = packed
 // qlen for H, qlen - 1 for E), cleared where the slot is left of the lane's first one (bw = packed
 // beg for H: s > beg; beg - 1 for E: s >= beg), ub = max(ub, c).  0 <= v <= 255; a positive v sits in
@@ -808,6 +863,47 @@ __device__ __forceinline__ void pc_gz_refresh(std::integer_sequence<int, S...>, 
     (pc_gz_seg<QMAX, BY, PRUNE, S>(std::make_integer_sequence<int, 8>{}, hh, ee, live, gz, pp), ...);
 }
 
+// group G of the right cap's walk: taken only when it is the group under the cap (uniform) and lies at or
+// above gz + 2.  ub = the largest UB of its slots (pc_pb_reg without a left limit) and the floor
+// 1 + (qlen - 4G): a zero slot may turn positive on the next row through the F chain.
+template <int QMAX, int G>
+__device__ __forceinline__ void pc_rp_group(uint32_t (&hh)[QMAX / 2], uint32_t (&ee)[QMAX / 2], bool live, int gzv,
+                                            int &cap4, int qlen, int t, uint32_t &nev)
+{
+    if (cap4 != 4 * G + 4 || G < gzv + 2) return;              // uniform
+    uint32_t ub = 0;
+    const uint32_t qw = pack2(qlen), qm1w = pack2(qlen - 1), allw = 0xffffffffu;   // every slot: s > -1
+    pc_pb_reg<2 * G + 1>(hh[2 * G + 1], qw, allw, ub);
+    pc_pb_reg<2 * G>(hh[2 * G], qw, allw, ub);
+    pc_pb_reg<2 * G + 1>(pc_pos2(ee[2 * G + 1]), qm1w, allw, ub);
+    pc_pb_reg<2 * G>(pc_pos2(ee[2 * G]), qm1w, allw, ub);
+    const int u = max((int)max(ub & 0xffffu, ub >> 16), 1 + qlen - 4 * G);
+    if (__ballot(live && u + BSW_PC_RP_SLACK >= t) == 0) {
+        hh[2 * G] = 0u; hh[2 * G + 1] = 0u; ee[2 * G] = 0u; ee[2 * G + 1] = 0u;
+        cap4 = 4 * G;
+        nev += 1;
+    }
+}
+
+template <int QMAX, int S, int... K>
+__device__ __forceinline__ void pc_rp_seg(std::integer_sequence<int, K...>, uint32_t (&hh)[QMAX / 2],
+                                          uint32_t (&ee)[QMAX / 2], bool live, int gzv, int &cap4, int qlen, int t,
+                                          uint32_t &nev)
+{
+    if (((cap4 - 4) >> 5) < S) return;                      // uniform: the cap lies below this segment
+    (pc_rp_group<QMAX, 8 * S + 7 - K>(hh, ee, live, gzv, cap4, qlen, t, nev), ...);
+}
+
+// the walk, from the group under the cap downward (segments of 8 groups, top first)
+template <int QMAX, int... S>
+__device__ __forceinline__ void pc_rp_walk(std::integer_sequence<int, S...>, uint32_t (&hh)[QMAX / 2],
+                                           uint32_t (&ee)[QMAX / 2], bool live, int gzv, int &cap4, int qlen, int t,
+                                           uint32_t &nev)
+{
+    constexpr int NS = sizeof...(S);
+    (pc_rp_seg<QMAX, NS - 1 - S>(std::make_integer_sequence<int, 8>{}, hh, ee, live, gzv, cap4, qlen, t, nev), ...);
+}
+
 // WPB waves per workgroup: with 1, a wave's slot (and its LDS) is reused as soon as that wave
 // ends, instead of when the slowest of its block's waves ends.
 //
@@ -828,6 +924,7 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
                                                     int32_t *__restrict__ rcnt)
 {
     constexpr bool PRUNE = !REDO && pc_left_prune<QMAX, BY>();
+    constexpr bool RP = !REDO && pc_right_prune<QMAX, BY>();
     constexpr int NG = QMAX / 4;        // groups = query words (4 codes each)
     constexpr int CDW = kPcChunkDw;     // target dwords per lane per 64-row chunk
 #ifdef BSW_PC_STATS
@@ -852,6 +949,12 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
         if (qlen >= QMAX || qlen < 0 || tlen < 0 || h0 < 0 || h0 + min(qlen, tlen) > 255 || idr < 0 || idq < 0) {
             atomicOr(err, 1);
             valid = false;
+        }
+        if constexpr (!REDO && pc_right_prune<QMAX, BY>()) {      // the rule's bits of the pair pointer must be free
+            if ((uintptr_t)sp >> 53) {
+                atomicOr(err, 1);
+                valid = false;
+            }
         }
     }
     // query codes, 4 per VGPR in byte order {c0, c2, c1, c3}: aligned dword loads (a dword
@@ -960,6 +1063,14 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
     int gz = 0;                             // left skip: groups below gz are all-zero in every live lane
     (void)gz;
     PcPrune pp{false, 0, 0, 0, 0u};         // left prune: the refresh's inputs
+    int cap4 = QMAX;                        // right prune: the cap's slot (QMAX = 4 NG: none), wave-uniform
+    bool rmark = false;                     // ... and the wave's mark: the cap has been set at least once
+    uint32_t nrev = 0;                      // (BSW_PC_STATS: groups the cap's walk passed over)
+    (void)cap4; (void)rmark; (void)nrev;
+#ifdef BSW_PC_STATS
+    uint32_t nrcap = 0, nrret = 0, rcause = 0;   // groups the cap removed, retreats (uniform); this lane's redo cause
+    (void)nrcap; (void)nrret; (void)rcause;
+#endif
     for (int i = 0;; ++i) {
         const bool act = alive && i < tlen;
         alive = act;
@@ -991,7 +1102,15 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
         const uint2 pr = s_prof[min(tcode, 7u)];   // one ds_read_b64 (codes > 4 score as N)
         __builtin_amdgcn_sched_barrier(0);
         const int beg = max(0, i - wl);
-        const int end = min(min(endc, i + wl + 1), qlen);
+        int endcl = min(min(endc, i + wl + 1), qlen);
+#ifdef BSW_PC_STATS
+        if constexpr (RP) {                // the groups between the cap and the static band end
+            const int eu = wave_max(act ? min(i + wl + 1, qlen) : -1), ec = wave_max(act ? min(endcl, cap4) : -1);
+            if (cap4 < QMAX && ec >= 0) nrcap += (uint32_t)max((min(eu, QMAX - 1) >> 2) - (min(ec, QMAX - 1) >> 2), 0);
+        }
+#endif
+        if constexpr (RP) endcl = min(endcl, cap4);   // the right cap (§3 item 13): one v_min with a uniform operand
+        const int end = endcl;
         endc = end;
 #if BSW_PC_EXP_HALFHEAD
         // experiment build only (make ab AB_FLAGS=-DBSW_PC_EXP_HALFHEAD=1; WRONG outputs): the row
@@ -1074,15 +1193,36 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
                     // one whose row maximum is 0 retires with its outputs final; the others -- and a
                     // lane whose band end would leave qlen (h1 == 0) -- are computed again.  The
                     // mark travels in the low bit of sp (SeqPair is 4-byte aligned).
+                    // (a wave under the right cap, item 13, takes the z-drop half of it on its own mark)
 #if BSW_PC_PRUNE_BRANCH
-                    if (gz & kPcPruned)
+                    if ((gz & kPcPruned) || (RP && rmark))
 #endif
                     {
-                        const bool rd = (gz & kPcPruned) != 0 &&
+                        const bool rd = ((gz & kPcPruned) != 0 || (RP && rmark)) &&
                                         ((act && !better && m > 0 && kp.zdrop > 0 && best - m > kp.zdrop) ||
-                                         (alive && h1 == 0));
+                                         ((gz & kPcPruned) != 0 && alive && h1 == 0));
                         alive = alive && !rd;
                         sp = (SeqPair *)((uintptr_t)sp | (uintptr_t)rd);
+#ifdef BSW_PC_STATS
+                        rcause = (rd && !rcause) ? 2u : rcause;
+#endif
+                    }
+                }
+                if constexpr (RP) {
+                    // the crossing certificate of a wave under the right cap (§3 item 13), behind one uniform
+                    // test: a lane whose band end has sat at the cap lets H(i, end-1) = h1 leave the computed
+                    // columns, diagonally or along the row, and h1's potential must stay below T = best - MARGIN
+                    if (rmark) {
+                        const int t = best - BSW_PC_RP_MARGIN, phi = h1 + (qlen - end);
+                        uint32_t hi = pc_sp_hi(sp);
+                        const bool cl = act && end < qlen && (end == cap4 || (hi & kPcClipHi) != 0);
+                        const bool rdc = cl && h1 > 0 && phi >= t;
+                        hi = cl ? pc_rp_raise(hi | kPcClipHi, t) : hi;    // (a redo lane's P is never read)
+                        sp = pc_sp_set(sp, hi, rdc);
+                        alive = alive && !rdc;
+#ifdef BSW_PC_STATS
+                        rcause = (rdc && !rcause) ? 1u : rcause;
+#endif
                     }
                 }
             }
@@ -1139,6 +1279,42 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
                     }
                     pc_gz_refresh<QMAX, BY, PRUNE>(std::make_integer_sequence<int, (NG + 7) / 8>{}, hh, ee, alive, gz,
                                                    pp);
+                    if constexpr (RP) {
+                        // the right cap: precheck (i >= ROW0 and every staying lane with a new best in the last
+                        // K rows: on a growing diagonal, where gscore will follow best), then the walk; a
+                        // failed precheck under a cap retreats one group
+                        if (__ballot(alive && !(i >= BSW_PC_RP_ROW0 && i - best_i <= BSW_PC_RP_K))) {
+                            if (cap4 < QMAX) {
+                                cap4 += 4;
+#ifdef BSW_PC_STATS
+                                nrret += 1;
+#endif
+                            }
+                        } else if ((!rmark || (i & BSW_PC_RP_WALK_MASK) == (BSW_PC_SKIP_ROW & BSW_PC_RP_WALK_MASK)) &&
+                                   __ballot(alive)) {
+                            int ql;                 // (opaque, as pp.qlen)
+                            asm volatile("v_mov_b32_e32 %0, %1" : "=v"(ql) : "v"(qlen));
+                            const uint32_t nev0 = nrev;
+                            pc_rp_walk<QMAX>(std::make_integer_sequence<int, NG / 8>{}, hh, ee, alive,
+                                             pc_gz_of<PRUNE>(gz), cap4, ql, best - BSW_PC_RP_MARGIN, nrev);
+                            if (nrev != nev0) {     // uniform: T was applied to every staying lane
+                                rmark = true;
+                                sp = pc_sp_set(sp, alive ? pc_rp_raise(pc_sp_hi(sp), best - BSW_PC_RP_MARGIN) : pc_sp_hi(sp), false);
+                            }
+                        }
+                        // the soft retreat, after the walk: one group up when a staying lane's crossing value, at the
+                        // cap or within RWIN slots under it, comes near its threshold (one ballot; the certificate
+                        // is what soundness rests on).  A cap the walk has just put above a moving band edge is
+                        // taken back before the edge reaches it: a band narrower than the query never clips
+                        if (rmark && cap4 < QMAX &&
+                            __ballot(alive && end < qlen && end + BSW_PC_RP_RWIN >= cap4 &&
+                                     h1 + (qlen - end) + BSW_PC_RP_SLACK2 >= best - BSW_PC_RP_MARGIN)) {
+                            cap4 += 4;
+#ifdef BSW_PC_STATS
+                            nrret += 1;
+#endif
+                        }
+                    }
                 }
             }
 #ifdef BSW_PC_STATS
@@ -1196,6 +1372,16 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
         // redo lanes: their pair index (read again: no register held it across the loop) appended to
         // the class's list, one atomic add per wave, lanes at base + rank.  At most one entry per
         // valid lane of the launch, so every index written is below the class's pair count.
+        if constexpr (RP) {
+            // the final certificate: a lane is final only when gscore reached every threshold applied to it;
+            // then the rule's bits leave the pointer
+            const int pf = (int)((uintptr_t)sp >> kPcPShift);
+            const bool rdf = pf != 0 && gsc < pf - 1;
+#ifdef BSW_PC_STATS
+            rcause = (rdf && !((uintptr_t)sp & 1u)) ? 3u : rcause;
+#endif
+            sp = (SeqPair *)((((uintptr_t)sp) | (uintptr_t)rdf) & (kPcClipped - 1));
+        }
         const bool rd = ((uintptr_t)sp & 1u) != 0;          // never an invalid lane (sp == nullptr)
         const unsigned long long rb = __ballot(rd);
         if (rb) {                                           // uniform
@@ -1211,6 +1397,13 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
         if (ln == 0) {
             atomicAdd(&g_pc_stats[11], (unsigned long long)pp.npr);
             atomicAdd(&g_pc_stats[12], (unsigned long long)__popcll(rb));
+            atomicAdd(&g_pc_stats[13], (unsigned long long)nrev);
+            atomicAdd(&g_pc_stats[14], (unsigned long long)nrcap);
+            atomicAdd(&g_pc_stats[15], (unsigned long long)nrret);
+        }
+        for (unsigned c = 1; c <= 3; ++c) {
+            const unsigned nc = (unsigned)__popcll(__ballot(rd && rcause == c));
+            if (ln == 0 && nc) atomicAdd(&g_pc_stats[15 + c], (unsigned long long)nc);
         }
 #endif
         if (rd) sp = nullptr;
@@ -1228,12 +1421,15 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
 #ifdef BSW_PC_STATS
 // [rows, groups entered, fast, masked-R, masked-L, lastpos scans, waves, uniform-end rows, early-stop scan
 // rows, lanes retired by the scalar bound, lanes retired by the per-cell bound, non-zero groups the left
-// prune passed over, redo lanes] summed over waves
+// prune passed over, redo lanes, groups the right cap's walk passed over, groups the cap removed from rows (up
+// to the static band end: an upper bound of what the cap removes), cap retreats, redo lanes by cause: crossing,
+// item 12's certificate (z-drop, or h1 == 0 in a left-pruned wave), final]
+// summed over waves
 extern "C" int bsw_pc_stats(unsigned long long *out, int reset)
 {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pc_stats), 13 * sizeof(unsigned long long)) != hipSuccess) return -5;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pc_stats), 19 * sizeof(unsigned long long)) != hipSuccess) return -5;
     if (reset) {
-        unsigned long long z[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        unsigned long long z[19] = {0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_pc_stats), z, sizeof(z)) != hipSuccess) return -5;
     }
     return 0;
