@@ -16,7 +16,7 @@ SYNTH    := $(LIBDIR)/libbsw_synth.so
 SHIMTEST := $(LIBDIR)/bsw_shim_example
 ORACLE   := oracle/liboracle.so
 
-HIP_HDRS := $(CSRC)/bsw_devcache.h $(CSRC)/bsw_pool.h $(CSRC)/bsw_kernels.h $(CSRC)/bsw_mate_k.h include/bsw_mate.h $(CSRC)/bsw_global_k.h include/bsw_global.h $(CSRC)/bsw_ext_k.h $(CSRC)/bsw_aln_k.h include/bsw_aln.h $(CSRC)/bsw_sel_k.h $(CSRC)/bsw_sel_dev.h include/bsw_sel.h $(CSRC)/bsw_pe_k.h include/bsw_pe.h $(CSRC)/bsw_matesw_k.h include/bsw_matesw.h $(CSRC)/bsw_rec_k.h include/bsw_rec.h include/bsw_bam.h $(CSRC)/bsw_bgzf_k.h include/bsw_bgzf.h $(CSRC)/bsw_bamsort_k.h include/bsw_bamsort.h $(CSRC)/bsw_wave.h $(CSRC)/bsw_formulas.h $(CSRC)/bsw_contig_seg.h include/bsw_contigs.h $(CSRC)/bsw_stage_k.h $(CSRC)/bsw_internal.h $(CSRC)/bsw_stage_plan.h $(CSRC)/bsw_engine.h $(CSRC)/bsw_sort.h $(CSRC)/bsw_fmi_internal.h include/bsw.h include/bsw_seqpair.h include/bsw_ext.h include/bsw_batch.h include/bsw_fmi.h include/bsw_fmi_launch.h
+HIP_HDRS := $(CSRC)/bsw_devcache.h $(CSRC)/bsw_pool.h $(CSRC)/bsw_kernels.h $(CSRC)/bsw_mate_k.h include/bsw_mate.h $(CSRC)/bsw_global_k.h include/bsw_global.h $(CSRC)/bsw_ext_k.h $(CSRC)/bsw_aln_k.h include/bsw_aln.h $(CSRC)/bsw_sel_k.h $(CSRC)/bsw_sel_dev.h include/bsw_sel.h $(CSRC)/bsw_pe_k.h include/bsw_pe.h $(CSRC)/bsw_matesw_k.h include/bsw_matesw.h $(CSRC)/bsw_rec_k.h include/bsw_rec.h include/bsw_bam.h $(CSRC)/bsw_bgzf_k.h include/bsw_bgzf.h $(CSRC)/bsw_bamsort_k.h include/bsw_bamsort.h $(CSRC)/bsw_wave.h $(CSRC)/bsw_pc_rules.h $(CSRC)/bsw_pc_group.h $(CSRC)/bsw_pc_scan.h $(CSRC)/bsw_formulas.h $(CSRC)/bsw_contig_seg.h include/bsw_contigs.h $(CSRC)/bsw_stage_k.h $(CSRC)/bsw_internal.h $(CSRC)/bsw_stage_plan.h $(CSRC)/bsw_engine.h $(CSRC)/bsw_sort.h $(CSRC)/bsw_fmi_internal.h include/bsw.h include/bsw_seqpair.h include/bsw_ext.h include/bsw_batch.h include/bsw_fmi.h include/bsw_fmi_launch.h
 
 # the product's objects; the experiment libraries below are this list with one object swapped
 OBJS := $(addprefix $(LIBDIR)/,bsw_kernels.o bsw_pc.o bsw_wv.o bsw_gq.o bsw_mate.o bsw_global.o bsw_ext_dev.o bsw_aln.o bsw_sel.o bsw_pe.o bsw_matesw.o bsw_rec.o bsw_bgzf.o bsw_bamsort.o bsw_stage.o \

@@ -1,5 +1,5 @@
 """The packed-column kernel's left prune as a CPU model of the KERNEL's loop
-(tests/left_prune_model.py): the left skip's model with gz also passing over non-zero groups that
+(tests/pc_wave_model.py with the right prune off): the left skip's model with gz also passing over non-zero groups that
 cannot reach gscore in any live lane, the wave-level `pruned` flag, the row-end certificate and the
 redo lanes recomputed without the rule.  It must give the oracle's six outputs on every pair, run
 no more rows per lane than the literal loop, remove a real share of the flagship's entered groups
@@ -12,33 +12,33 @@ import pytest
 
 import bsw
 import early_stop_model as esm
-import left_prune_model as lpm
-import left_skip_model as lsm
 import oracle
+import pc_batches as pcb
+import pc_wave_model as pwm
 
 
 @pytest.fixture(scope="module")
 def models(tmp_path_factory):
-    d = tmp_path_factory.mktemp("lp_model")
-    return lpm.build(d), esm.build(d)
+    d = tmp_path_factory.mktemp("pc_model")
+    return pwm.build(d), esm.build(d)
 
 
 def _check(models, params, pairs, ref, qer, w, order, tag, want=None, rows0=None):
     """The model with the prune on the lanes in `order`: 0 differing fields against the oracle,
     rows per lane no more than the literal loop's.  Returns (want, rows0, per-wave sums)."""
-    libs, elib = models
+    lib, elib = models
     if want is None:
         want = pairs.copy()
         oracle.get_scores(params, want, ref, qer, w, nthreads=8)
         _, rows0, _ = esm.run(elib, params, pairs, ref, qer, w, 0)
-    got, rows, _, wst = lpm.run(libs, params, pairs, ref, qer, w, order=order)
+    got, rows, _, wst = pwm.run(lib, params, pairs, ref, qer, w, order=order, rprune=False)
     for f in bsw.OUT_FIELDS:
         bad = np.flatnonzero(want[f] != got[f])
         assert len(bad) == 0, (f"{tag}: field {f} differs in {len(bad)} pairs; first {bad[0]} "
                                f"tlen={pairs['len1'][bad[0]]} qlen={pairs['len2'][bad[0]]} h0={pairs['h0'][bad[0]]} "
                                f"want {want[f][bad[0]]} got {got[f][bad[0]]}")
     assert (rows <= rows0).all(), f"{tag}: a lane ran more rows than the literal loop"
-    return want, rows0, wst.sum(0)
+    return want, rows0, wst[:, :5].sum(0)
 
 
 def test_model_random_shapes(models):
@@ -55,7 +55,7 @@ def test_model_random_shapes(models):
             pairs, ref, qer = esm.random_shapes(per, seed=2000 + k)
         params = oracle.make_params(zdrop=zdrop, end_bonus=eb)
         tag = f"w={w} zdrop={zdrop} end_bonus={eb}"
-        want, rows0, st = _check(models, params, pairs, ref, qer, w, lsm.default_order(pairs, ref, qer), tag + " sorted")
+        want, rows0, st = _check(models, params, pairs, ref, qer, w, pcb.default_order(pairs, ref, qer), tag + " sorted")
         tot["sorted"] += st
         shuffled = np.random.default_rng(k).permutation(len(pairs)).astype(np.int32)
         _, _, st = _check(models, params, pairs, ref, qer, w, shuffled, tag + " shuffled", want, rows0)
@@ -65,7 +65,7 @@ def test_model_random_shapes(models):
     while n + extra < 300_000:
         pairs, ref, qer = esm.random_shapes(per, seed=5000 + extra)
         want, rows0, st = _check(models, oracle.make_params(), pairs, ref, qer, 100,
-                                 lsm.default_order(pairs, ref, qer), "extra sorted")
+                                 pcb.default_order(pairs, ref, qer), "extra sorted")
         tot["sorted"] += st
         extra += len(pairs)
     n += extra
@@ -80,13 +80,13 @@ def test_model_c2(models):
     """100,000 pairs of the flagship batch (150 bp query, 300 bp window, w = 100) in the waves of
     the default sort key: exact, at least 5 % of the groups the skip alone enters removed, at most
     0.1 % of the lanes sent to the redo pass."""
-    libs, _ = models
+    lib, _ = models
     pairs, ref, qer = bsw.synth_batch(100_000)
     params = oracle.make_params()
-    order = lsm.default_order(pairs, ref, qer)
+    order = pcb.default_order(pairs, ref, qer)
     _, _, (rows, ent, skp, ev, redo) = _check(models, params, pairs, ref, qer, 100, order, "C2")
-    _, _, wst0 = lsm.run(libs[1], params, pairs, ref, qer, 100, order=order)
-    r0, e0, _ = wst0.sum(0)
+    _, _, _, wst0 = pwm.run(lib, params, pairs, ref, qer, 100, order=order, prune=False, rprune=False)
+    r0, e0, _ = wst0[:, :3].sum(0)
     share = 1.0 - ent / e0
     print(f"C2: rows per wave {rows / len(wst0):.1f} ({r0 / len(wst0):.1f} with the skip alone), groups entered per "
           f"row {ent / rows:.2f} ({e0 / r0:.2f}); share of entered groups removed {share:.4f}; prune events {ev}; "
@@ -96,31 +96,31 @@ def test_model_c2(models):
 
 
 BUILT = {
-    "a_c2_shaped": (lambda: lpm.c2_shaped(4096, 71), 100, dict(zdrop=100, end_bonus=5)),
-    "b_collapse_all": (lambda: lpm.late_collapse(1024, 72), 100, dict(zdrop=10)),
-    "b_collapse_one_in_8": (lambda: lpm.late_collapse(1024, 73, every=8), 100, dict(zdrop=10)),
-    "c_collapse_120_z100": (lambda: lpm.late_collapse(1024, 74, at=120), 100, dict(zdrop=100)),
-    "c_collapse_135_z0": (lambda: lpm.late_collapse(1024, 75, at=135), 100, dict(zdrop=0)),
-    "d_classes_w100": (lambda: lpm.class_edges(512, 76), 100, dict(zdrop=100, end_bonus=5)),
-    "d_classes_w20": (lambda: lpm.class_edges(512, 77), 20, dict(zdrop=100, end_bonus=5)),
-    "e_interior_zeros": (lambda: lsm.interior_zeros(2048, 66), 100, dict(zdrop=100, end_bonus=5)),
-    "e_pinned": (lambda: lsm.pinned_waves(5, 67, True), 100, lsm.PIN_SCORING),
-    "e_uneven_lifetimes": (lambda: lsm.uneven_lifetimes(30, 68), 100, dict(zdrop=100, end_bonus=5)),
-    "e_boundary_alive": (lambda: lsm.boundary_alive(2048, 65), 100, dict(zdrop=100, end_bonus=5)),
+    "a_c2_shaped": (lambda: pcb.c2_shaped(4096, 71), 100, dict(zdrop=100, end_bonus=5)),
+    "b_collapse_all": (lambda: pcb.late_collapse(1024, 72), 100, dict(zdrop=10)),
+    "b_collapse_one_in_8": (lambda: pcb.late_collapse(1024, 73, every=8), 100, dict(zdrop=10)),
+    "c_collapse_120_z100": (lambda: pcb.late_collapse(1024, 74, at=120), 100, dict(zdrop=100)),
+    "c_collapse_135_z0": (lambda: pcb.late_collapse(1024, 75, at=135), 100, dict(zdrop=0)),
+    "d_classes_w100": (lambda: pcb.class_edges(512, 76), 100, dict(zdrop=100, end_bonus=5)),
+    "d_classes_w20": (lambda: pcb.class_edges(512, 77), 20, dict(zdrop=100, end_bonus=5)),
+    "e_interior_zeros": (lambda: pcb.interior_zeros(2048, 66), 100, dict(zdrop=100, end_bonus=5)),
+    "e_pinned": (lambda: pcb.pinned_waves(5, 67, True), 100, pcb.PIN_SCORING),
+    "e_uneven_lifetimes": (lambda: pcb.uneven_lifetimes(30, 68), 100, dict(zdrop=100, end_bonus=5)),
+    "e_boundary_alive": (lambda: pcb.boundary_alive(2048, 65), 100, dict(zdrop=100, end_bonus=5)),
 }
 
 
 def test_model_built_cases(models):
     """The batches the GPU test runs, in the engine's wave layout: exact, each prunes, the
     z-drop collapse batches redo -- more than one wave's worth in one class."""
-    libs, elib = models
+    lib, elib = models
     for name, (make, w, sc) in BUILT.items():
         pairs, ref, qer = make()
         params = oracle.make_params(**sc)
         want = pairs.copy()
         oracle.get_scores(params, want, ref, qer, w, nthreads=8)
         _, rows0, _ = esm.run(elib, params, pairs, ref, qer, w, 0)
-        got, rows, redo, wst = lpm.run_planned(libs, params, pairs, ref, qer, w)
+        got, rows, redo, wst = pwm.run_planned(lib, params, pairs, ref, qer, w, rprune=False)
         for f in bsw.OUT_FIELDS:
             assert np.array_equal(want[f], got[f]), f"{name}: field {f} differs"
         assert (rows <= rows0).all()
@@ -132,7 +132,7 @@ def test_model_built_cases(models):
         if name.startswith(("a_", "c_")):
             assert nredo == 0, f"{name}: {nredo} redo lanes"
         if name.startswith("d_"):            # every class that carries the rule prunes
-            cls = lsm.qmax_class(pairs)[lsm.default_order(pairs, ref, qer)][::64]
+            cls = pcb.qmax_class(pairs)[pcb.default_order(pairs, ref, qer)][::64]
             assert len(cls) == len(wst)
             for c in (3, 4):                 # QMAX 128 and 160; the 96 class is compiled without the rule
                 assert wst[cls == c, 3].sum() > 0, f"{name}: class {c} never pruned"

@@ -1,5 +1,5 @@
 """The packed-column kernel's left skip as a CPU model of the KERNEL's loop
-(tests/left_skip_model.py): 64 lanes per wave with the static left edge, the wave-uniform prefix
+(tests/pc_wave_model.py with both prunes off): 64 lanes per wave with the static left edge, the wave-uniform prefix
 bound gz refreshed on the kernel's phase from the live lanes' stored rows, groups below gz not
 computed, and the early stop scanning only entered groups.  It must give the oracle's six outputs
 on every pair, run no more rows per lane than the literal loop -- and must actually skip groups,
@@ -12,14 +12,15 @@ import pytest
 
 import bsw
 import early_stop_model as esm
-import left_skip_model as lsm
 import oracle
+import pc_batches as pcb
+import pc_wave_model as pwm
 
 
 @pytest.fixture(scope="module")
 def models(tmp_path_factory):
-    d = tmp_path_factory.mktemp("ls_model")
-    return lsm.build(d), esm.build(d)
+    d = tmp_path_factory.mktemp("pc_model")
+    return pwm.build(d), esm.build(d)
 
 
 def _check(models, params, pairs, ref, qer, w, order, tag, want=None, rows0=None):
@@ -30,14 +31,14 @@ def _check(models, params, pairs, ref, qer, w, order, tag, want=None, rows0=None
         want = pairs.copy()
         oracle.get_scores(params, want, ref, qer, w, nthreads=8)
         _, rows0, _ = esm.run(elib, params, pairs, ref, qer, w, 0)
-    got, rows, wst = lsm.run(lib, params, pairs, ref, qer, w, order=order)
+    got, rows, _, wst = pwm.run(lib, params, pairs, ref, qer, w, order=order, prune=False, rprune=False)
     for f in bsw.OUT_FIELDS:
         bad = np.flatnonzero(want[f] != got[f])
         assert len(bad) == 0, (f"{tag}: field {f} differs in {len(bad)} pairs; first {bad[0]} "
                                f"tlen={pairs['len1'][bad[0]]} qlen={pairs['len2'][bad[0]]} h0={pairs['h0'][bad[0]]} "
                                f"want {want[f][bad[0]]} got {got[f][bad[0]]}")
     assert (rows <= rows0).all(), f"{tag}: a lane ran more rows than the literal loop"
-    return want, rows0, wst.sum(0)
+    return want, rows0, wst[:, :3].sum(0)
 
 
 def test_model_random_shapes(models):
@@ -56,7 +57,7 @@ def test_model_random_shapes(models):
             pairs, ref, qer = esm.random_shapes(per, seed=2000 + k)
         params = oracle.make_params(zdrop=zdrop, end_bonus=eb)
         tag = f"w={w} zdrop={zdrop} end_bonus={eb}"
-        want, rows0, st = _check(models, params, pairs, ref, qer, w, lsm.default_order(pairs, ref, qer), tag + " sorted")
+        want, rows0, st = _check(models, params, pairs, ref, qer, w, pcb.default_order(pairs, ref, qer), tag + " sorted")
         tot["sorted"] += st
         shuffled = np.random.default_rng(k).permutation(len(pairs)).astype(np.int32)
         _, _, st = _check(models, params, pairs, ref, qer, w, shuffled, tag + " shuffled", want, rows0)
@@ -67,7 +68,7 @@ def test_model_random_shapes(models):
     while n + extra < 300_000:
         pairs, ref, qer = esm.random_shapes(per, seed=5000 + extra)
         want, rows0, st = _check(models, oracle.make_params(), pairs, ref, qer, 100,
-                                 lsm.default_order(pairs, ref, qer), "extra sorted")
+                                 pcb.default_order(pairs, ref, qer), "extra sorted")
         tot["sorted"] += st
         extra += len(pairs)
     n += extra
@@ -86,13 +87,14 @@ def test_model_c2(models):
     lib, _ = models
     pairs, ref, qer = bsw.synth_batch(100_000)
     params = oracle.make_params()
-    order = lsm.default_order(pairs, ref, qer)
+    order = pcb.default_order(pairs, ref, qer)
     _, _, (rows, ent, skp) = _check(models, params, pairs, ref, qer, 100, order, "C2")
-    _, rows_off, wst_off = lsm.run(lib, params, pairs, ref, qer, 100, order=order, skip=False)
-    r0, e0, s0 = wst_off.sum(0)
+    _, rows_off, _, wst_off = pwm.run(lib, params, pairs, ref, qer, 100, order=order, skip=False, prune=False, rprune=False)
+    r0, e0, s0 = wst_off[:, :3].sum(0)
     assert s0 == 0 and e0 == ent + skp and r0 >= rows
     share = skp / (ent + skp)
-    print(f"C2 (refresh on rows with (i & {lsm.SKIP_MASK}) == {lsm.SKIP_ROW}): rows per wave {rows / len(wst_off):.1f} "
+    cfg = pwm.defaults(lib)
+    print(f"C2 (refresh on rows with (i & {cfg.skip_mask}) == {cfg.skip_row}): rows per wave {rows / len(wst_off):.1f} "
           f"({r0 / len(wst_off):.1f} without the skip), groups entered per row {ent / rows:.2f} with the skip, "
           f"{e0 / r0:.2f} without; skipped share of entered groups {share:.4f}")
     assert share >= 0.05, f"the skip removes only {share:.4f} of the entered groups"
@@ -103,27 +105,27 @@ def test_model_built_cases(models):
     lib, elib = models
     skipped = {}
     for name, (pairs, ref, qer) in {
-        "boundary_alive": lsm.boundary_alive(512, 11),
-        "pin_dies": lsm.pinned_waves(4, 12, True),
-        "pin_lives": lsm.pinned_waves(4, 12, False),
-        "uneven": lsm.uneven_lifetimes(5, 13),
-        "interior": lsm.interior_zeros(512, 14),
+        "boundary_alive": pcb.boundary_alive(512, 11),
+        "pin_dies": pcb.pinned_waves(4, 12, True),
+        "pin_lives": pcb.pinned_waves(4, 12, False),
+        "uneven": pcb.uneven_lifetimes(5, 13),
+        "interior": pcb.interior_zeros(512, 14),
     }.items():
-        params = oracle.make_params(**(lsm.PIN_SCORING if name.startswith("pin") else {}))
+        params = oracle.make_params(**(pcb.PIN_SCORING if name.startswith("pin") else {}))
         want = pairs.copy()
         oracle.get_scores(params, want, ref, qer, 100, nthreads=8)
         _, rows0, _ = esm.run(elib, params, pairs, ref, qer, 100, 0)
-        got, rows, wst = lsm.run_planned(lib, params, pairs, ref, qer, 100)
+        got, rows, _, wst = pwm.run_planned(lib, params, pairs, ref, qer, 100, prune=False, rprune=False)
         for f in bsw.OUT_FIELDS:
             assert np.array_equal(want[f], got[f]), f"{name}: field {f} differs"
         assert (rows <= rows0).all()
         skipped[name] = int(wst[:, 2].sum())
-        print(f"{name}: {len(pairs)} pairs, skipped groups {skipped[name]} of {int(wst[:, 1:].sum())}")
+        print(f"{name}: {len(pairs)} pairs, skipped groups {skipped[name]} of {int(wst[:, 1:3].sum())}")
         assert skipped[name] > 0, f"{name}: the skip never fired"
     # every wave of the pinned batches holds its one pinning lane, first in the wave
     for dies in (True, False):
-        pairs, ref, qer = lsm.pinned_waves(4, 12, dies)
-        order = lsm.default_order(pairs, ref, qer).reshape(-1, 64)
+        pairs, ref, qer = pcb.pinned_waves(4, 12, dies)
+        order = pcb.default_order(pairs, ref, qer).reshape(-1, 64)
         assert (pairs["h0"][order[:, 0]] == 100).all() and (pairs["h0"][order[:, 1:]] <= 10).all()
     # a pinning lane that lives on holds gz back for about its h0 rows
     assert skipped["pin_lives"] < skipped["pin_dies"]

@@ -3,17 +3,17 @@ GPU: all six output fields bit-exact against the CPU oracle on small batches of 
 prune that dropped a cell the outputs need, a certificate that missed a lane, or a redo list that
 lost or repeated one would show.  The int16 planes (kernel8 = 1) carry the rule in the QMAX 128 and
 160 classes; the byte planes (kernel8 = 2) and the 96 class are compiled without it and run the same
-batches.  The CPU model of the kernel's loop (tests/left_prune_model.py, in the engine's wave
-layout) vouches that each batch prunes, and that the collapse batches redo."""
+batches.  The CPU model of the kernel's loop (tests/pc_wave_model.py with the right prune off, in the
+engine's wave layout) vouches that each batch prunes, and that the collapse batches redo."""
 
 import numpy as np
 import pytest
 
 import bsw
 import hiprt
-import left_prune_model as lpm
-import left_skip_model as lsm
 import oracle
+import pc_batches as pcb
+import pc_wave_model as pwm
 
 pytestmark = pytest.mark.gpu
 
@@ -23,26 +23,26 @@ Z10 = dict(zdrop=10)
 
 def _collapse_b():
     """b. 1,024 pairs with every lane collapsing at base 130 and 1,024 with one lane in eight."""
-    return lpm.concat(lpm.late_collapse(1024, 72), lpm.late_collapse(1024, 73, every=8))
+    return pcb.concat(pcb.late_collapse(1024, 72), pcb.late_collapse(1024, 73, every=8))
 
 
 def _mixed_e():
     """e. Zeros inside rows, a lane that pins gz, uneven lifetimes, the live boundary -- and a
     partial last wave: 37 + 64 k pairs."""
-    parts = [lsm.interior_zeros(512, 66), lsm.pinned_waves(3, 67, True), lsm.uneven_lifetimes(6, 68),
-             lsm.boundary_alive(512, 65)]
-    p, r, q = lpm.concat(*parts)
+    parts = [pcb.interior_zeros(512, 66), pcb.pinned_waves(3, 67, True), pcb.uneven_lifetimes(6, 68),
+             pcb.boundary_alive(512, 65)]
+    p, r, q = pcb.concat(*parts)
     n = (len(p) - 37) // 64 * 64 + 37
     return p[:n], r, q
 
 
 BATCHES = {
-    "a_c2_shaped": (lambda: lpm.c2_shaped(4096, 71), 100, DEFAULT),
+    "a_c2_shaped": (lambda: pcb.c2_shaped(4096, 71), 100, DEFAULT),
     "b_late_collapse": (_collapse_b, 100, Z10),
-    "c_collapse_120_z100": (lambda: lpm.late_collapse(1024, 74, at=120), 100, dict(zdrop=100)),
-    "c_collapse_135_z0": (lambda: lpm.late_collapse(1024, 75, at=135), 100, dict(zdrop=0)),
-    "d_classes_w100": (lambda: lpm.class_edges(512, 76), 100, DEFAULT),
-    "d_classes_w20": (lambda: lpm.class_edges(512, 77), 20, DEFAULT),
+    "c_collapse_120_z100": (lambda: pcb.late_collapse(1024, 74, at=120), 100, dict(zdrop=100)),
+    "c_collapse_135_z0": (lambda: pcb.late_collapse(1024, 75, at=135), 100, dict(zdrop=0)),
+    "d_classes_w100": (lambda: pcb.class_edges(512, 76), 100, DEFAULT),
+    "d_classes_w20": (lambda: pcb.class_edges(512, 77), 20, DEFAULT),
     "e_mixed": (_mixed_e, 100, Z10),
 }
 _cache = {}
@@ -56,8 +56,8 @@ def _batch(name, tmp_path_factory):
         par = oracle.make_params(**sc)
         want = pairs.copy()
         oracle.get_scores(par, want, ref, qer, w, nthreads=8)
-        libs = lpm.build(tmp_path_factory.mktemp("lp_model"))
-        got, _, redo, wst = lpm.run_planned(libs, par, pairs, ref, qer, w)
+        lib = pwm.build(tmp_path_factory.mktemp("pc_model"))
+        got, _, redo, wst = pwm.run_planned(lib, par, pairs, ref, qer, w, rprune=False)
         for f in bsw.OUT_FIELDS:
             assert np.array_equal(want[f], got[f]), f"{name}: the model disagrees with the oracle in {f}"
         _cache[name] = (pairs, ref, qer, w, sc, want, redo, wst)
@@ -107,14 +107,14 @@ def _vouch(name, pairs, ref, qer, redo, wst):
           f"groups per row {wst[:, 1].sum() / wst[:, 0].sum():.2f}")
     assert ev > 0, f"{name}: the model never prunes on this batch"
     if name.startswith("b_"):
-        cls = lsm.qmax_class(pairs)
+        cls = pcb.qmax_class(pairs)
         assert (cls == 4).all() and nredo > 64, f"{name}: {nredo} redo lanes in one class"
         assert (wst[:, 4] > 0).sum() > 2               # spread over several waves of the main launch
     if name.startswith(("a_", "c_")):
         assert nredo == 0, f"{name}: {nredo} redo lanes"
     if name.startswith("d_"):
-        order = lsm.default_order(pairs, ref, qer)
-        wcls = lsm.qmax_class(pairs)[order][::64]
+        order = pcb.default_order(pairs, ref, qer)
+        wcls = pcb.qmax_class(pairs)[order][::64]
         for c in (3, 4):                       # the classes that carry the rule
             assert wst[wcls == c, 3].sum() > 0, f"{name}: class {c} never pruned"
     if name.startswith("e_"):

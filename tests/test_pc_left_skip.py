@@ -2,7 +2,7 @@
 output fields bit-exact against the CPU oracle, for the int16 planes (kernel8 = 1) and the byte
 planes (kernel8 = 2), on small batches of the shapes where a skip that dropped live cells -- or a
 dead lane that held gz back or corrupted it -- would show.  The CPU model of the kernel's loop
-(tests/left_skip_model.py, run in the engine's wave layout) vouches that each batch exercises the
+(tests/pc_wave_model.py with both prunes off, run in the engine's wave layout) vouches that each batch exercises the
 skip: it reports the groups it removed from the entered set."""
 
 import numpy as np
@@ -11,8 +11,9 @@ import pytest
 import bsw
 import bswgen
 import hiprt
-import left_skip_model as lsm
 import oracle
+import pc_batches as pcb
+import pc_wave_model as pwm
 
 pytestmark = pytest.mark.gpu
 
@@ -46,11 +47,11 @@ BATCHES = {
     "b_quick_w5": (lambda: _quick_prefix(62), 5, DEFAULT),
     "b_quick_w10": (lambda: _quick_prefix(63), 10, DEFAULT),
     "b_quick_w20": (lambda: _quick_prefix(64), 20, DEFAULT),
-    "c_boundary_alive": (lambda: lsm.boundary_alive(2048, 65), 100, DEFAULT),
-    "d_interior_zeros": (lambda: lsm.interior_zeros(2048, 66), 100, DEFAULT),
-    "e_pin_dies": (lambda: lsm.pinned_waves(5, 67, True), 100, lsm.PIN_SCORING),
-    "e_pin_lives": (lambda: lsm.pinned_waves(5, 67, False), 100, lsm.PIN_SCORING),
-    "f_uneven_lifetimes": (lambda: lsm.uneven_lifetimes(30, 68), 100, DEFAULT),
+    "c_boundary_alive": (lambda: pcb.boundary_alive(2048, 65), 100, DEFAULT),
+    "d_interior_zeros": (lambda: pcb.interior_zeros(2048, 66), 100, DEFAULT),
+    "e_pin_dies": (lambda: pcb.pinned_waves(5, 67, True), 100, pcb.PIN_SCORING),
+    "e_pin_lives": (lambda: pcb.pinned_waves(5, 67, False), 100, pcb.PIN_SCORING),
+    "f_uneven_lifetimes": (lambda: pcb.uneven_lifetimes(30, 68), 100, DEFAULT),
 }
 _cache = {}
 
@@ -63,8 +64,8 @@ def _batch(name, tmp_path_factory):
         par = oracle.make_params(**sc)
         want = pairs.copy()
         oracle.get_scores(par, want, ref, qer, w, nthreads=8)
-        lib = lsm.build(tmp_path_factory.mktemp("ls_model"))
-        got, _, wst = lsm.run_planned(lib, par, pairs, ref, qer, w)
+        lib = pwm.build(tmp_path_factory.mktemp("pc_model"))
+        got, _, _, wst = pwm.run_planned(lib, par, pairs, ref, qer, w, prune=False, rprune=False)
         for f in bsw.OUT_FIELDS:
             assert np.array_equal(want[f], got[f]), f"{name}: the model disagrees with the oracle in {f}"
         _cache[name] = (pairs, ref, qer, w, sc, want, wst)
@@ -107,13 +108,13 @@ def _run(eng, pairs, ref, qer, w, want, tag):
 @pytest.mark.parametrize("name", list(BATCHES))
 def test_left_skip_batch(engine, tmp_path_factory, name, kernel8):
     pairs, ref, qer, w, sc, want, wst = _batch(name, tmp_path_factory)
-    rows, ent, skp = (int(x) for x in wst.sum(0))
+    rows, ent, skp = (int(x) for x in wst[:, :3].sum(0))
     print(f"{name}: {len(pairs)} pairs in {len(wst)} waves, model skips {skp} of {ent + skp} entered groups "
           f"({(ent + skp) / rows:.2f} -> {ent / rows:.2f} per row)")
     assert skp > 0, f"{name}: the model never skips a group on this batch"
     if name.startswith("e_"):
         # the waves are the ones built: the pinning lane first, its 63 neighbours after it
-        order = lsm.default_order(pairs, ref, qer).reshape(-1, 64)
+        order = pcb.default_order(pairs, ref, qer).reshape(-1, 64)
         assert (pairs["h0"][order[:, 0]] == 100).all() and (pairs["h0"][order[:, 1:]] <= 10).all()
         other = _batch("e_pin_lives" if name == "e_pin_dies" else "e_pin_dies", tmp_path_factory)[6]
         lives, dies = (wst, other) if name == "e_pin_lives" else (other, wst)

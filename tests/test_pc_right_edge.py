@@ -13,8 +13,8 @@ import pytest
 import bsw
 import bswgen
 import hiprt
-import left_skip_model as lsm
 import oracle
+import pc_batches as pcb
 
 pytestmark = pytest.mark.gpu
 
@@ -63,7 +63,7 @@ def _mixed_qlens():
 def _close_ends():
     """c. Lanes of one wave whose band ends differ by a few columns on the same rows: one qlen and
     one tlen / 32 bucket per wave, every query an exact copy of the window's first 40 bases (the
-    default key then ties in all but h0, as in left_skip_model.pinned_waves) and 2-10 % substitutions
+    default key then ties in all but h0, as in pc_batches.pinned_waves) and 2-10 % substitutions
     after them; h0 1-100 sets how far right of the diagonal a row stays positive."""
     rng = np.random.default_rng(73)
     items = []
@@ -121,7 +121,7 @@ BATCHES = {
     "b_mixed2": (lambda: _mixed_qlens()[1], 100),
     "c_close_ends": (_close_ends, 100),
     "c_close_ends_w20": (_close_ends, 20),
-    "d_stale_slots": (lambda: lsm.interior_zeros(2048, 74), 100),
+    "d_stale_slots": (lambda: pcb.interior_zeros(2048, 74), 100),
     "e_degenerate": (_degenerate, 100),
 }
 _cache = {}
@@ -174,14 +174,14 @@ def _run(eng, pairs, ref, qer, w, want, tag):
 def test_right_edge_batch(engine, name, kernel8):
     pairs, ref, qer, w, want = _batch(name)
     if name == "a_tail":                 # one qlen per wave, in the engine's own lane order
-        order = lsm.default_order(pairs, ref, qer)
-        cls = lsm.qmax_class(pairs)[order]
+        order = pcb.default_order(pairs, ref, qer)
+        cls = pcb.qmax_class(pairs)[order]
         for c in range(5):
             q = pairs["len2"][order][cls == c].reshape(-1, 64)
             assert (q == q[:, :1]).all()
     if name.startswith("b_"):            # every class has a wave of two qlens
-        order = lsm.default_order(pairs, ref, qer)
-        cls = lsm.qmax_class(pairs)[order]
+        order = pcb.default_order(pairs, ref, qer)
+        cls = pcb.qmax_class(pairs)[order]
         for c in range(5):
             q = pairs["len2"][order][cls == c]
             assert any(len(set(q[k:k + 64])) > 1 for k in range(0, len(q), 64))

@@ -3,7 +3,7 @@ fields bit-exact against the CPU oracle on small batches of the shapes where a c
 the outputs need, a certificate that missed a lane, or a redo list that lost or repeated one would
 show.  The int16 planes (kernel8 = 1) carry the rule in the QMAX 128 and 160 classes; the byte planes
 (kernel8 = 2) are compiled without it and run the same batches.  The CPU model of the kernel's loop
-(tests/right_prune_model.py, in the engine's wave layout) is checked against the oracle first and
+(tests/pc_wave_model.py, in the engine's wave layout) is checked against the oracle first and
 vouches that each batch prunes, retreats or redoes as stated."""
 
 import numpy as np
@@ -11,10 +11,9 @@ import pytest
 
 import bsw
 import hiprt
-import left_prune_model as lpm
-import left_skip_model as lsm
 import oracle
-import right_prune_model as rpm
+import pc_batches as pcb
+import pc_wave_model as pwm
 from test_right_prune_model import BUILT, vouch
 
 pytestmark = pytest.mark.gpu
@@ -23,9 +22,9 @@ pytestmark = pytest.mark.gpu
 def _mixed():
     """Zeros inside rows, a lane that pins gz, uneven lifetimes, the live boundary -- and a partial
     last wave: 37 + 64 k pairs (the left prune's mixed batch)."""
-    parts = [lsm.interior_zeros(512, 66), lsm.pinned_waves(3, 67, True), lsm.uneven_lifetimes(6, 68),
-             lsm.boundary_alive(512, 65)]
-    p, r, q = lpm.concat(*parts)
+    parts = [pcb.interior_zeros(512, 66), pcb.pinned_waves(3, 67, True), pcb.uneven_lifetimes(6, 68),
+             pcb.boundary_alive(512, 65)]
+    p, r, q = pcb.concat(*parts)
     n = (len(p) - 37) // 64 * 64 + 37
     return p[:n], r, q
 
@@ -44,8 +43,8 @@ def _batch(name, tmp_path_factory):
         par = oracle.make_params(**sc)
         want = pairs.copy()
         oracle.get_scores(par, want, ref, qer, w, nthreads=8)
-        libs = rpm.build(tmp_path_factory.mktemp("rp_model"))
-        got, _, redo, wst = rpm.run_planned(libs, par, pairs, ref, qer, w)
+        lib = pwm.build(tmp_path_factory.mktemp("pc_model"))
+        got, _, redo, wst = pwm.run_planned(lib, par, pairs, ref, qer, w)
         for f in bsw.OUT_FIELDS:
             assert np.array_equal(want[f], got[f]), f"{name}: the model disagrees with the oracle in {f}"
         _cache[name] = (pairs, ref, qer, w, sc, what, want, redo, wst)

@@ -1,5 +1,5 @@
 """The packed-column kernel's right prune as a CPU model of the KERNEL's loop
-(tests/right_prune_model.py): the left prune's model with the wave-uniform right cap, the zeroing
+(tests/pc_wave_model.py): the left prune's model with the wave-uniform right cap, the zeroing
 walk, the per-row crossing certificate, the soft retreat, the final certificate and the redo lanes
 recomputed without either rule.  It must give the oracle's six outputs on every pair, run no more
 rows per lane than the literal loop, remove a real share of the groups the left prune alone enters on
@@ -12,34 +12,33 @@ import pytest
 
 import bsw
 import early_stop_model as esm
-import left_prune_model as lpm
-import left_skip_model as lsm
 import oracle
-import right_prune_model as rpm
+import pc_batches as pcb
+import pc_wave_model as pwm
 
 
 @pytest.fixture(scope="module")
 def models(tmp_path_factory):
-    d = tmp_path_factory.mktemp("rp_model")
-    return rpm.build(d), esm.build(d)
+    d = tmp_path_factory.mktemp("pc_model")
+    return pwm.build(d), esm.build(d)
 
 
 def _check(models, params, pairs, ref, qer, w, order, tag, want=None, rows0=None):
     """The model with both prunes on the lanes in `order`: 0 differing fields against the oracle,
     rows per lane no more than the literal loop's.  Returns (want, rows0, per-wave sums by name)."""
-    libs, elib = models
+    lib, elib = models
     if want is None:
         want = pairs.copy()
         oracle.get_scores(params, want, ref, qer, w, nthreads=8)
         _, rows0, _ = esm.run(elib, params, pairs, ref, qer, w, 0)
-    got, rows, _, wst = rpm.run(libs, params, pairs, ref, qer, w, order=order)
+    got, rows, _, wst = pwm.run(lib, params, pairs, ref, qer, w, order=order)
     for f in bsw.OUT_FIELDS:
         bad = np.flatnonzero(want[f] != got[f])
         assert len(bad) == 0, (f"{tag}: field {f} differs in {len(bad)} pairs; first {bad[0]} "
                                f"tlen={pairs['len1'][bad[0]]} qlen={pairs['len2'][bad[0]]} h0={pairs['h0'][bad[0]]} "
                                f"want {want[f][bad[0]]} got {got[f][bad[0]]}")
     assert (rows <= rows0).all(), f"{tag}: a lane ran more rows than the literal loop"
-    return want, rows0, rpm.totals(wst)
+    return want, rows0, pwm.totals(wst)
 
 
 def _add(tot, st):
@@ -61,7 +60,7 @@ def test_model_random_shapes(models):
             pairs, ref, qer = esm.random_shapes(per, seed=2000 + k)
         params = oracle.make_params(zdrop=zdrop, end_bonus=eb)
         tag = f"w={w} zdrop={zdrop} end_bonus={eb}"
-        want, rows0, st = _check(models, params, pairs, ref, qer, w, lsm.default_order(pairs, ref, qer), tag + " sorted")
+        want, rows0, st = _check(models, params, pairs, ref, qer, w, pcb.default_order(pairs, ref, qer), tag + " sorted")
         _add(tot["sorted"], st)
         shuffled = np.random.default_rng(k).permutation(len(pairs)).astype(np.int32)
         _, _, st = _check(models, params, pairs, ref, qer, w, shuffled, tag + " shuffled", want, rows0)
@@ -71,7 +70,7 @@ def test_model_random_shapes(models):
     while n + extra < 300_000:
         pairs, ref, qer = esm.random_shapes(per, seed=5000 + extra)
         want, rows0, st = _check(models, oracle.make_params(), pairs, ref, qer, 100,
-                                 lsm.default_order(pairs, ref, qer), "extra sorted")
+                                 pcb.default_order(pairs, ref, qer), "extra sorted")
         _add(tot["sorted"], st)
         shuffled = np.random.default_rng(7000 + extra).permutation(len(pairs)).astype(np.int32)
         _, _, st = _check(models, oracle.make_params(), pairs, ref, qer, 100, shuffled, "extra shuffled", want, rows0)
@@ -90,12 +89,12 @@ def test_model_c2(models):
     """100,000 pairs of the flagship batch (150 bp query, 300 bp window, w = 100) in the waves of the
     default sort key: exact, at least 7 % of the groups the left prune alone enters removed, at most
     0.1 % of the lanes sent to the redo pass (a cap, not a target)."""
-    libs, _ = models
+    lib, _ = models
     pairs, ref, qer = bsw.synth_batch(100_000)
     params = oracle.make_params()
-    order = lsm.default_order(pairs, ref, qer)
+    order = pcb.default_order(pairs, ref, qer)
     _, _, t = _check(models, params, pairs, ref, qer, 100, order, "C2")
-    _, _, _, wst0 = lpm.run(libs[1:], params, pairs, ref, qer, 100, order=order)
+    _, _, _, wst0 = pwm.run(lib, params, pairs, ref, qer, 100, order=order, rprune=False)
     r0, e0 = int(wst0[:, 0].sum()), int(wst0[:, 1].sum())
     share = 1.0 - t["entered"] / e0
     print(f"C2: rows per wave {t['rows'] / len(wst0):.1f} ({r0 / len(wst0):.1f} with the left prune alone), groups "
@@ -110,24 +109,24 @@ Z100 = dict(zdrop=100)
 DEFAULT = dict(zdrop=100, end_bonus=5)
 # name: (builder, w, scoring, the event the batch is built for)
 BUILT = {
-    "c2_shaped": (lambda: lpm.c2_shaped(4096, 71), 100, DEFAULT, "prunes"),
-    "collapse_120_z100": (lambda: lpm.late_collapse(1024, 74, at=120), 100, Z100, "final"),
-    "classes_w100": (lambda: lpm.class_edges(512, 76), 100, DEFAULT, "classes"),
-    "a_clipped_tails_z100": (lambda: rpm.clipped_tails(1536, 81), 100, Z100, "final"),
-    "a_clipped_tails_z0": (lambda: rpm.clipped_tails(1536, 82), 100, dict(zdrop=0), "final"),
-    "b_second_diagonal": (lambda: rpm.second_diagonal(1024, 83), 100, DEFAULT, "refuse_or_redo"),
-    "c_late_insertion": (lambda: rpm.late_insertion(1024, 84), 100, DEFAULT, "retreat"),
-    "d_low_h0": (lambda: rpm.low_h0(2048, 85), 100, DEFAULT, "low_h0"),
-    "e_w20": (lambda: lpm.c2_shaped(2048, 86), 20, DEFAULT, "band"),
-    "f_class_tops": (lambda: rpm.class_tops(3, 87), 100, DEFAULT, "classes"),
-    "g_odd_lane": (lambda: rpm.odd_lane(16, 88), 100, dict(zdrop=10), "odd"),
+    "c2_shaped": (lambda: pcb.c2_shaped(4096, 71), 100, DEFAULT, "prunes"),
+    "collapse_120_z100": (lambda: pcb.late_collapse(1024, 74, at=120), 100, Z100, "final"),
+    "classes_w100": (lambda: pcb.class_edges(512, 76), 100, DEFAULT, "classes"),
+    "a_clipped_tails_z100": (lambda: pcb.clipped_tails(1536, 81), 100, Z100, "final"),
+    "a_clipped_tails_z0": (lambda: pcb.clipped_tails(1536, 82), 100, dict(zdrop=0), "final"),
+    "b_second_diagonal": (lambda: pcb.second_diagonal(1024, 83), 100, DEFAULT, "refuse_or_redo"),
+    "c_late_insertion": (lambda: pcb.late_insertion(1024, 84), 100, DEFAULT, "retreat"),
+    "d_low_h0": (lambda: pcb.low_h0(2048, 85), 100, DEFAULT, "low_h0"),
+    "e_w20": (lambda: pcb.c2_shaped(2048, 86), 20, DEFAULT, "band"),
+    "f_class_tops": (lambda: pcb.class_tops(3, 87), 100, DEFAULT, "classes"),
+    "g_odd_lane": (lambda: pcb.odd_lane(16, 88), 100, dict(zdrop=10), "odd"),
 }
 
 
 def vouch(name, what, pairs, ref, qer, redo, wst):
     """What the model must show for a built batch to test what it is built for (the GPU test calls it
     too).  `redo` is the per-pair redo mark, `wst` the per-wave figures."""
-    t = rpm.totals(wst)
+    t = pwm.totals(wst)
     n = len(pairs)
     print(f"{name}: {n} pairs in {len(wst)} waves, model: right-prune events {t['right_events']}, group tests refused "
           f"{t['refused']}, clipped lanes {t['clipped']}, retreats {t['retreats']}, redo lanes {t['redo']} (crossing "
@@ -150,10 +149,10 @@ def vouch(name, what, pairs, ref, qer, redo, wst):
     if what == "band":                # (e) the band's edge stays left of the cap, throughout
         assert t["clipped"] == 0 and t["redo"] == 0, f"{name}: {t['clipped']} lanes clipped, {t['redo']} redone"
     if what == "classes":             # (f) both classes that carry the rule prune
-        wcls = lsm.qmax_class(pairs)[lsm.default_order(pairs, ref, qer)][::64]
+        wcls = pcb.qmax_class(pairs)[pcb.default_order(pairs, ref, qer)][::64]
         assert len(wcls) == len(wst)
         for c in (3, 4):
-            assert wst[wcls == c, rpm.WST.index("right_events")].sum() > 0, f"{name}: class {c} never pruned"
+            assert wst[wcls == c, pwm.WST.index("right_events")].sum() > 0, f"{name}: class {c} never pruned"
         assert t["clipped"] > 0
     if what == "odd":                 # (g) P is raised in staying lanes only: exactly the odd lanes are redone, the
         odd = np.arange(n) % 64       # lanes that stay owe nothing for them
@@ -164,14 +163,14 @@ def vouch(name, what, pairs, ref, qer, redo, wst):
 
 def test_model_built_cases(models):
     """The batches the GPU test runs, in the engine's wave layout: exact, each shows its event."""
-    libs, elib = models
+    lib, elib = models
     for name, (make, w, sc, what) in BUILT.items():
         pairs, ref, qer = make()
         params = oracle.make_params(**sc)
         want = pairs.copy()
         oracle.get_scores(params, want, ref, qer, w, nthreads=8)
         _, rows0, _ = esm.run(elib, params, pairs, ref, qer, w, 0)
-        got, rows, redo, wst = rpm.run_planned(libs, params, pairs, ref, qer, w)
+        got, rows, redo, wst = pwm.run_planned(lib, params, pairs, ref, qer, w)
         for f in bsw.OUT_FIELDS:
             assert np.array_equal(want[f], got[f]), f"{name}: field {f} differs"
         assert (rows <= rows0).all()
