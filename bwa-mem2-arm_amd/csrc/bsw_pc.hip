@@ -65,6 +65,36 @@ __device__ __forceinline__ uint64_t gbits(int lo, int n)
     return m;
 }
 
+// the same for a width the caller has already bounded (0 <= n <= 63): no clamp, so a uniform n stays in SGPRs
+__device__ __forceinline__ uint64_t gbits_nc(int lo, int n)
+{
+    uint64_t m;
+    asm("s_bfm_b64 %0, %1, %2" : "=s"(m)
+        : "s"(__builtin_amdgcn_readfirstlane(n)), "s"(__builtin_amdgcn_readfirstlane(lo)));
+    return m;
+}
+
+// Lane conditions of the row loop as wave masks: a compare writes its SGPR pair, and / or / not of
+// conditions are scalar instructions, a vote is a test of the pair, and a select takes the pair as it is.  (A bool
+// that is not itself a compare costs v_cndmask 0, 1 + v_cmp_ne at every __ballot, and the short-circuit forms
+// of && and || come back as exec-masked blocks.)  The row loop runs with every lane enabled.
+typedef uint64_t lmask;
+__device__ __forceinline__ lmask m_eq(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 32); }
+__device__ __forceinline__ lmask m_ne(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 33); }
+__device__ __forceinline__ lmask m_gt(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 38); }
+__device__ __forceinline__ lmask m_ge(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 39); }
+__device__ __forceinline__ lmask m_lt(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 40); }
+__device__ __forceinline__ lmask m_le(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 41); }
+// this lane's bit of a mask, for a select or a helper that takes a lane's bool (no instruction)
+__device__ __forceinline__ bool m_on(lmask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// a select on a lane mask as one v_cndmask that the compiler cannot turn back into an exec-masked block
+__device__ __forceinline__ int pc_sel(lmask mask, int a, int b)
+{
+    int r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(mask));
+    return r;
+}
+
 // group G of a row, where the class has it: its query word and plane registers to the group statement
 template <int QMAX, bool BY, int G>
 __device__ __forceinline__ void pc_group_if(PcPlane<QMAX, BY> &hh, PcPlane<QMAX, BY> &ee,
@@ -184,6 +214,12 @@ __device__ __forceinline__ uint32_t pc_rp_raise(uint32_t hi, int t)
 {
     return max(hi, ((uint32_t)(max(t, 0) + 1) << (kPcPShift - 32)) | (hi & kPcLowHi));
 }
+// the same on a clipped lane's row, with the clipped mark, without the max: a lane's best never falls, so the
+// threshold of the row at hand is at least every threshold the field has held
+__device__ __forceinline__ uint32_t pc_rp_put(uint32_t hi, int t)
+{
+    return (hi & kPcLowHi) | (((uint32_t)max(t, 0) << (kPcPShift - 32)) + ((1u << (kPcPShift - 32)) | kPcClipHi));
+}
 
 // WPB waves per workgroup: with 1, a wave's slot (and its LDS) is reused as soon as that wave
 // ends, instead of when the slowest of its block's waves ends.
@@ -300,8 +336,8 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
         wl = min(wl, max((ni + kp.e_ins) / kp.e_ins, 1));
         wl = min(wl, max((nd + kp.e_del) / kp.e_del, 1));
     }
-    int best = h0, best_i = -1, best_j = -1, max_ie = -1, gsc = -1, moff = 0, endc = qlen;
-    bool alive = valid && tlen > 0;
+    int best = h0, best_i = -1, best_d = 0, max_ie = -1, gsc = -1, moff = 0, endc = qlen;
+    const bool alive0 = valid && tlen > 0;
     // an invalid lane stores nothing: kept as a null pair pointer, not as a lane mask that would
     // hold an SGPR pair across the row loop (the loop has none to spare: it was spilled to a VGPR)
     if (!valid) sp = nullptr;
@@ -319,10 +355,10 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
             __builtin_amdgcn_global_load_lds((gptr_t)(twp + min(16 * ch + k, tlast)),
                                              (lptr_t)(dst + 64 * k), 4, 0, 0);
     };
-    if (alive) { issue_chunk(0); issue_chunk(1); }
+    if (alive0) { issue_chunk(0); issue_chunk(1); }
     uint32_t tcur = 0;
-    const int wl_max = wave_max(alive ? wl : -1);
-    const int wl_min = wave_min(alive ? wl : INT_MAX);
+    const int wl_max = __builtin_amdgcn_readfirstlane(wave_max(alive0 ? wl : -1));
+    const int wl_min = __builtin_amdgcn_readfirstlane(wave_min(alive0 ? wl : INT_MAX));
     const uint32_t oe2 = (uint32_t)(kp.o_del + kp.e_del) * 0x10001u;
     const uint32_t ed2 = (uint32_t)kp.e_del * 0x10001u;
     uint32_t ctr[4] = {0, 0, 0, 0};                       // BSW_PC_STATS group-path counters
@@ -348,10 +384,12 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
     uint32_t nrcap = 0, nrret = 0, rcause = 0;   // groups the cap removed, retreats (uniform); this lane's redo cause
     (void)nrcap; (void)nrret; (void)rcause;
 #endif
+    const int zdrop = kp.zdrop > 0 ? kp.zdrop : INT_MAX;   // z-drop off: a distance no row reaches
+    lmask alive = __ballot(alive0);         // the lanes still running, a wave mask (lmask, above) all through the loop
     for (int i = 0;; ++i) {
-        const bool act = alive && i < tlen;
+        const lmask act = alive & m_lt(i, tlen);
         alive = act;
-        if (__ballot(act) == 0) break;
+        if (act == 0) break;
         // the row's target base and score profile first: their LDS reads then overlap the band
         // bookkeeping below instead of stalling the first group (lgkmcnt wait)
         // every lane reads (a dead lane's slots are harmless): no exec-masked block on the row's path
@@ -371,7 +409,7 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
             tcur = __builtin_amdgcn_alignbyte(d.y, d.x, tsh);
             if ((i & 63) == 0) {
                 __builtin_amdgcn_sched_barrier(0);
-                if (i > 0 && act) issue_chunk((i >> 6) + 1);   // refill the buffer just drained
+                if (i > 0 && m_on(act)) issue_chunk((i >> 6) + 1);   // refill the buffer just drained
             }
         }
         // per-row score profile of target base t (8 bytes: mat[t][q], q = 0..7)
@@ -382,7 +420,7 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
         int endcl = min(min(endc, i + wl + 1), qlen);
 #ifdef BSW_PC_STATS
         if constexpr (RP) {                // the groups between the cap and the static band end
-            const int eu = wave_max(act ? min(i + wl + 1, qlen) : -1), ec = wave_max(act ? min(endcl, cap4) : -1);
+            const int eu = wave_max(m_on(act) ? min(i + wl + 1, qlen) : -1), ec = wave_max(m_on(act) ? min(endcl, cap4) : -1);
             if (cap4 < QMAX && ec >= 0) nrcap += (uint32_t)max((min(eu, QMAX - 1) >> 2) - (min(ec, QMAX - 1) >> 2), 0);
         }
 #endif
@@ -391,7 +429,7 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
         endc = end;
         int emax, emin;
         PcRow r;
-        wave_maxmin_bc(act ? end : -1, act ? end : INT_MAX, emax, emin);
+        wave_maxmin_bc(m_on(act) ? end : -1, m_on(act) ? end : INT_MAX, emax, emin);
         {
             const int ulo = __builtin_amdgcn_readfirstlane(max(0, i - wl_max));  // min beg
             const int uhi = __builtin_amdgcn_readfirstlane(emax);                // max end
@@ -401,11 +439,16 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
             const int gsp = max((min(uhi, QMAX - 1) >> 2) - glo, -1);      // uhi >= 0: a live lane
             // FAST needs 4G > every beg (entering chain valid) -- or one common beg == 4G with
             // nothing computed before it -- and 4G + 4 <= every end
-            const int gfa = (ulo == flo && (flo & 3) == 0) ? (flo >> 2) : (flo >> 2) + 1;
+            // (gfa = flo >> 2 for one common beg on a group boundary, else (flo >> 2) + 1, in three scalar
+            // instructions: flo rounded up to a group, one more when the begs differ.  gfn <= NG: fhi is a live
+            // lane's end, so its set takes no clamp)
+            int gfa;
+            asm("s_cmp_lg_u32 %1, %2\n\ts_addc_u32 %0, %2, 3" : "=s"(gfa) : "s"(ulo), "s"(flo) : "scc");
+            gfa >>= 2;
             const int gfn = max((fhi >> 2) - gfa, 0);
+            r.fast = gbits_nc(gfa, gfn);
             const int gln = (flo >> 2) - glo;
             r.enter = gbits(glo, gsp + 1);
-            r.fast = gbits(gfa, gfn);
             r.left = gbits(glo, gln + 1);
             if constexpr (pc_left_skip<QMAX>()) {   // groups below gz leave the entered set; the FAST
                 const uint64_t keep = ~0ull << pc_gz_of<PRUNE>(gz);   // test comes first in a group, so its set too
@@ -433,59 +476,64 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
             h1 = (int)((uint32_t)h1 >> 16);               // H(i, end-1)
             const uint32_t k32 = max(key & 0xffffu, key >> 16);
             const int m = (int)(k32 >> 8), mj = (int)(k32 & 0xffu);
+            // (each compare once: a mask built by a builtin is not merged with its twin)
+            const lmask atend = m_eq(end, qlen), h1z = m_eq(h1, 0);   // end <= qlen and h1 >= 0 always
             {                                     // A.4: j == qlen; h1 = H(i, qlen - 1)
-                const bool atq = act && end == qlen;
-                max_ie = (atq && !(gsc > h1)) ? i : max_ie;
-                gsc = atq ? max(gsc, h1) : gsc;
+                const lmask atq = act & atend;
+                max_ie = m_on(atq & ~m_gt(gsc, h1)) ? i : max_ie;
+                gsc = m_on(atq) ? max(gsc, h1) : gsc;
             }
-            // A.4 row end as selects, no branches on the row's path: m <= 0 ends the lane; a new
-            // best moves (best, best_i, best_j, max_off); otherwise z-drop against the old best
+            // A.4 row end, straight-line: m <= 0 ends the lane; a new best moves (best, best_i,
+            // best_j, max_off); otherwise z-drop against the old best
             {
-                const int di = i - best_i, dj = mj - best_j;
-                // |di - dj| and e are small and non-negative: 24-bit multiplies (full rate)
-                const int dz = (di > dj) ? best - m - (int)__umul24((unsigned)(di - dj), (unsigned)kp.e_del)
-                                         : best - m - (int)__umul24((unsigned)(dj - di), (unsigned)kp.e_ins);
-                const bool better = act && m > best;       // best >= h0 >= 0: never with m <= 0
-                const bool zdropped = kp.zdrop > 0 && dz > kp.zdrop;
-                alive = act && m > 0 && (better || !zdropped);
-                moff = better ? max(moff, abs(mj - i)) : moff;
-                best_i = better ? i : best_i;
-                best_j = better ? mj : best_j;
-                best = better ? m : best;
+                // the lane carries best_d = best_i - best_j in place of best_j: d = di - dj = x - best_d with x =
+                // i - mj, which max_off shares; one of the two products is 0 (|d| and e are small and non-negative:
+                // 24-bit multiplies, full rate).  dz is made opaque, so it is computed on every row and not inside
+                // an exec-masked block for the lanes with m > 0
+                const int x = i - mj;
+                int dz = best - m - (int)__umul24((unsigned)max(x - best_d, 0), (unsigned)kp.e_del)
+                                  - (int)__umul24((unsigned)max(best_d - x, 0), (unsigned)kp.e_ins);
+                asm volatile("" : "+v"(dz));
+                const lmask pos = m_gt(m, 0);
+                const lmask better = act & m_gt(m, best);        // best >= h0 >= 0: never with m <= 0
+                alive = act & pos & (better | m_le(dz, zdrop));
+                const int zb = best - m;                         // against the old best, where the row has no new one
+                moff = pc_sel(better, max(moff, abs(x)), moff);
+                best_i = pc_sel(better, i, best_i);
+                best_d = pc_sel(better, x, best_d);
+                best = pc_sel(better, m, best);
                 if constexpr (PRUNE) {
-                    // the certificate of a pruned wave (§3 item 12), before the early stop: zeroed
-                    // cells only lower values, all below gscore, so a lane whose row has a new best
-                    // or is far from z-drop whatever mj is (dz <= best - m) is in its true state;
-                    // one whose row maximum is 0 retires with its outputs final; the others -- and a
-                    // lane whose band end would leave qlen (h1 == 0) -- are computed again.  The
-                    // mark travels in the low bit of sp (SeqPair is 4-byte aligned).
-                    // (a wave under the right cap, item 13, takes the z-drop half of it on its own mark)
+                    // a marked wave (left-pruned, item 12; under the right cap, item 13): both certificates in one
+                    // block behind one uniform test.  Item 12, before the early stop: zeroed cells only lower
+                    // values, all below gscore, so a lane whose row has a new best or is far from z-drop whatever
+                    // mj is (dz <= best - m) is in its true state; one whose row maximum is 0 retires with its
+                    // outputs final; the others -- and, in a left-pruned wave, a lane whose band end would leave
+                    // qlen (h1 == 0) -- are computed again.  Item 13, the crossing certificate: a lane whose band
+                    // end has sat at the cap lets H(i, end-1) = h1 leave the computed columns, diagonally or along
+                    // the row, and h1's potential must stay below T = best - MARGIN.  Without rmark the cap is QMAX
+                    // and no lane carries the clipped mark, so cl is empty and item 13's half needs no test of its
+                    // own.  The redo mark travels in the low bit of sp (SeqPair is 4-byte aligned), one bit for both.
                     if ((gz & kPcPruned) || (RP && rmark)) {     // uniform: the wave's marks
-                        const bool rd = ((gz & kPcPruned) != 0 || (RP && rmark)) &&
-                                        ((act && !better && m > 0 && kp.zdrop > 0 && best - m > kp.zdrop) ||
-                                         ((gz & kPcPruned) != 0 && alive && h1 == 0));
-                        alive = alive && !rd;
-                        sp = (SeqPair *)((uintptr_t)sp | (uintptr_t)rd);
+                        lmask rd = (act ^ better) & pos & m_gt(zb, zdrop);
+                        if (gz & kPcPruned) rd |= alive & h1z;
 #ifdef BSW_PC_STATS
-                        rcause = (rd && !rcause) ? 2u : rcause;
+                        rcause = (m_on(rd) && !rcause) ? 2u : rcause;
 #endif
-                    }
-                }
-                if constexpr (RP) {
-                    // the crossing certificate of a wave under the right cap (§3 item 13), behind one uniform
-                    // test: a lane whose band end has sat at the cap lets H(i, end-1) = h1 leave the computed
-                    // columns, diagonally or along the row, and h1's potential must stay below T = best - MARGIN
-                    if (rmark) {
-                        const int t = best - BSW_PC_RP_MARGIN, phi = h1 + (qlen - end);
-                        uint32_t hi = pc_sp_hi(sp);
-                        const bool cl = act && end < qlen && (end == cap4 || (hi & kPcClipHi) != 0);
-                        const bool rdc = cl && h1 > 0 && phi >= t;
-                        hi = cl ? pc_rp_raise(hi | kPcClipHi, t) : hi;    // (a redo lane's P is never read)
-                        sp = pc_sp_set(sp, hi, rdc);
-                        alive = alive && !rdc;
+                        if constexpr (RP) {
+                            const int t = best - BSW_PC_RP_MARGIN, phi = h1 + (qlen - end);
+                            const uint32_t hi = pc_sp_hi(sp);
+                            const lmask cl = act & ~atend & (m_eq(end, cap4) | m_ne((int)(hi & kPcClipHi), 0));
+                            const lmask rdc = cl & ~h1z & m_ge(phi, t);
 #ifdef BSW_PC_STATS
-                        rcause = (rdc && !rcause) ? 1u : rcause;
+                            rcause = (m_on(rdc) && !rcause) ? 1u : rcause;
 #endif
+                            rd |= rdc;
+                            // (a redo lane's P is never read)
+                            sp = pc_sp_set(sp, (uint32_t)pc_sel(cl, (int)pc_rp_put(hi, t), (int)hi), m_on(rd));
+                        } else {
+                            sp = (SeqPair *)((uintptr_t)sp | (uintptr_t)m_on(rd));
+                        }
+                        alive &= ~rd;
                     }
                 }
             }
@@ -502,30 +550,32 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
                              "v_sub_u32_e32 %2, %3, %7"
                              : "=&v"(gq), "=&v"(gt), "=&v"(gm)
                              : "v"(qlen), "v"(beg), "s"(i), "v"(tlen), "v"(mj));
-                const bool edge = end == qlen && gq < qlen;    // beg > 0, from the opaque difference: a
+                const lmask edge = atend & m_lt(gq, qlen);         // beg > 0, from the opaque difference: a
                                                                // test of beg is made at the row head and
                                                                // its mask kept across the groups
                 const int ubs = m - 1 + min(gq, gt);
-                const bool stop = edge && ubs <= best && ubs < gsc;
+                const lmask stop = edge & m_le(ubs, best) & m_lt(ubs, gsc);
 #ifdef BSW_PC_STATS
-                nstop_s += alive && stop;
+                nstop_s += m_on(alive & stop);
 #endif
-                alive = alive && !stop;
+                alive &= ~stop;
 #if BSW_PC_EARLY_SCAN
                 // the per-cell bound, on rows of one phase (wave-uniform: every fourth) and only for lanes
                 // whose arg-max cell already passes it (a necessary condition: false all along the
                 // diagonal phase, true right after it).  Not for QMAX <= 64: there the scan's
                 // registers cost the int16 form its fourth wave per SIMD (127 -> 137 VGPRs)
-                const int ubm = m - 1 + gm;
-                const bool want = QMAX > 64 && alive && edge && ubm <= best && ubm < gsc;
-                if (QMAX > 64 && (i & BSW_PC_SCAN_PHASE) == BSW_PC_SCAN_PHASE && __ballot(want)) {
-                    const int ubc = pc_ubscan<QMAX, BY>(std::make_integer_sequence<int, NG>{}, hh, gq + beg, beg, r.enter);
-                    const bool stopc = want && ubc <= best && ubc < gsc;
+                if (QMAX > 64 && (i & BSW_PC_SCAN_PHASE) == BSW_PC_SCAN_PHASE) {
+                    const int ubm = m - 1 + gm;
+                    const lmask want = alive & edge & m_le(ubm, best) & m_lt(ubm, gsc);
+                    if (want) {
+                        const int ubc = pc_ubscan<QMAX, BY>(std::make_integer_sequence<int, NG>{}, hh, gq + beg, beg, r.enter);
+                        const lmask stopc = want & m_le(ubc, best) & m_lt(ubc, gsc);
 #ifdef BSW_PC_STATS
-                    nscan += 1;
-                    nstop_c += stopc;
+                        nscan += 1;
+                        nstop_c += m_on(stopc);
 #endif
-                    alive = alive && !stopc;
+                        alive &= ~stopc;
+                    }
                 }
 #endif
             }
@@ -534,44 +584,43 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
                 if ((i & BSW_PC_SKIP_MASK) == BSW_PC_SKIP_ROW) {
                     if constexpr (PRUNE) {         // the prune's precheck: every static beg > 0, and
                                                    // every staying lane at the query's end with gsc > 0
-                        pp.pre = i > wl_max && __ballot(alive && !(end == qlen && gsc > 0)) == 0;
+                        pp.pre = i > wl_max && (alive & ~(atend & m_gt(gsc, 0))) == 0;
                         // (qlen through an opaque move: its packed forms are then built in the walk,
                         // not hoisted into registers that live across the groups)
                         asm volatile("v_mov_b32_e32 %0, %1" : "=v"(pp.qlen) : "v"(qlen));
                         pp.beg = beg; pp.gsc = gsc;
                     }
-                    pc_gz_refresh<QMAX, BY, PRUNE>(std::make_integer_sequence<int, (NG + 7) / 8>{}, hh, ee, alive, gz,
-                                                   pp);
+                    pc_gz_refresh<QMAX, BY, PRUNE>(std::make_integer_sequence<int, (NG + 7) / 8>{}, hh, ee, m_on(alive),
+                                                   gz, pp);
                     if constexpr (RP) {
                         // the right cap: precheck (i >= ROW0 and every staying lane with a new best in the last
                         // K rows: on a growing diagonal, where gscore will follow best), then the walk; a
                         // failed precheck under a cap retreats one group
-                        if (__ballot(alive && !(i >= BSW_PC_RP_ROW0 && i - best_i <= BSW_PC_RP_K))) {
+                        if (alive & (i < BSW_PC_RP_ROW0 ? ~0ull : m_gt(i - best_i, BSW_PC_RP_K))) {
                             if (cap4 < QMAX) {
                                 cap4 += 4;
 #ifdef BSW_PC_STATS
                                 nrret += 1;
 #endif
                             }
-                        } else if ((!rmark || (i & BSW_PC_RP_WALK_MASK) == (BSW_PC_SKIP_ROW & BSW_PC_RP_WALK_MASK)) &&
-                                   __ballot(alive)) {
+                        } else if ((!rmark || (i & BSW_PC_RP_WALK_MASK) == (BSW_PC_SKIP_ROW & BSW_PC_RP_WALK_MASK)) && alive) {
                             int ql;                 // (opaque, as pp.qlen)
                             asm volatile("v_mov_b32_e32 %0, %1" : "=v"(ql) : "v"(qlen));
                             const uint32_t nev0 = nrev;
-                            pc_rp_walk<QMAX>(std::make_integer_sequence<int, NG / 8>{}, hh, ee, alive,
+                            pc_rp_walk<QMAX>(std::make_integer_sequence<int, NG / 8>{}, hh, ee, m_on(alive),
                                              pc_gz_of<PRUNE>(gz), cap4, ql, best - BSW_PC_RP_MARGIN, nrev);
                             if (nrev != nev0) {     // uniform: T was applied to every staying lane
                                 rmark = true;
-                                sp = pc_sp_set(sp, alive ? pc_rp_raise(pc_sp_hi(sp), best - BSW_PC_RP_MARGIN) : pc_sp_hi(sp), false);
+                                sp = pc_sp_set(sp, m_on(alive) ? pc_rp_raise(pc_sp_hi(sp), best - BSW_PC_RP_MARGIN) : pc_sp_hi(sp), false);
                             }
                         }
                         // the soft retreat, after the walk: one group up when a staying lane's crossing value, at the
-                        // cap or within RWIN slots under it, comes near its threshold (one ballot; the certificate
+                        // cap or within RWIN slots under it, comes near its threshold (one vote; the certificate
                         // is what soundness rests on).  A cap the walk has just put above a moving band edge is
                         // taken back before the edge reaches it: a band narrower than the query never clips
                         if (rmark && cap4 < QMAX &&
-                            __ballot(alive && end < qlen && end + BSW_PC_RP_RWIN >= cap4 &&
-                                     h1 + (qlen - end) + BSW_PC_RP_SLACK2 >= best - BSW_PC_RP_MARGIN)) {
+                            (alive & ~atend & m_ge(end + BSW_PC_RP_RWIN, cap4) &
+                             m_ge(h1 + (qlen - end) + BSW_PC_RP_SLACK2, best - BSW_PC_RP_MARGIN))) {
                             cap4 += 4;
 #ifdef BSW_PC_STATS
                             nrret += 1;
@@ -581,21 +630,21 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
                 }
             }
 #ifdef BSW_PC_STATS
-            nrows += act;
-            nue += act && (emax == emin);  // every live lane has the same band end
+            nrows += m_on(act);
+            nue += m_on(act) && (emax == emin);  // every live lane has the same band end
 #endif
             {                                      // end_{i+1} = min(lastH + 3, ...), DESIGN.md §3
-                const bool need = alive && h1 == 0;  // H(i, end-1) == 0 -> lastH < end - 1
+                const lmask need = alive & h1z;          // H(i, end-1) == 0 -> lastH < end - 1
                 int lp1 = end;
-                if (__ballot(need)) {
+                if (need) {
 #ifdef BSW_PC_STATS
                     nlast += 1;
 #endif
-                    const int lp = pc_lastpos<QMAX, BY>(std::make_integer_sequence<int, NG>{}, hh, end, need,
+                    const int lp = pc_lastpos<QMAX, BY>(std::make_integer_sequence<int, NG>{}, hh, end, m_on(need),
                                                         emax >> 2);
-                    lp1 = need ? lp : end;
+                    lp1 = m_on(need) ? lp : end;
                 }
-                endc = alive ? min(lp1 + 2, qlen) : endc;
+                endc = m_on(alive) ? min(lp1 + 2, qlen) : endc;
             }
         }
     }
@@ -675,7 +724,7 @@ __global__ __launch_bounds__(64 * WPB, BY ? 3 : 2) void pc_kernel(const KParams 
         sp->score = best;
         sp->tle = best_i + 1;
         sp->gtle = max_ie + 1;
-        sp->qle = best_j + 1;
+        sp->qle = best_i - best_d + 1;
         sp->gscore = gsc;
         sp->max_off = moff;
     }
