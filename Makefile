@@ -16,10 +16,10 @@ SYNTH    := $(LIBDIR)/libbsw_synth.so
 SHIMTEST := $(LIBDIR)/bsw_shim_example
 ORACLE   := oracle/liboracle.so
 
-HIP_HDRS := $(CSRC)/bsw_devcache.h $(CSRC)/bsw_pool.h $(CSRC)/bsw_kernels.h $(CSRC)/bsw_mate_k.h include/bsw_mate.h $(CSRC)/bsw_global_k.h include/bsw_global.h $(CSRC)/bsw_ext_k.h $(CSRC)/bsw_aln_k.h include/bsw_aln.h $(CSRC)/bsw_sel_k.h $(CSRC)/bsw_sel_dev.h include/bsw_sel.h $(CSRC)/bsw_pe_k.h include/bsw_pe.h $(CSRC)/bsw_matesw_k.h include/bsw_matesw.h $(CSRC)/bsw_rec_k.h include/bsw_rec.h include/bsw_bam.h $(CSRC)/bsw_bgzf_k.h include/bsw_bgzf.h $(CSRC)/bsw_bamsort_k.h include/bsw_bamsort.h $(CSRC)/bsw_wave.h $(CSRC)/bsw_pc_rules.h $(CSRC)/bsw_pc_group.h $(CSRC)/bsw_pc_scan.h $(CSRC)/bsw_formulas.h $(CSRC)/bsw_contig_seg.h include/bsw_contigs.h $(CSRC)/bsw_stage_k.h $(CSRC)/bsw_internal.h $(CSRC)/bsw_stage_plan.h $(CSRC)/bsw_engine.h $(CSRC)/bsw_sort.h $(CSRC)/bsw_fmi_internal.h include/bsw.h include/bsw_seqpair.h include/bsw_ext.h include/bsw_batch.h include/bsw_fmi.h include/bsw_fmi_launch.h
+HIP_HDRS := $(CSRC)/bsw_devcache.h $(CSRC)/bsw_pool.h $(CSRC)/bsw_kernels.h $(CSRC)/bsw_mate_k.h include/bsw_mate.h $(CSRC)/bsw_global_k.h include/bsw_global.h $(CSRC)/bsw_ext_k.h $(CSRC)/bsw_aln_k.h include/bsw_aln.h $(CSRC)/bsw_sel_k.h $(CSRC)/bsw_sel_dev.h include/bsw_sel.h $(CSRC)/bsw_pe_k.h include/bsw_pe.h $(CSRC)/bsw_matesw_k.h include/bsw_matesw.h $(CSRC)/bsw_rec_k.h include/bsw_rec.h include/bsw_bam.h $(CSRC)/bsw_bgzf_k.h include/bsw_bgzf.h $(CSRC)/bsw_bamsort_k.h include/bsw_bamsort.h $(CSRC)/bsw_markdup_k.h include/bsw_markdup.h $(CSRC)/bsw_wave.h $(CSRC)/bsw_pc_rules.h $(CSRC)/bsw_pc_group.h $(CSRC)/bsw_pc_scan.h $(CSRC)/bsw_formulas.h $(CSRC)/bsw_contig_seg.h include/bsw_contigs.h $(CSRC)/bsw_stage_k.h $(CSRC)/bsw_internal.h $(CSRC)/bsw_stage_plan.h $(CSRC)/bsw_engine.h $(CSRC)/bsw_sort.h $(CSRC)/bsw_fmi_internal.h include/bsw.h include/bsw_seqpair.h include/bsw_ext.h include/bsw_batch.h include/bsw_fmi.h include/bsw_fmi_launch.h
 
 # the product's objects; the experiment libraries below are this list with one object swapped
-OBJS := $(addprefix $(LIBDIR)/,bsw_kernels.o bsw_pc.o bsw_wv.o bsw_gq.o bsw_mate.o bsw_global.o bsw_ext_dev.o bsw_aln.o bsw_sel.o bsw_pe.o bsw_matesw.o bsw_rec.o bsw_bgzf.o bsw_bamsort.o bsw_stage.o \
+OBJS := $(addprefix $(LIBDIR)/,bsw_kernels.o bsw_pc.o bsw_wv.o bsw_gq.o bsw_mate.o bsw_global.o bsw_ext_dev.o bsw_aln.o bsw_sel.o bsw_pe.o bsw_matesw.o bsw_rec.o bsw_bgzf.o bsw_bamsort.o bsw_markdup.o bsw_stage.o \
           bsw_fmi.o bsw_fmi_build.o bsw_memchain.o bsw_chain.o bsw_dispatch.o bsw_sort.o bsw_pipeline.o bsw_host.o bsw_stages.o bsw_ext.o \
           bsw_pack.o bsw_devcache.o bsw_batch.o)
 LINK  = $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(1) -lpthread
@@ -75,8 +75,18 @@ $(BAMSORT_MODEL): tools/bamsort_model.cpp $(CSRC)/bsw_bamsort_k.h | $(LIBDIR)
 $(BAMSORT_MODEL)_asan: tools/bamsort_model.cpp $(CSRC)/bsw_bamsort_k.h | $(LIBDIR)
 	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I$(CSRC) -o $@ $<
 
+# the serial model of the duplicate marking (tools/markdup_model.cpp over bsw_markdup_k.h; no GPU), and the same program
+# under AddressSanitizer + UBSan: stand-alone, run over files (tests/test_markdup.py writes them)
+MARKDUP_MODEL := $(LIBDIR)/markdup_model
+MARKDUP_DEPS  := tools/markdup_model.cpp $(CSRC)/bsw_markdup_k.h $(CSRC)/bsw_contig_seg.h $(CSRC)/bsw_formulas.h include/bsw_rec.h
+markdup-model: $(MARKDUP_MODEL) $(MARKDUP_MODEL)_asan
+$(MARKDUP_MODEL): $(MARKDUP_DEPS) | $(LIBDIR)
+	g++ -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $<
+$(MARKDUP_MODEL)_asan: $(MARKDUP_DEPS) | $(LIBDIR)
+	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I$(CSRC) -o $@ $<
+
 clean:
-	rm -f $(LIBDIR)/*.o $(LIBDIR)/*.so $(ORACLE) $(BAMSORT_MODEL) $(BAMSORT_MODEL)_asan
+	rm -f $(LIBDIR)/*.o $(LIBDIR)/*.so $(ORACLE) $(BAMSORT_MODEL) $(BAMSORT_MODEL)_asan $(MARKDUP_MODEL) $(MARKDUP_MODEL)_asan
 
 # experiment build: pc_kernel group-path counters (tools/pc_stats.py), never loaded by the product
 STATSLIB := $(LIBDIR)/libbsw_hip_stats.so
@@ -91,7 +101,8 @@ $(STATSLIB): $(subst bsw_pc.o,bsw_pc_stats.o,$(OBJS))
 # host_shard) -> libbsw_hip_abhost.so; abfmi: bsw_fmi.hip (SMEM walk) -> libbsw_hip_abfmi.so; abrec: bsw_rec.hip
 # (lanes per record of the text kernel, -DBSW_REC_TEXT_GROUP=N, and of the BAM kernel, -DBSW_REC_BAM_GROUP=N)
 # -> libbsw_hip_abrec.so; absort: bsw_sort.hip (-DBSW_SORT_ONESWEEP: the library's radix route) -> libbsw_hip_absort.so;
-# abbgzf: bsw_bgzf.hip (-DBSW_BGZF_PACK_BYTES: byte stores in the compaction) -> libbsw_hip_abbgzf.so
+# abbgzf: bsw_bgzf.hip (-DBSW_BGZF_PACK_BYTES: byte stores in the compaction) -> libbsw_hip_abbgzf.so;
+# abmarkdup: bsw_markdup.hip (lanes per read of the score kernel, -DBSW_MD_SCORE_GROUP=N) -> libbsw_hip_abmarkdup.so
 AB_FLAGS ?=
 AB_SRC_ab := bsw_pc
 AB_SRC_abhost := bsw_pipeline
@@ -99,11 +110,12 @@ AB_SRC_abfmi := bsw_fmi
 AB_SRC_abrec := bsw_rec
 AB_SRC_absort := bsw_sort
 AB_SRC_abbgzf := bsw_bgzf
-ab abhost abfmi abrec absort abbgzf:
+AB_SRC_abmarkdup := bsw_markdup
+ab abhost abfmi abrec absort abbgzf abmarkdup:
 	$(HIPCC) $(HIPFLAGS) $(AB_FLAGS) -c $(CSRC)/$(AB_SRC_$@).hip -o $(LIBDIR)/$(AB_SRC_$@)_ab.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/libbsw_hip_$@.so $(subst $(AB_SRC_$@).o,$(AB_SRC_$@)_ab.o,$(OBJS)) -lpthread
 
-.PHONY: all product synth oracle percall clean stats ab abfmi abhost abrec absort abbgzf bamsort-model
+.PHONY: all product synth oracle percall clean stats ab abfmi abhost abrec absort abbgzf abmarkdup bamsort-model markdup-model
 
 # host sanitizer build: AddressSanitizer + UBSan over the host C / C++ of the
 # product (bsw_pack.cpp, bsw_ext.cpp, bsw_batch.c, bsw_synth.c) and the oracle, driven by

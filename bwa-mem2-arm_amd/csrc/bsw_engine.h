@@ -33,6 +33,7 @@
 #include "../../include/bsw_bam.h"
 #include "../../include/bsw_bgzf.h"
 #include "../../include/bsw_bamsort.h"
+#include "../../include/bsw_markdup.h"
 #include "../../include/bsw_contigs.h"
 #include "bsw_contig_seg.h"
 #include "bsw_kernels.h"
@@ -170,6 +171,7 @@ struct BSW_HIDDEN Slot {
     Event evm;                          // class-count readback of the last run_plan
     Event evh;                          // inputs ready on the call's stream (pstream waits)
     Event evd;                          // host pipeline: a chunk's DP done (its outputs' readback waits)
+    Event evq0, evq1;                   // duplicate marking: its mark group (the other groups: ev0 / ev1, ev2 / ev3, evw0 / evw1)
     Event evw0, evw1;                   // mate-rescue stage: its helper kernels (the batched ksw_align2 times itself with ev0..ev3)
     // device buffers (grown on demand)
     DevBuf<SeqPair> d_pairs;
@@ -254,6 +256,11 @@ struct BSW_HIDDEN Slot {
     DevBuf<uint32_t> d_qlin;            // index: the flat linear index, sum((ref_len + 16383) >> 14) entries
     DevBuf<int64_t> d_qref64;           // index: win_off, ref_size, ref_off (n_ref + 1 each), then ref_len
     DevBuf<int32_t> d_qmeta;            // kBsMetaWords / kBiMetaWords
+    // duplicate marking (bsw_markdup.h); scans and radix sorts use d_tmp, the host form stages in d_aio, the kernel
+    // groups are timed with ev0 / ev1, ev2 / ev3, evw0 / evw1 and evq0 / evq1
+    DevBuf<uint64_t> d_dwords;          // end words, key words, the sorts' keys in and out
+    DevBuf<int32_t> d_dints;            // scores, flags, scans, compact indices, the sorts' values, set heads; the marks
+    DevBuf<int32_t> d_dmeta;            // kMdMetaWords
     bool timed = false;
     hipStream_t run_stream = nullptr;   // stream of the last run_device (finish_stats waits on it)
     bsw_stats_t stats{};
@@ -453,6 +460,7 @@ struct bsw_ctx {
     bsw_bam_stats_t bam_last{};
     bsw_bgzf_stats_t bgzf_last{};
     bsw_bamsort_stats_t bamsort_last{};
+    bsw_markdup_stats_t markdup_last{};
     struct Pinned { std::mutex mu; bsw::PinnedBuf<uint8_t> b; } pin[2];
     int glob_band = 0;                  // BSW_OPT_GLOB_BAND
     int64_t ext_chunk = 0;              // BSW_OPT_EXT_CHUNK (0: the int32-offset bound)

@@ -1,8 +1,9 @@
 // bsw_stages.cpp -- the stages behind the extension, each in a device-resident form and a
 // host-array form behind the C ABI: final alignments (bsw_aln.h), region selection (bsw_sel.h),
 // the paired-end stage (bsw_pe.h), mate rescue (bsw_matesw.h), SAM records (bsw_rec.h), BGZF
-// (bsw_bgzf.h) and the BAM sort and index (bsw_bamsort.h).  Their kernels are in bsw_aln.hip, bsw_sel.hip,
-// bsw_pe.hip, bsw_matesw.hip, bsw_rec.hip, bsw_bgzf.hip and bsw_bamsort.hip; what the calls share is below.
+// (bsw_bgzf.h), the BAM sort and index (bsw_bamsort.h) and duplicate marking (bsw_markdup.h).  Their kernels are in
+// bsw_aln.hip, bsw_sel.hip, bsw_pe.hip, bsw_matesw.hip, bsw_rec.hip, bsw_bgzf.hip, bsw_bamsort.hip and bsw_markdup.hip;
+// what the calls share is below.
 // (Layout of the engine: bsw_engine.h.)
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -20,6 +21,7 @@
 #include "bsw_rec_k.h"
 #include "bsw_bgzf_k.h"
 #include "bsw_bamsort_k.h"
+#include "bsw_markdup_k.h"
 #include "bsw_stage_k.h"
 
 // ---------------------------------------------------------------- shared by the stages
@@ -1507,6 +1509,199 @@ static void put_bamsort_stats(bsw_ctx_t *ctx, const bsw_bamsort_stats_t &qs, boo
     }
 }
 
+// ---------------------------------------------------------------- duplicate marking (bsw_markdup.h)
+static int markdup_check_args(const bsw_ctx_t *ctx, const bsw_markdup_opt_t *opt, const void *recs, const void *rec_first,
+                              int32_t n_rec, const void *aln, const void *cigar, int32_t cigar_stride, int32_t n_aln,
+                              const void *read_off, const void *read_len, int32_t n_reads, int64_t quals_len, int32_t paired,
+                              const void *dup)
+{
+    if (!ctx || !opt || opt->l_pac <= 0 || opt->l_pac > markdup::kMaxLPac || opt->min_qual < 0 || opt->flags) return BSW_E_INVAL;
+    if (n_rec < 0 || n_aln < 0 || n_reads < 0 || quals_len < 0 || cigar_stride < 1 || (paired && (n_reads & 1))) return BSW_E_INVAL;
+    if ((n_reads > 0 && (!rec_first || !read_off || !read_len || !dup)) || (n_rec > 0 && !recs) || (n_aln > 0 && (!aln || !cigar)))
+        return BSW_E_INVAL;
+    return BSW_OK;
+}
+
+static bool markdup_ctg_ok(const DeviceCtx &dc, const bsw_markdup_opt_t &opt)
+{
+    return dc.ctg_ok(opt.l_pac) && dc.n_ctg <= markdup::kMaxContigs;
+}
+
+// The stable sort of n members by the words of k, most significant first: perm[j] = the member at sorted place j.
+// Digits come from the varying bits (k.mask) alone.  They fit one word: packed, one radix sort.  Otherwise stable LSD
+// passes of the 64-bit sort, the low word first, each over its word's span of varying bits.
+static int md_sort(hipStream_t st, const MdWords &k, int32_t n, uint64_t *key_a, uint64_t *key_b, int32_t *val_a,
+                   int32_t *perm, void *tmp, size_t tmp_bytes, int32_t *bits, int32_t *route)
+{
+    int total = 0, passes = 0;
+    for (int q = 0; q < k.n; ++q) {
+        total += markdup::bit_count(k.mask[q]);
+        passes += k.mask[q] != 0;
+    }
+    *bits = total;
+    size_t tb = tmp_bytes;
+    if (total == 0) {                               // no bit varies: the input order
+        *route = BSW_MARKDUP_ROUTE_NONE;
+        BSW_TRY(launch_md_gather(k.w[0], nullptr, n, key_a, perm, st));
+    } else if (total <= 64) {
+        *route = BSW_MARKDUP_ROUTE_ONE;
+        BSW_TRY(launch_md_pack(k, n, key_a, val_a, st));
+        BSW_TRY(launch_bamsort_pairs(tmp, &tb, key_a, key_b, val_a, perm, n, 0, total, st));
+    } else {
+        *route = BSW_MARKDUP_ROUTE_MULTI;
+        int32_t *in = nullptr;
+        int i = 0;
+        for (int q = k.n - 1; q >= 0; --q) {
+            if (!k.mask[q]) continue;
+            int32_t *out = (passes - 1 - i) & 1 ? val_a : perm;     // (the last pass leaves perm)
+            int lo, hi;
+            markdup::mask_span(k.mask[q], &lo, &hi);
+            if (!in) in = out == perm ? val_a : perm;               // the first pass: the input order
+            BSW_TRY(launch_md_gather(k.w[q], i ? in : nullptr, n, key_a, in, st));
+            tb = tmp_bytes;
+            BSW_TRY(launch_bamsort_pairs(tmp, &tb, key_a, key_b, in, out, n, lo, hi, st));
+            in = out;
+            ++i;
+        }
+    }
+    return BSW_OK;
+}
+
+struct MdIo {                           // device pointers of one call, either form
+    bsw_rec_t *recs;
+    const int32_t *rec_first;
+    const bsw_aln_t *aln;
+    const uint32_t *cigar;
+    const int64_t *read_off;
+    const int32_t *read_len;
+    const uint8_t *quals;
+    uint8_t *dup;
+};
+
+// scores -> ends, candidates, scans, keys -> ONE readback before anything of the caller's is written (error word, the
+// counts, the keys' OR / NOR) -> the pair sort and the end sort -> set heads and marks -> the mark kernel -> the counters
+static int markdup_device(const DeviceCtx &dc, Slot &s, hipStream_t st, const bsw_markdup_opt_t &opt, const MdIo &io,
+                          int32_t n_rec, int32_t n_aln, int32_t cigar_stride, int32_t n_reads, int64_t quals_len,
+                          int32_t paired, bsw_markdup_stats_t &ds)
+{
+    const size_t N = (size_t)n_reads, P = paired ? N / 2 : 0;
+    size_t scan_bytes = 0, sort_bytes = 0;
+    BSW_TRY(launch_scan32(nullptr, &scan_bytes, nullptr, nullptr, n_reads, st));
+    BSW_TRY(launch_bamsort_pairs(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, n_reads, 0, 64, st));
+    const size_t tmp_bytes = std::max<size_t>(std::max(scan_bytes, sort_bytes), 16);
+    BSW_TRY(s.d_tmp.grow(tmp_bytes));
+    BSW_TRY(s.d_dwords.grow(5 * N + 3 * P));
+    BSW_TRY(s.d_dints.grow(10 * (N + 1) + 4 * (P + 1) + (N + 3) / 4));
+    BSW_TRY(s.d_dmeta.grow(kMdMetaWords));
+    MdArgs a{};
+    a.recs = io.recs; a.rec_first = io.rec_first; a.aln = io.aln; a.cigar = io.cigar;
+    a.read_off = io.read_off; a.read_len = io.read_len; a.quals = io.quals; a.dup = io.dup;
+    a.quals_len = quals_len; a.l_pac = opt.l_pac;
+    a.n_rec = n_rec; a.n_aln = n_aln; a.n_reads = n_reads; a.n_pairs = (int32_t)P; a.cigar_stride = cigar_stride;
+    a.paired = paired != 0; a.min_qual = opt.min_qual;
+    a.ctg = dc.ctg_view(opt.l_pac);
+    uint64_t *w = s.d_dwords;
+    a.eword = w; w += N;
+    for (int q = 0; q < 3; ++q) { a.pkey[q] = w; w += P; }
+    for (int q = 0; q < 2; ++q) { a.ekey[q] = w; w += N; }
+    uint64_t *key_a = w, *key_b = w + N;
+    int32_t *v = s.d_dints;
+    a.score = v; v += N + 1;
+    a.cflag = v; v += N + 1;
+    a.cidx = v; v += N + 1;
+    a.cid = v; v += N + 1;
+    int32_t *val_a = v; v += N + 1;
+    int32_t *perm_e = v; v += N + 1;
+    a.hflag = v; v += N + 1;
+    a.hidx = v; v += N + 1;
+    a.hpos = v; v += N + 1;
+    a.pflag = v; v += P + 1;
+    a.pidx = v; v += P + 1;
+    a.pid = v; v += P + 1;
+    int32_t *perm_p = v; v += P + 1;
+    a.dupr = (uint8_t *)v;                          // the tenth run of N + 1 ints is spare
+    a.meta = s.d_dmeta;
+    HelperTimer t_score, t_key, t_sort, t_mark;     // one event pair of the slot each
+    BSW_TRY(t_score.init(s.ev0, s.ev1, st));
+    BSW_TRY(t_key.init(s.ev2, s.ev3, st));
+    BSW_TRY(t_sort.init(s.evw0, s.evw1, st));
+    BSW_TRY(t_mark.init(s.evq0, s.evq1, st));
+    static_assert(kMdMetaWords + 2 <= kMetaWords, "the slot's pinned mirror holds the meta words and the two counts");
+    BSW_TRY(hipMemsetAsync(s.d_dmeta, 0, kMdMetaWords * sizeof(int32_t), st));
+    BSW_TRY(hipMemsetAsync(a.dupr, 0, N, st));
+    BSW_TRY(t_score.begin());
+    BSW_TRY(launch_md_scores(a, st));
+    BSW_TRY(t_score.end());
+    BSW_TRY(t_key.begin());
+    BSW_TRY(launch_md_ends(a, st));
+    size_t tb = tmp_bytes;
+    BSW_TRY(launch_scan32(s.d_tmp, &tb, a.cflag, a.cidx, n_reads, st));
+    if (P) {
+        tb = tmp_bytes;
+        BSW_TRY(launch_scan32(s.d_tmp, &tb, a.pflag, a.pidx, (int32_t)P, st));
+    }
+    BSW_TRY(launch_md_keys(a, st));
+    BSW_TRY(t_key.end());
+    s.h_meta[kMdMetaWords + 1] = 0;
+    BSW_TRY(hipMemcpyAsync(s.h_meta, s.d_dmeta, kMdMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipMemcpyAsync(s.h_meta + kMdMetaWords, a.cidx + N, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (P) BSW_TRY(hipMemcpyAsync(s.h_meta + kMdMetaWords + 1, a.pidx + P, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(t_score.add(ds.score_ms));
+    BSW_TRY(t_key.add(ds.key_ms));
+    if (s.h_meta[kMdErr]) return BSW_E_RANGE;
+    const int32_t n_cand = s.h_meta[kMdMetaWords], n_pc = s.h_meta[kMdMetaWords + 1];
+    ds.n_cand = n_cand;
+    ds.n_pair_cand = n_pc;
+    auto words = [&](uint64_t *const *arr, int n, int at_or, int at_nor) {
+        MdWords k{};
+        k.n = n;
+        for (int q = 0; q < n; ++q) {
+            uint64_t or_, nor_;
+            memcpy(&or_, s.h_meta + at_or + 2 * q, sizeof or_);
+            memcpy(&nor_, s.h_meta + at_nor + 2 * q, sizeof nor_);
+            k.w[q] = arr[q];
+            k.mask[q] = or_ & nor_;
+        }
+        return k;
+    };
+    MdWords kp = words(a.pkey, 3, kMdOrPair, kMdNorPair), ke = words(a.ekey, 2, kMdOrEnd, kMdNorEnd);
+    BSW_TRY(t_sort.begin());
+    if (n_pc > 0)
+        if (const int r = md_sort(st, kp, n_pc, key_a, key_b, val_a, perm_p, s.d_tmp, tmp_bytes, &ds.pair_key_bits, &ds.pair_route))
+            return r;
+    if (n_cand > 0)
+        if (const int r = md_sort(st, ke, n_cand, key_a, key_b, val_a, perm_e, s.d_tmp, tmp_bytes, &ds.end_key_bits, &ds.end_route))
+            return r;
+    BSW_TRY(t_sort.end());
+    BSW_TRY(t_mark.begin());
+    if (n_pc > 0) {
+        kp.n = 2;                                   // a set: equal ends, whatever the score
+        BSW_TRY(launch_md_heads(kp, perm_p, n_pc, a.hflag, st));
+        BSW_TRY(launch_md_pair_marks(a, perm_p, n_pc, st));
+    }
+    if (n_cand > 0) {
+        ke.n = 1;
+        BSW_TRY(launch_md_heads(ke, perm_e, n_cand, a.hflag, st));
+        tb = tmp_bytes;
+        BSW_TRY(launch_scan32(s.d_tmp, &tb, a.hflag, a.hidx, n_cand, st));
+        BSW_TRY(launch_md_end_marks(a, perm_e, n_cand, st));
+    }
+    BSW_TRY(launch_md_mark(a, st));
+    BSW_TRY(t_mark.end());
+    BSW_TRY(hipMemcpyAsync(s.h_meta, s.d_dmeta, kMdMetaWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BSW_TRY(hipStreamSynchronize(st));
+    BSW_TRY(t_sort.add(ds.sort_ms));
+    BSW_TRY(t_mark.add(ds.mark_ms));
+    ds.n_dup_pairs = s.h_meta[kMdDupPairs];
+    ds.n_dup_frag = s.h_meta[kMdDupFrag];
+    ds.n_dup_frag_by_pair = s.h_meta[kMdDupFragByPair];
+    ds.n_pair_sets = s.h_meta[kMdPairSets];
+    ds.n_end_sets = s.h_meta[kMdEndSets];
+    ds.n_flagged = s.h_meta[kMdFlagged];
+    return BSW_OK;
+}
+
 }  // namespace bsw
 
 extern "C" {
@@ -2028,6 +2223,86 @@ int bsw_bam_index(bsw_ctx_t *ctx, const bsw_bamsort_opt_t *opt, const int32_t *r
 int bsw_bamsort_last_stats(bsw_ctx_t *ctx, bsw_bamsort_stats_t *out)
 {
     return bsw::get_stats(ctx, &bsw_ctx::bamsort_last, out);
+}
+
+// ---------------------------------------------------------------- duplicate marking (include/bsw_markdup.h)
+void bsw_markdup_opt_default(bsw_markdup_opt_t *opt)
+{
+    if (!opt) return;
+    memset(opt, 0, sizeof(*opt));
+    opt->min_qual = 15;
+}
+
+int bsw_mark_duplicates_resident(bsw_ctx_t *ctx, const bsw_markdup_opt_t *opt, bsw_rec_t *d_recs,
+                                 const int32_t *d_rec_first, int32_t n_rec, const bsw_aln_t *d_aln,
+                                 const uint32_t *d_cigar, int32_t cigar_stride, int32_t n_aln,
+                                 const int64_t *d_read_off, const int32_t *d_read_len, int32_t n_reads,
+                                 const uint8_t *d_quals, int64_t quals_len, int32_t paired, uint8_t *d_dup, void *stream)
+{
+    if (const int rc = bsw::markdup_check_args(ctx, opt, d_recs, d_rec_first, n_rec, d_aln, d_cigar, cigar_stride, n_aln,
+                                               d_read_off, d_read_len, n_reads, quals_len, paired, d_dup))
+        return rc;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);   // the contig table stays put
+    if (!bsw::markdup_ctg_ok(dc, *opt)) return BSW_E_INVAL;
+    bsw_markdup_stats_t ds{};
+    ds.n_reads = n_reads;
+    if (n_reads > 0) {
+        const bsw::MdIo io{d_recs, d_rec_first, d_aln, d_cigar, d_read_off, d_read_len, d_quals, d_dup};
+        const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+            hipStream_t st = stream ? (hipStream_t)stream : s.stream;
+            return bsw::markdup_device(dc, s, st, *opt, io, n_rec, n_aln, cigar_stride, n_reads, quals_len, paired, ds);
+        });
+        if (rc) return rc;
+    }
+    bsw::put_stats(ctx, &bsw_ctx::markdup_last, ds);
+    return BSW_OK;
+}
+
+int bsw_mark_duplicates(bsw_ctx_t *ctx, const bsw_markdup_opt_t *opt, bsw_rec_t *recs, const int32_t *rec_first,
+                        int32_t n_rec, const bsw_aln_t *aln, const uint32_t *cigar, int32_t cigar_stride, int32_t n_aln,
+                        const int64_t *read_off, const int32_t *read_len, int32_t n_reads, const uint8_t *quals,
+                        int64_t quals_len, int32_t paired, uint8_t *dup)
+{
+    if (const int rc = bsw::markdup_check_args(ctx, opt, recs, rec_first, n_rec, aln, cigar, cigar_stride, n_aln, read_off,
+                                               read_len, n_reads, quals_len, paired, dup))
+        return rc;
+    bsw::DeviceCtx &dc = *ctx->devs[0];
+    std::shared_lock<std::shared_mutex> refg(dc.refmu);
+    if (!bsw::markdup_ctg_ok(dc, *opt)) return BSW_E_INVAL;
+    bsw_markdup_stats_t ds{};
+    ds.n_reads = n_reads;
+    if (n_reads > 0) {
+        const size_t nr = (size_t)n_reads, nc = (size_t)n_rec, na = (size_t)n_aln;
+        bsw::StagedIo io;
+        const auto d_recs = io.inout(recs, nc);
+        const auto d_rec_first = io.in(rec_first, nr + 1);
+        const auto d_aln = io.in(aln, na);
+        const auto d_cigar = io.in(cigar, na * (size_t)cigar_stride);
+        const auto d_read_off = io.in(read_off, nr);
+        const auto d_read_len = io.in(read_len, nr);
+        const auto d_quals = io.in_opt(quals, (size_t)quals_len);
+        const auto d_dup = io.out(dup, nr);
+        const int rc = bsw::with_slot(dc, [&](bsw::Slot &s) -> int {
+            BSW_TRY(io.stage(s));
+            const bsw::MdIo m{d_recs, d_rec_first, d_aln, d_cigar, d_read_off, d_read_len, d_quals, d_dup};
+            if (const int r = bsw::markdup_device(dc, s, s.stream, *opt, m, n_rec, n_aln, cigar_stride, n_reads, quals_len,
+                                                  paired, ds))
+                return r;
+            BSW_TRY(io.back(d_recs));
+            BSW_TRY(io.back(d_dup));
+            BSW_TRY(hipStreamSynchronize(s.stream));
+            return BSW_OK;
+        });
+        if (rc) return rc;
+    }
+    bsw::put_stats(ctx, &bsw_ctx::markdup_last, ds);
+    return BSW_OK;
+}
+
+int bsw_markdup_last_stats(bsw_ctx_t *ctx, bsw_markdup_stats_t *out)
+{
+    return bsw::get_stats(ctx, &bsw_ctx::markdup_last, out);
 }
 
 }  // extern "C"

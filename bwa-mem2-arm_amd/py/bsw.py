@@ -63,6 +63,10 @@ BAMSORT_SYMBOLS = ("bsw_bam_sort", "bsw_bam_sort_resident", "bsw_bam_index", "bs
                    "bsw_bamsort_last_stats")
 # include/bsw_fmi_launch.h (additive likewise: BSW_FMI_LAUNCH_API)
 FMI_LAUNCH_SYMBOLS = ("bsw_fmi_last_launch",)
+# include/bsw_markdup.h (additive likewise: BSW_MARKDUP_API)
+MARKDUP_SYMBOLS = ("bsw_markdup_opt_default", "bsw_mark_duplicates", "bsw_mark_duplicates_resident", "bsw_markdup_last_stats")
+BSW_DUP_PAIR, BSW_DUP_FRAG, BSW_DUP_FRAG_BY_PAIR = 1, 2, 3
+MARKDUP_ROUTE_NONE, MARKDUP_ROUTE_ONE, MARKDUP_ROUTE_MULTI = 0, 1, 2
 BAMSORT_PERM_TILE = 8192           # bytes of output per workgroup of the permute kernel (bsw_bamsort_k.h: kPermTile), for tests
 BAMSORT_SORT_TILE = 4096            # a size above which the radix sort runs over more than one of its tiles, for tests
 CONTIG_MAX_NAME = 63
@@ -281,6 +285,13 @@ def hip_lib():
         L.bsw_bam_index_resident.argtypes = L.bsw_bam_index.argtypes + [P]
         L.bsw_bamsort_last_stats.argtypes = [P, P]
         for f in BAMSORT_SYMBOLS:
+            getattr(L, f).restype = ctypes.c_int
+        L.bsw_markdup_opt_default.argtypes = [P]
+        L.bsw_markdup_opt_default.restype = None
+        L.bsw_mark_duplicates.argtypes = [P, P, P, P, i32, P, P, i32, i32, P, P, i32, P, i64, i32, P]
+        L.bsw_mark_duplicates_resident.argtypes = L.bsw_mark_duplicates.argtypes + [P]
+        L.bsw_markdup_last_stats.argtypes = [P, P]
+        for f in MARKDUP_SYMBOLS[1:]:
             getattr(L, f).restype = ctypes.c_int
         L.bsw_set_contigs.argtypes = [P, i32, P, ctypes.POINTER(ctypes.c_char_p)]
         L.bsw_set_contigs.restype = ctypes.c_int
@@ -1500,6 +1511,66 @@ def bam_index_resident(engine, ref_len, d_bam: int, d_bam_off: int, n_rec: int, 
 def bamsort_last_stats(engine) -> BamsortStats:
     st = BamsortStats()
     _check(hip_lib().bsw_bamsort_last_stats(engine._ctx, ctypes.byref(st)))
+    return st
+
+
+# ---------------------------------------------------------------- duplicate marking (bsw_markdup.h)
+class MarkdupOpt(ctypes.Structure):
+    _fields_ = [("l_pac", ctypes.c_int64), ("min_qual", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class MarkdupStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("n_reads", "n_cand", "n_pair_cand", "n_dup_pairs", "n_dup_frag", "n_dup_frag_by_pair",
+                                              "n_pair_sets", "n_end_sets", "n_flagged", "pair_key_bits", "end_key_bits",
+                                              "pair_route", "end_route")] + \
+               [(k, ctypes.c_float) for k in ("score_ms", "key_ms", "sort_ms", "mark_ms")] + [("reserved", ctypes.c_int32)]
+
+
+def markdup_opt(l_pac: int, min_qual: int | None = None, flags: int = 0) -> MarkdupOpt:
+    """bsw_markdup_opt_default with l_pac set; min_qual=None keeps the default (15)"""
+    o = MarkdupOpt()
+    hip_lib().bsw_markdup_opt_default(ctypes.byref(o))
+    o.l_pac, o.flags = l_pac, flags
+    if min_qual is not None:
+        o.min_qual = min_qual
+    return o
+
+
+def mark_duplicates(engine, recs, rec_first, aln, cigar, read_off, read_len, quals, paired: bool, opt: MarkdupOpt):
+    """bsw_mark_duplicates (host arrays): records, alignments and CIGAR rows as bsw_records left them, the reads'
+    offsets and lengths, quals (uint8, parallel to the reads) or None -> (the records with 0x400 set or cleared,
+    dup uint8 [n_reads])"""
+    recs = np.array(recs, dtype=REC_DTYPE, copy=True)
+    rec_first = np.ascontiguousarray(rec_first, dtype=np.int32)
+    aln = np.ascontiguousarray(aln, dtype=ALN_DTYPE)
+    cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+    read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+    read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+    n_reads = len(read_len)
+    stride = cigar.shape[1] if cigar.ndim == 2 else 1
+    q = None if quals is None else np.ascontiguousarray(
+        np.frombuffer(quals, dtype=np.uint8) if isinstance(quals, (bytes, bytearray)) else quals, dtype=np.uint8)
+    dup = np.zeros(max(n_reads, 1), dtype=np.uint8)
+    _check(hip_lib().bsw_mark_duplicates(engine._ctx, ctypes.byref(opt), _ptr(recs), _ptr(rec_first), len(recs), _ptr(aln),
+                                         _ptr(cigar), stride, len(aln), _ptr(read_off), _ptr(read_len), n_reads,
+                                         None if q is None else _ptr(q), 0 if q is None else len(q), int(bool(paired)), _ptr(dup)))
+    return recs, dup[:n_reads]
+
+
+def mark_duplicates_resident(engine, d_recs: int, d_rec_first: int, n_rec: int, d_aln: int, d_cigar: int, cigar_stride: int,
+                             n_aln: int, d_read_off: int, d_read_len: int, n_reads: int, d_quals: int, quals_len: int,
+                             paired: bool, d_dup: int, opt: MarkdupOpt, stream: int = 0) -> None:
+    """bsw_mark_duplicates_resident: every array a device pointer; d_recs is marked in place"""
+    V = ctypes.c_void_p
+    _check(hip_lib().bsw_mark_duplicates_resident(engine._ctx, ctypes.byref(opt), V(d_recs or None), V(d_rec_first or None), n_rec,
+                                                  V(d_aln or None), V(d_cigar or None), cigar_stride, n_aln, V(d_read_off or None),
+                                                  V(d_read_len or None), n_reads, V(d_quals or None), quals_len,
+                                                  int(bool(paired)), V(d_dup or None), V(stream or None)))
+
+
+def markdup_last_stats(engine) -> MarkdupStats:
+    st = MarkdupStats()
+    _check(hip_lib().bsw_markdup_last_stats(engine._ctx, ctypes.byref(st)))
     return st
 
 

@@ -1,6 +1,7 @@
 """ResidentBatch: the device arrays of one batch of reads and the resident stage chain over them,
 
     seeds -> chain2aln -> select -> pe_stat -> matesw -> pe_pair -> reg2aln / records -> sam_text / bam_records -> bgzf
+    (duplicates marked: records -> mark_duplicates -> sam_text / bam_records)
     (coordinate-sorted and indexed: bam_records -> bam_sort -> bgzf(src="sbam") -> bam_index)
 
 Plumbing for tests and tools, like bsw.py: every stage method is one bsw.*_resident call on the buffers the
@@ -44,6 +45,8 @@ BGZF_LAYOUT = {"bgzf": (np.uint8, (), "bgzf"), "bgzf_blk": (np.int64, (), "bgzf_
 # the coordinate-sorted blocks and their index (bsw_bamsort.h), in a table of its own likewise
 SORT_LAYOUT = {"sbam": (np.uint8, (), "sbam"), "sbam_off": (np.int64, (), "sbam_off"), "bam_perm": (np.int32, (), "bam_perm"),
                "bai": (np.uint8, (), "bai")}
+# the reads' duplicate marks (bsw_markdup.h), in a table of its own likewise
+DUP_LAYOUT = {"dup": (np.uint8, (), "n_reads")}
 FIXED = ("reads", "n_reads", "first")           # counts the constructor sets for good
 # (regs, read, info, first) as the extension, the selection and the rescue leave them
 LISTS = {"c": ("regs", "sr", None, None), "s": ("sreg", "sread", "sinfo", "sfirst"), "m": ("mreg", "mread", "minfo", "mfirst")}
@@ -52,7 +55,7 @@ LISTS = {"c": ("regs", "sr", None, None), "s": ("sreg", "sread", "sinfo", "sfirs
 def _row(name):
     """(dtype, stride keys, count key) of a buffer name"""
     pre, dot, base = name.rpartition(".")
-    table = next((t for t in (LAYOUT, BAM_LAYOUT, BGZF_LAYOUT, SORT_LAYOUT) if base in t), None)
+    table = next((t for t in (LAYOUT, BAM_LAYOUT, BGZF_LAYOUT, SORT_LAYOUT, DUP_LAYOUT) if base in t), None)
     if table is None:
         raise ValueError(f"no buffer named '{name}'")
     dtype, strides, key = table[base]
@@ -216,6 +219,17 @@ class ResidentBatch:
             self.engine, *self._p("reads", "off", "lens"), self.n_reads, *self._p(regs, info, first), k,
             self.buf["pairs"].ptr if paired else 0, *out, ropt)
         return self.n["recs"], self.n["aln"]
+
+    def mark_duplicates(self, dopt, paired=True):
+        """between records() and sam_text() / bam_records(): 0x400 set or cleared on "recs" in place, the reads' marks
+        in "dup" (bsw.BSW_DUP_*).  Returns bsw.markdup_last_stats."""
+        self._have("mark_duplicates", "recs", "rec_first", "aln", "cigar")
+        quals = self.buf.get("quals")
+        bsw.mark_duplicates_resident(self.engine, *self._p("recs", "rec_first"), self.n["recs"], *self._p("aln", "cigar"),
+                                     self.stride["cigar"], self.n["aln"], *self._p("off", "lens"), self.n_reads,
+                                     0 if quals is None else quals.ptr, 0 if quals is None else self.n["reads"], paired,
+                                     self.alloc("dup", self.n_reads).ptr, dopt)
+        return bsw.markdup_last_stats(self.engine)
 
     def _records_out(self, stage, fn, out, ropt, names, paired, cap):
         """call 2 in either form: fn = bsw.sam_text_resident into "text" / "text_off", or bsw.bam_records_resident

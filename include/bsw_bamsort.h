@@ -7,8 +7,9 @@
  * rules below and with an independent reader that follows SAMv1 section 5 from the query's side.  Byte parity
  * with `samtools index` is neither claimed nor needed: a reader of the format finds every record.
  *
- * SCOPE.  One call sorts one batch; merging the sorted runs of several batches, .csi indexes, duplicate
- * marking and file I/O are the caller's.  A run is a valid sorted BAM when the batch is the whole file.  The
+ * SCOPE.  One call sorts one batch; merging the sorted runs of several batches, .csi indexes and file I/O are
+ * the caller's (duplicates of one batch are marked upstream, bsw_markdup.h; duplicates across batches are the
+ * caller's).  A run is a valid sorted BAM when the batch is the whole file.  The
  * `@HD SO:coordinate` line is part of the caller's header text (bsw_bam_header copies it as given).
  * Both stages read nothing but BAM bytes and offsets: any uncompressed BAM record stream will do.
  *

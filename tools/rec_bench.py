@@ -28,10 +28,18 @@ beside this encoder's blocks of the same chunks.
   (x) bsw_bam_index_resident: index_ms, the index's size
 and, as context on the host, numpy's stable argsort over the same keys (its order has to be the device's).
 
+--markdup: duplicate marking (include/bsw_markdup.h) on the same fragments with a share d of them emitted a second time
+under fresh quals, for d = 0 and d = 0.1, each through the front end and bsw_records_resident; alternating:
+  (m) bsw_mark_duplicates_resident: wall time, score_ms, key_ms, sort_ms, mark_ms
+  (s) bsw_bam_sort_resident over the batch's BAM blocks: as many 64-bit keys, twice the bytes moved
+  (q) a device-to-device hipMemcpy of the quals bytes, beside score_ms
+and, for d = 0.1, d_dup against tests/markdup_py.py on a sample of 20,000 pairs taken with their whole sets.
+
     python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 7 --out profiles/rec/bench.json
     python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 7 --only-out --out profiles/bam/bench.json
     python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 5 --bgzf --out profiles/bgzf/bench.json
     python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 5 --sort --out profiles/bamsort/bench.json
+    python tools/rec_bench.py --pairs 1000000 --ref-mb 16 --reps 5 --markdup --out profiles/markdup/bench.json
 """
 
 import argparse
@@ -186,6 +194,112 @@ def sort_legs(args, eng, b, bam_bytes, bam, copy_bam, l_pac, log):
             "host_numpy_stable_argsort_s": round(t_np, 4)}
 
 
+def end_words(recs, rec_first, aln, cigar):
+    """per read (rid 0, u, s) as one integer, -1 for a read that is no candidate: numpy over the downloaded arrays, used
+    only to close the checked sample over its sets (the verdict on the sample is tests/markdup_py.py's)"""
+    first = recs[rec_first[:-1].clip(max=len(recs) - 1)]
+    cand = (rec_first[1:] > rec_first[:-1]) & (first["flag"] & 4 == 0)
+    a = first["aln"].clip(min=0)
+    cg, nc = cigar[a], aln["n_cigar"][a]
+    op, ln = (cg & 15).astype(np.int64), (cg >> 4).astype(np.int64)
+    live = np.arange(cg.shape[1])[None, :] < nc[:, None]
+    rlen = (ln * (live & ((op == 0) | (op == 2)))).sum(axis=1)
+    lead = np.where((op[:, 0] == 3) | (op[:, 0] == 4), ln[:, 0], 0)
+    last = np.take_along_axis(cg, (nc.clip(min=1) - 1)[:, None].astype(np.int64), axis=1)[:, 0].astype(np.int64)
+    trail = np.where((last & 15 == 3) | (last & 15 == 4), last >> 4, 0)
+    rev = first["is_rev"] != 0
+    u = np.where(rev, first["pos"] + rlen - 1 + trail, first["pos"] - lead)
+    return np.where(cand, (u + (1 << 31)) << 1 | rev, -1)
+
+
+def check_sample(b, l_pac, quals, off, lens, dup, n_sample, log):
+    """d_dup against tests/markdup_py.py on the first n_sample pairs, taken with every pair that shares an end with them"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import markdup_py as md
+    recs, rec_first, aln, cigar = b.get("recs"), b.get("rec_first"), b.get("aln"), b.get("cigar")
+    recs = recs.copy()
+    recs["flag"] &= ~0x400                                        # (the stage has run: its input is the records without the mark)
+    recs["sam_flag"] &= ~0x400
+    w = end_words(recs, rec_first, aln, cigar)
+    n_pairs = len(w) // 2
+    mine = w[:2 * n_sample]
+    hit = np.isin(w, mine[mine >= 0])
+    pairs = np.flatnonzero(hit[0::2] | hit[1::2] | (np.arange(n_pairs) < n_sample))
+    reads = np.stack([2 * pairs, 2 * pairs + 1], axis=1).ravel()
+    counts = (rec_first[1:] - rec_first[:-1])[reads]
+    sub_first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    idx = np.concatenate([np.arange(rec_first[r], rec_first[r + 1]) for r in reads])
+    sub = recs[idx]
+    sub["read"] = np.repeat(np.arange(len(reads)), counts)
+    c = md.make_case([], True, l_pac=l_pac, stride=cigar.shape[1])
+    c.recs, c.rec_first, c.aln, c.cigar, c.read_off, c.read_len, c.quals, c.n_reads = (sub, sub_first, aln, cigar, off[reads], lens[reads],
+                                                                                     quals, len(reads))
+    assert md.check(c) == 0
+    want = md.mark(c)[1]
+    keep = np.flatnonzero(pairs < n_sample)
+    keep = np.stack([2 * keep, 2 * keep + 1], axis=1).ravel()
+    got = dup[reads][keep]
+    if not np.array_equal(got, want[keep]):
+        raise SystemExit(f"d_dup differs from tests/markdup_py.py at {int((got != want[keep]).sum())} reads of the sample")
+    log(f"sample: {n_sample} pairs within {len(pairs)} (their sets), {int((got != 0).sum())} duplicate reads, == tests/markdup_py.py")
+    return {"sample_pairs": int(n_sample), "sample_pairs_with_sets": int(len(pairs)), "sample_dup_reads": int((got != 0).sum())}
+
+
+def markdup_legs(args, eng, fmi, ref, reads, off, lens, l_pac, share, log):
+    """the --markdup legs with a share of the fragments emitted a second time under fresh quals; returns the JSON fields"""
+    n_pairs = len(lens) // 2
+    extra = np.arange(0, n_pairs, int(round(1 / share)))[:int(share * n_pairs)] if share > 0 else np.zeros(0, np.int64)
+    ends = np.stack([2 * extra, 2 * extra + 1], axis=1).ravel()
+    if len(ends):
+        more = np.concatenate([reads[off[e]:off[e] + lens[e]] for e in ends])
+        off = np.concatenate([off, len(reads) + np.concatenate([[0], np.cumsum(lens[ends])[:-1]])]).astype(np.int64)
+        lens = np.concatenate([lens, lens[ends]]).astype(np.int32)
+        reads = np.concatenate([reads, more])
+    quals = (33 + (np.arange(len(reads)) * 7) % 41).astype(np.uint8)
+    if len(ends):                                                 # fresh quals for the second copies
+        quals[off[2 * n_pairs]:] = np.random.default_rng(3).integers(35, 74, len(reads) - int(off[2 * n_pairs]))
+    n = len(lens)
+    opt, sopt, popt = bsw.ext_opt(w=args.w, l_pac=l_pac), bsw.sel_opt(w=args.w, l_pac=l_pac), bsw.pe_opt(l_pac=l_pac)
+    ropt, dopt = bsw.rec_opt(w=args.w, l_pac=l_pac, rname="chrS"), bsw.markdup_opt(l_pac)
+    b = ResidentBatch(eng, reads, off, lens, quals=quals)
+    b.seed_and_chain(fmi)
+    b.chain2aln(opt)
+    b.select(sopt)
+    b.pe_pair(b.pe_stat(popt), popt)
+    b.records(ropt)
+    b.bam_records(ropt, [b"frag%08d" % i for i in range(n // 2)], True)
+    d_copy = hiprt.DeviceBuffer(len(reads))
+
+    def copy_quals():
+        hiprt.check(hiprt.rt().hipMemcpy(ctypes.c_void_p(d_copy.ptr), ctypes.c_void_p(b.buf["quals"].ptr), len(reads), hiprt.D2D))
+        hiprt.synchronize()
+
+    mark = lambda: b.mark_duplicates(dopt)  # noqa: E731
+    sort = lambda: b.bam_sort(1)  # noqa: E731
+    mark(), sort(), copy_quals()                                  # warm-up
+    tm, ts, tq, groups = [], [], [], {k: [] for k in ("score_ms", "key_ms", "sort_ms", "mark_ms")}
+    for _ in range(args.reps):
+        tm.append(timed(mark))
+        st = bsw.markdup_last_stats(eng)
+        for k in groups:
+            groups[k].append(getattr(st, k))
+        ts.append(timed(sort))
+        tq.append(timed(copy_quals))
+    dup = b.get("dup")
+    out = {"share": share, "pairs": n // 2, "reads": n, "records": int(b.n["recs"]), "quals_bytes": int(len(reads)),
+           "stats": {k: int(getattr(st, k)) for k in ("n_cand", "n_pair_cand", "n_dup_pairs", "n_dup_frag", "n_dup_frag_by_pair",
+                                                      "n_pair_sets", "n_end_sets", "n_flagged", "pair_key_bits", "end_key_bits",
+                                                      "pair_route", "end_route")},
+           "m_mark_duplicates_s": spread(tm), **{"m_" + k: spread(v) for k, v in groups.items()},
+           "s_bam_sort_s": spread(ts), "s_bam_bytes": int(b.n["bam"]), "q_memcpy_d2d_quals_s": spread(tq),
+           "m_over_s_median": round(spread(tm)["median"] / spread(ts)["median"], 3),
+           "score_ms_over_q_median": round(spread(groups["score_ms"])["median"] * 1e-3 / spread(tq)["median"], 3)}
+    log(f"markdup d={share}: {out['stats']}")
+    if share > 0:
+        out.update(check_sample(b, l_pac, quals, off, lens, dup, min(20000, n_pairs), log))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=1_000_000)
@@ -197,6 +311,8 @@ def main():
     ap.add_argument("--only-out", action="store_true")
     ap.add_argument("--bgzf", action="store_true")
     ap.add_argument("--sort", action="store_true")
+    ap.add_argument("--markdup", action="store_true")
+    ap.add_argument("--shares", default="0,0.1", help="--markdup: the shares of fragments emitted twice")
     ap.add_argument("--zlib-chunks", type=int, default=256)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -213,6 +329,19 @@ def main():
     log(f"index of {len(ref)} bases built in {time.perf_counter() - t0:.1f} s")
     eng = bsw.Engine()
     bsw.set_reference(eng, T)
+    if args.markdup:
+        out = {"tool": "rec_bench", "legs": "markdup", "lib": os.path.basename(bsw.HIP_LIB), "read_len": args.read_len,
+               "ref_mb": args.ref_mb, "reps": args.reps,
+               "runs": [markdup_legs(args, eng, fmi, ref, reads, off, lens, l_pac, d, log) for d in map(float, args.shares.split(","))]}
+        line = json.dumps(out)
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        eng.close()
+        fmi.close()
+        return
     opt = bsw.ext_opt(w=args.w, l_pac=l_pac)
     sopt = bsw.sel_opt(w=args.w, l_pac=l_pac)
     popt = bsw.pe_opt(l_pac=l_pac)
